@@ -6,7 +6,7 @@ already resident in HBM: build the per-call row tables, run the Gram kernel for 
 all-gather the row slabs over RCCL (N > 1), normalise the assembled matrix (division by the self
 norms, unit diagonal) on every rank.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload c2|peaks|c3|c5]
+    python bench.py [--gpus N --steps K --warmup W] [--workload c2|peaks|c3|c5] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1 (`--assembly auto`, the default) measures BOTH multi-GPU drivers, each in fresh processes with a timeout:
@@ -22,6 +22,9 @@ PARITY GATE: after the timed region the matrix the last timed step produced is c
 its strict lower triangle (the cells the reference writes, src/gkmkern_pylib.c:83,218-221) is compared with the digest
 of the reference's own matrix (tests/golden/<workload>_full_digest.npz) -- on every rank's / device's copy for N > 1.
 A mismatch sets `value` aside (`parity_failed`, exit code 3).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes a fixed, seeded sample of that same matrix (values and their
+coordinates, about 32 MiB) to DIR/*.npy (dump_outputs()), so that two builds can be compared output for output.
 
 Rank 0 prints ONE JSON line.  `value` = N(N-1)/2 pairs / (max-over-ranks seconds per step).
 The total work is fixed as the GPU count grows (the N x N matrix is sharded by row block), so
@@ -227,6 +230,46 @@ def merge_parity(per_copy):
             if key in out:
                 out[key] = max(p[key] for p in per_copy)
     return out
+
+
+# --dump-outputs: cells of the lower triangle written (values float64 + coordinates 2 x float32: 32 MiB in all)
+DUMP_CELLS = 1 << 21
+DUMP_SEED = 20261015
+
+
+def dump_outputs(K, outdir):
+    """--dump-outputs: what the timed path hands its caller -- the normalised n x n matrix, of which the lower triangle
+    with its unit diagonal is written (symmetric=False: the upper triangle is never touched) -- as .npy files in
+    `outdir`:
+      K_lower_sample.npy  float64, K[row, col] at DUMP_CELLS cells of the lower triangle drawn with DUMP_SEED (every cell
+                          when the triangle has no more), in row-major order
+      K_lower_rows.npy    float32, the row of each cell (exact: n < 2^24)
+      K_lower_cols.npy    float32, its column
+    The cells depend on n alone, so two builds run with the same arguments can be compared file for file.
+    K: torch tensor on any device.  -> what the line records about the dump."""
+    import numpy as np
+    import torch
+    n = K.shape[0]
+    assert n < (1 << 24), "coordinates are stored as float32"
+    total = n * (n + 1) // 2
+    if total <= DUMP_CELLS:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(total, DUMP_CELLS, replace=False))
+    starts = np.arange(n, dtype=np.int64) * (np.arange(n, dtype=np.int64) + 1) // 2
+    rows = np.searchsorted(starts, idx, side="right") - 1
+    cols = idx - starts[rows]
+    vals = K[torch.from_numpy(rows).to(K.device), torch.from_numpy(cols).to(K.device)].cpu().numpy()
+    arrays = {"K_lower_sample": vals.astype(np.float64), "K_lower_rows": rows.astype(np.float32),
+              "K_lower_cols": cols.astype(np.float32)}
+    os.makedirs(outdir, exist_ok=True)
+    nbytes = 0
+    for name, a in arrays.items():
+        path = os.path.join(outdir, name + ".npy")
+        np.save(path, a)
+        nbytes += os.path.getsize(path)
+    return {"dir": outdir, "files": sorted(name + ".npy" for name in arrays), "bytes": nbytes, "cells": int(len(idx)),
+            "cells_in_lower_triangle": total, "seed": DUMP_SEED if total > DUMP_CELLS else None}
 
 
 def make_problem(args):
@@ -451,7 +494,13 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-end-to-end", action="store_true")
     ap.add_argument("--check", action="store_true", help="compare the assembled matrix with a 1-GPU run (debug)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of the matrix the last one produced to DIR/*.npy")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     w = WORKLOADS[args.workload]
     custom = False
     for i, name in enumerate(("n_pos", "n_neg", "length", "length_range", "kernel_type", "L", "k", "d")):
@@ -618,6 +667,11 @@ def brief_line(line):
             "allgather_GBps_per_rank": rf.get("allgather_GBps_per_rank")}
 
 
+def _cabi_counts(cabi_line, cabi_err):
+    """The C-ABI child's line is the merged line's (merge_assemblies)."""
+    return cabi_line is not None and not cabi_err and not cabi_line.get("parity_failed")
+
+
 def merge_assemblies(cabi_line, cabi_err, torch_line, torch_err, torch_rc=0):
     """-> (the line to print, exit code).  Primary = the product's own entry (gkmhip_gram_allgather); the
     torch.distributed ranks are the cross-check and, when the primary CRASHES or is killed at its timeout, the fallback
@@ -627,8 +681,7 @@ def merge_assemblies(cabi_line, cabi_err, torch_line, torch_err, torch_rc=0):
     cabi_parity_failed = bool(cabi_line and cabi_line.get("parity_failed"))
     torch_parity_failed = bool(torch_line and torch_line.get("parity_failed"))
     torch_failed = bool(torch_rc) and not torch_parity_failed
-    cabi_ok = cabi_line is not None and not cabi_err and not cabi_parity_failed
-    if cabi_ok:
+    if _cabi_counts(cabi_line, cabi_err):
         out = cabi_line
         out["assembly"] = "cabi: gkmhip_gram_allgather (one process, one host thread per device)"
         also = brief_line(torch_line) if torch_line else {"error": torch_err or "no line"}
@@ -673,6 +726,8 @@ def run_auto(args, argv):
     if "WORLD_SIZE" not in os.environ:
         # no launcher: this process orchestrates and never touches a GPU
         cabi_line, cabi_err = run_cabi_child(args, argv)
+        if _cabi_counts(cabi_line, cabi_err):     # --dump-outputs: the child wrote the line's matrix
+            torch_argv = _strip_flag(torch_argv, "--dump-outputs")
         captured = []
         rc = launch_ranks(targs, torch_argv, capture=captured)
         torch_line = _last_json_line(captured[0]) if captured else None
@@ -699,6 +754,8 @@ def run_auto(args, argv):
                 if os.path.exists(stale):
                     os.unlink(stale)
             cabi_line, cabi_err = run_cabi_child(args, argv)
+            if _cabi_counts(cabi_line, cabi_err):
+                targs.dump_outputs = None
         finally:
             with open(sync + ".tmp", "w") as f:
                 json.dump({"line": cabi_line, "error": cabi_err, "written_at": time.time()}, f)
@@ -965,6 +1022,7 @@ def run_rank(args, emit=None):
         dist.all_gather_object(gathered_par, parity_mine[0])
         parity_mine = gathered_par
     parity = merge_parity(parity_mine)
+    dumped = dump_outputs(full, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     # dominant kernel: extra launches bracketed by HIP events on the launch stream (recorded inside
     # gkmhip_gram_rows), outside the wall-clock region
@@ -1064,6 +1122,8 @@ def run_rank(args, emit=None):
     }
     # the parity gate: a matrix that is not the reference's, on any copy, sets the number aside
     out["parity"] = parity
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     parity_failed = parity is not None and parity.get("ok") is False
     if parity_failed:
         out["parity_failed"] = True

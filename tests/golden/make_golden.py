@@ -6,6 +6,7 @@ Run in the development container only (needs /root/reference):
     make -C oracle all ref
     python tests/golden/make_golden.py            # everything except the full C2 run
     python tests/golden/make_golden.py --c2-full  # + full 10 000 x 10 000 reference run (minutes)
+    python tests/golden/make_golden.py --only-ragged  # only ragged_expected.npz
 
 The reference has no tests or known-answer vectors of its own, so
 every expected value here is an OUTPUT OF THE REFERENCE ITSELF:
@@ -145,6 +146,31 @@ def write_batch_rows(tmp):
     np.savez_compressed(os.path.join(HERE, "batch_rows_expected.npz"), **out)
 
 
+# (viii) a small ragged problem (45 sequences of 40-400 bp) through the reference's profiles and gkm_main_pywrapper
+# name: (seed, n, length, length_range, length_seed) per file; params: (kernel_type, L, k, d, M, H, gamma)
+RAGGED_FILES = {"pos": (11, 20, 120, (40, 400), 5), "neg": (12, 25, 120, (40, 400), 6)}
+RAGGED_PARAMS = [(4, 11, 7, 3, 50, 50.0, 1.5), (5, 12, 8, 4, 50, 50.0, 1.5), (0, 7, 4, 3, 50, 50.0, 1.5)]
+
+
+def write_ragged(tmp):
+    out = {}
+    paths = {}
+    for name, (seed, n, ln, lr, ls) in RAGGED_FILES.items():
+        paths[name] = os.path.join(tmp, "ragged_%s.fa" % name)
+        synth.write_fasta(paths[name], synth.make_sequences(seed, n, ln, lr, ls), name[0])
+        out[name + "_cfg"] = np.array([seed, n, ln, lr[0], lr[1], ls])
+    for idx, (t, L, k, d, M, H, g) in enumerate(RAGGED_PARAMS):
+        opt = O.make_opt(t, L, k, d, M, H, g, paths["pos"], paths["neg"], nthreads=4)
+        r = O.ref_profiles(opt)
+        n = r["n"]
+        K, _ = ref_K(opt, n)
+        out["p%d_params" % idx] = np.array([t, L, k, d, M, H, g], dtype=np.float64)
+        out["p%d_P" % idx] = r["P"][np.tril_indices(n)]
+        out["p%d_K" % idx] = tril_pack(K)
+        print("ragged", (t, L, k, d, M, H, g), "N", n)
+    np.savez_compressed(os.path.join(HERE, "ragged_expected.npz"), **out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--c2-full", action="store_true")
@@ -153,6 +179,7 @@ def main():
     ap.add_argument("--only-full", action="store_true", help="skip the small fixtures")
     ap.add_argument("--only-batch", action="store_true",
                     help="only batch_rows_expected.npz (the reference's batch-vs-set scoring entry)")
+    ap.add_argument("--only-ragged", action="store_true", help="only ragged_expected.npz (a small ragged problem)")
     ap.add_argument("--threads", type=int, default=os.cpu_count(), help="row threads of the reference for --full")
     args = ap.parse_args()
     if not O.have_ref():
@@ -160,6 +187,10 @@ def main():
 
     tmp = os.path.join(ROOT, "gpurun_out", "golden_tmp")
     os.makedirs(tmp, exist_ok=True)
+    if args.only_ragged or not (args.only_full or args.only_batch):
+        write_ragged(tmp)
+    if args.only_ragged:
+        return
     if args.only_batch or not args.only_full:
         write_batch_rows(tmp)
     if args.only_batch:

@@ -62,6 +62,26 @@ def synth_codes(n_pos, n_neg, length=300, length_range=None):
     return [encode(s) for s in pos + neg]
 
 
+def ragged_expected():
+    """tests/golden/ragged_expected.npz: a small ragged problem through the reference's profiles and gkm_main_pywrapper
+    (tests/golden/make_golden.py --only-ragged).  -> (files, cases): files maps "pos" / "neg" to the arguments of
+    synth.make_sequences; each case holds the parameters, P over the lower triangle with the diagonal (row-major) and K
+    over the strict lower triangle."""
+    z = np.load(os.path.join(GOLDEN, "ragged_expected.npz"))
+    files = {}
+    for name in ("pos", "neg"):
+        seed, n, ln, lo, hi, ls = (int(x) for x in z[name + "_cfg"])
+        files[name] = (seed, n, ln, (lo, hi), ls)
+    cases = []
+    i = 0
+    while "p%d_params" % i in z:
+        t, L, k, d, M, H, g = z["p%d_params" % i]
+        cases.append(dict(kernel_type=int(t), L=int(L), k=int(k), d=int(d), M=int(M), H=float(H), gamma=float(g),
+                          P=z["p%d_P" % i], K=z["p%d_K" % i]))
+        i += 1
+    return files, cases
+
+
 def batch_rows_expected():
     """tests/golden/batch_rows_expected.npz: the reference's gkmkernel_kernelfunc_batch (src/libgkm.c:1115-1153) driven
     by tests/golden/make_golden.py --only-batch.  -> list of dict(name, n_support, n_query, length, length_range,

@@ -137,6 +137,86 @@ def test_gpus_2_under_the_launcher_prints_its_line_on_stdout(built):
     assert d["parity"]["checked_copies"] == 2
 
 
+def _load_dump(d):
+    import numpy as np
+    vals = np.load(os.path.join(d, "K_lower_sample.npy"))
+    rows = np.load(os.path.join(d, "K_lower_rows.npy"))
+    cols = np.load(os.path.join(d, "K_lower_cols.npy"))
+    assert vals.dtype == np.float64 and rows.dtype == cols.dtype == np.float32 and vals.shape == rows.shape == cols.shape
+    return vals, rows.astype(np.int64), cols.astype(np.int64)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_holds_the_timed_matrix(built, tmp_path):
+    """--dump-outputs on a workload small enough to be written whole (C1: 400 sequences): the lower triangle of the matrix
+    the last of exactly --steps timed steps produced, against the reference's matrix; the unit diagonal included."""
+    import numpy as np
+    from tests import helpers
+    d = _one_line(_run(["--workload", "c1", "--steps", "3", "--warmup", "0", "--no-end-to-end", "--no-cpu-baseline",
+                        "--dump-outputs", str(tmp_path / "out")]))
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["parity"]["ok"] is True
+    assert "timed steps" in d["roofline"]["kernel_ms_source"]    # one Gram launch per timed step, 3 of them
+    n = 400
+    assert d["dump_outputs"]["cells"] == n * (n + 1) // 2 and d["dump_outputs"]["bytes"] <= 64 << 20
+    vals, rows, cols = _load_dump(tmp_path / "out")
+    assert (rows == np.tril_indices(n)[0]).all() and (cols == np.tril_indices(n)[1]).all()
+    assert (vals[rows == cols] == 1.0).all()
+    K = np.zeros((n, n))
+    K[rows, cols] = vals
+    assert helpers.max_rel_err(helpers.tril_pack(K), helpers.synthetic_expected()["c1_full_K"]) < 1e-6
+
+
+@pytest.mark.gpu
+def test_dump_outputs_with_two_ranks(built, tmp_path):
+    """`--gpus 2` (two ranks sharing the box's one GPU): the dump is the line's matrix, and it is the one-GPU matrix."""
+    import numpy as np
+    one = _one_line(_run(SMALL + ["--no-end-to-end", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "one")]))
+    two = _one_line(_run(["--gpus", "2", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "two")] + SMALL,
+                         {"GKM_BENCH_SHARE_GPU": "1", "GKM_BENCH_BACKEND": "gloo"}))
+    assert two["assembly"].startswith("cabi") and two["dump_outputs"]["cells"] == one["dump_outputs"]["cells"]
+    for a, b in zip(_load_dump(tmp_path / "one"), _load_dump(tmp_path / "two")):
+        assert np.array_equal(a, b)
+
+
+def test_dump_outputs_is_a_fixed_sample_of_the_lower_triangle(tmp_path, monkeypatch):
+    """bench.dump_outputs: every cell of a small lower triangle; of a larger one, the same seeded, sorted sample of
+    DUMP_CELLS distinct cells on every call, never above the diagonal, with the values at those cells."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.DUMP_CELLS * (8 + 4 + 4) + 3 * 4096 <= 64 << 20       # the size limit of a dump
+    rng = np.random.default_rng(3)
+    K = torch.from_numpy(np.tril(rng.random((60, 60))) + np.triu(np.full((60, 60), 7.0), 1))
+    info = bench.dump_outputs(K, str(tmp_path / "small"))
+    vals, rows, cols = _load_dump(tmp_path / "small")
+    assert info["cells"] == 60 * 61 // 2 and info["seed"] is None and sorted(info["files"]) == info["files"]
+    assert (rows == np.tril_indices(60)[0]).all() and (cols == np.tril_indices(60)[1]).all()
+    assert np.array_equal(vals, K.numpy()[rows, cols])
+    monkeypatch.setattr(bench, "DUMP_CELLS", 1000)
+    K = torch.from_numpy(np.tril(rng.random((300, 300))) + np.triu(np.full((300, 300), 7.0), 1))
+    info = bench.dump_outputs(K, str(tmp_path / "a"))
+    bench.dump_outputs(K * 2.0, str(tmp_path / "b"))
+    va, ra, ca = _load_dump(tmp_path / "a")
+    vb, rb, cb = _load_dump(tmp_path / "b")
+    assert info["cells"] == 1000 and info["cells_in_lower_triangle"] == 300 * 301 // 2 and info["seed"] is not None
+    assert np.array_equal(ra, rb) and np.array_equal(ca, cb) and (cb <= rb).all()
+    lin = ra * 300 + ca
+    assert (np.diff(lin) > 0).all()                                   # row-major, distinct
+    assert np.array_equal(va, K.numpy()[ra, ca]) and np.array_equal(vb, 2.0 * va)
+
+
+def test_steps_and_dump_arguments():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "0", "--dump-outputs", "rel/dir"])
+    assert a.steps == 7 and a.warmup == 0 and a.dump_outputs == os.path.abspath("rel/dir")
+    assert bench.parse_args([]).dump_outputs is None
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
 def test_headline_roofline_uses_only_a_matching_pmc_summary(tmp_path, monkeypatch):
     """frac comes from rocprofv3 SQ_INSTS_VALU of the committed summary; a summary taken on other kernel
     code (hash mismatch) or another workload must be refused."""

@@ -93,27 +93,22 @@ def test_pywrapper_restatement_matches_reference_cells(O):
     assert helpers.max_rel_err(helpers.tril_pack(kmat[:n, :n]), c["K"]) < 1e-12
 
 
-@pytest.mark.skipif(not __import__("os").path.exists("/root/reference/src/libgkm.c"),
-                    reason="the reference only exists in the development container")
-def test_oracle_vs_live_reference(O, tmp_path):
-    """Where the reference can be run: a fresh random problem through both."""
-    if not O.have_ref():
-        pytest.skip("oracle/_ref not built")
+def test_oracle_vs_reference_on_a_ragged_problem(O, tmp_path):
+    """A ragged random problem (45 sequences of 40-400 bp) through the oracle against the reference's profiles and
+    matrix (fixture made by tests/golden/make_golden.py --only-ragged)."""
     from gkmqc_amd import synth
-    pos = synth.make_sequences(11, 20, 120, (40, 400), 5)
-    neg = synth.make_sequences(12, 25, 120, (40, 400), 6)
+    files, cases = helpers.ragged_expected()
     pf, nf = str(tmp_path / "p.fa"), str(tmp_path / "n.fa")
-    synth.write_fasta(pf, pos, "p")
-    synth.write_fasta(nf, neg, "n")
-    for (t, L, k, d) in [(4, 11, 7, 3), (5, 12, 8, 4), (0, 7, 4, 3)]:
-        opt = O.make_opt(t, L, k, d, 50, 50.0, 1.5, pf, nf, nthreads=4)
-        ref = O.ref_profiles(opt)
+    synth.write_fasta(pf, synth.make_sequences(*files["pos"]), "p")
+    synth.write_fasta(nf, synth.make_sequences(*files["neg"]), "n")
+    assert len(cases) == 3
+    for c in cases:
+        opt = O.make_opt(c["kernel_type"], c["L"], c["k"], c["d"], c["M"], c["H"], c["gamma"], pf, nf, nthreads=4)
         mine = O.gram(opt, nthreads=8)
-        il = np.tril_indices(ref["n"])
-        assert (mine["P"][il] == ref["P"][il]).all()
-        rc, kref, _, _ = O.ref_pywrapper(opt, ref["n"])
-        assert rc == 0
-        assert helpers.max_rel_err(helpers.tril_pack(mine["K"]), helpers.tril_pack(kref)) < 1e-12
+        n = mine["n"]
+        assert n == files["pos"][1] + files["neg"][1] and mine["n_pos"] == files["pos"][1]
+        assert (mine["P"][np.tril_indices(n)] == c["P"]).all()
+        assert helpers.max_rel_err(helpers.tril_pack(mine["K"]), c["K"]) < 1e-12
 
 
 def test_batch_rows_fixture_is_the_symmetric_completion(O, tmp_path):
