@@ -101,6 +101,7 @@ struct DirectArgs {
     double c[GKM_MAXD1];
     GramOut out;
     int cj, L, d, mode, n;
+    int col_begin, col_end; /* COLS_RANGE: the launch's columns */
 };
 
 /*
@@ -118,7 +119,8 @@ __global__ __launch_bounds__(64) void k_gram_direct(const DirectArgs A)
     const int ridx = tile * 64 + lane;
     const int a = ridx < A.nrows ? A.rows[ridx] : -1;
     const int amin = A.rows[tile * 64], amax = A.rows[min(tile * 64 + 63, A.nrows - 1)];
-    const int cbeg = A.mode == COLS_DIAGONAL ? amin : 0, cend = A.mode == COLS_FULL ? A.n : amax + 1;
+    const int cbeg = A.mode == COLS_RANGE ? A.col_begin : A.mode == COLS_DIAGONAL ? amin : 0;
+    const int cend = A.mode == COLS_RANGE ? A.col_end : A.mode == COLS_FULL ? A.n : amax + 1;
     const int j0 = cbeg + blockIdx.x * A.cj;
     const int j1 = min(j0 + A.cj, cend);
     if (j0 >= j1) return;
@@ -243,8 +245,10 @@ struct BitslicePlan {
 
 /* Pack the rows, choose the kernel variant, fill the per-lane tables, the tiles' column ranges and the work-item order.
  * mode says which columns every tile of rows visits: COLS_TRIANGLE j <= largest row of the tile (the path of
- * gkm_main_pywrapper), COLS_FULL every sequence, COLS_DIAGONAL only the band of the tile's own rows (self norms). */
-static int plan_bitslice(const gkmhip_ctx *ctx, const int *rows, int nrows, int mode, BitslicePlan &P)
+ * gkm_main_pywrapper), COLS_FULL every sequence, COLS_DIAGONAL only the band of the tile's own rows (self norms),
+ * COLS_RANGE the columns [col_begin, col_end) whatever the rows (scoring: support vectors x a block of queries). */
+static int plan_bitslice(const gkmhip_ctx *ctx, const int *rows, int nrows, int mode, int col_begin, int col_end,
+                         BitslicePlan &P)
 {
     const int L = ctx->L, d = ctx->d, n = ctx->n;
     std::vector<int> nwin((size_t)nrows);
@@ -259,7 +263,8 @@ static int plan_bitslice(const gkmhip_ctx *ctx, const int *rows, int nrows, int 
      * items: gkm_pack.h) */
     auto pack = [&](int max_rows) {
         gkmpack::Packing a = gkmpack::pack_rows(rows, nwin.data(), nrows, 10, L, max_rows, 0, own_mult);
-        if (mode == COLS_FULL || rows[nrows - 1] - rows[0] + 1 == nrows) return a; /* (no jump, or every tile visits all columns) */
+        if (mode == COLS_FULL || mode == COLS_RANGE || rows[nrows - 1] - rows[0] + 1 == nrows)
+            return a; /* (no jump, or every tile visits the same columns) */
         gkmpack::Packing b = gkmpack::pack_rows(rows, nwin.data(), nrows, 10, L, max_rows, gkmpack::LANES, own_mult);
         return gkmpack::triangle_items(b) < gkmpack::triangle_items(a) ? b : a;
     };
@@ -330,8 +335,8 @@ static int plan_bitslice(const gkmhip_ctx *ctx, const int *rows, int nrows, int 
     for (int t = 0; t < ntiles; t++) {
         int amin = n;
         for (int rs = 0; rs < pk.tile_nrows[(size_t)t]; rs++) amin = std::min(amin, pk.tile_row[(size_t)t * gkmpack::MAX_ROWS + rs]);
-        P.cbeg[(size_t)t] = mode == COLS_DIAGONAL ? amin : 0;
-        P.cend[(size_t)t] = mode == COLS_FULL ? n : pk.tile_amax[(size_t)t] + 1;
+        P.cbeg[(size_t)t] = mode == COLS_RANGE ? col_begin : mode == COLS_DIAGONAL ? amin : 0;
+        P.cend[(size_t)t] = mode == COLS_RANGE ? col_end : mode == COLS_FULL ? n : pk.tile_amax[(size_t)t] + 1;
         P.soff[(size_t)t + 1] = P.soff[(size_t)t] + (P.cend[(size_t)t] - P.cbeg[(size_t)t]);
     }
     if (P.soff[(size_t)ntiles] <= 0 || P.soff[(size_t)ntiles] > 0x7fffffffLL) return set_err_msg("gram: bad work item count", 2);
@@ -350,9 +355,11 @@ static int plan_bitslice(const gkmhip_ctx *ctx, const int *rows, int nrows, int 
     const double col_bytes = (4.0 * (mean_len + W) + 2.0 * (mean_len / 16.0 + 1.0)) * sizeof(uint32_t);
     long chunk = col_bytes * 4096.0 / 8.0 <= 3.0 * 1048576.0 ? 4096 : 0;
     if (const char *cc = getenv("GKM_COL_CHUNK")) chunk = atol(cc) & ~7L;
-    if (chunk >= 8 && chunk < n) {
+    /* (the chunks walk the columns a launch can visit: [0, n), or the range of a COLS_RANGE launch) */
+    const long c_lo = mode == COLS_RANGE ? col_begin : 0, c_hi = mode == COLS_RANGE ? col_end : n;
+    if (chunk >= 8 && chunk < c_hi - c_lo) {
         int64_t at = 0;
-        for (long c0 = 0; c0 < n; c0 += chunk)
+        for (long c0 = c_lo; c0 < c_hi; c0 += chunk)
             for (int t = 0; t < ntiles; t++) {
                 const int j0 = std::max<long>(P.cbeg[(size_t)t], c0), j1 = (int)std::min<long>(P.cend[(size_t)t], c0 + chunk);
                 if (j0 >= j1) continue;
@@ -486,7 +493,8 @@ static int enqueue_bitslice(gkmhip_ctx *ctx, const BitslicePlan &P, int nrows, G
 }
 
 /* ---- the general kernel's launch ---- */
-static int enqueue_direct(gkmhip_ctx *ctx, const int *rows, int nrows, int mode, GramOut out, hipStream_t stream)
+static int enqueue_direct(gkmhip_ctx *ctx, const int *rows, int nrows, int mode, int col_begin, int col_end, GramOut out,
+                          hipStream_t stream)
 {
     const int n = ctx->n;
     auto &scr = ctx->scratch[ctx->sel];
@@ -505,12 +513,14 @@ static int enqueue_direct(gkmhip_ctx *ctx, const int *rows, int nrows, int mode,
     for (int m = 0; m < GKM_MAXD1; m++) A.c[m] = ctx->c[m];
     A.out = out;
     A.L = ctx->L; A.d = ctx->d; A.mode = mode; A.n = n;
+    A.col_begin = col_begin; A.col_end = col_end;
     const unsigned ntiles = (unsigned)((nrows + 63) / 64);
     int span = 0; /* widest column range of any 64-row tile */
     double items = 0; /* (tile, column) pairs of the launch */
     for (unsigned t = 0; t < ntiles; t++) {
         const int amin = rows[t * 64], amax = rows[std::min<int>((int)t * 64 + 63, nrows - 1)];
-        const int cols = mode == COLS_FULL ? n : mode == COLS_DIAGONAL ? amax + 1 - amin : amax + 1;
+        const int cols = mode == COLS_RANGE ? col_end - col_begin : mode == COLS_FULL ? n : mode == COLS_DIAGONAL ? amax + 1 - amin
+                                                                                                            : amax + 1;
         span = std::max(span, cols);
         items += cols;
     }
@@ -528,22 +538,28 @@ static int enqueue_direct(gkmhip_ctx *ctx, const int *rows, int nrows, int mode,
     return 0;
 }
 
-/* One launch of the Gram kernel for a set of rows (mode: see plan_bitslice). */
-static int gram_launch(gkmhip_ctx *ctx, const int *rows, int nrows, int mode, GramOut out, hipStream_t stream)
+/* One launch of the Gram kernel for a set of rows (mode: see plan_bitslice; [col_begin, col_end) for COLS_RANGE). */
+static int gram_launch(gkmhip_ctx *ctx, const int *rows, int nrows, int mode, GramOut out, hipStream_t stream,
+                       int col_begin = 0, int col_end = 0)
 {
     if (!ctx || !rows || nrows <= 0) return set_err_msg("gram: bad arguments", 2);
     if (ctx->n <= 0) return set_err_msg("gram: no sequences uploaded", 2);
     HIPCHK(hipSetDevice(ctx->device));
     (void)hipGetLastError(); /* the launch checks below must see this call's errors only */
     const int L = ctx->L, d = ctx->d, n = ctx->n;
+    if (mode == COLS_RANGE && (col_begin < 0 || col_end > n || col_begin >= col_end))
+        return set_err_msg("gram: the column range must satisfy 0 <= col_begin < col_end <= n", 2);
     double comparisons = 0;
     for (int i = 0; i < nrows; i++) {
         if (rows[i] < 0 || rows[i] >= n || (i > 0 && rows[i] <= rows[i - 1]))
             return set_err_msg("rows must be strictly ascending sequence indices", 2);
         const double na = (double)(ctx->h_len[(size_t)rows[i]] - L + 1);
-        comparisons += 2.0 * na * (mode == COLS_FULL ? ctx->h_cum_n[(size_t)n] : mode == COLS_DIAGONAL ? na : ctx->h_cum_n[(size_t)rows[i] + 1]);
+        comparisons += 2.0 * na * (mode == COLS_RANGE ? ctx->h_cum_n[(size_t)col_end] - ctx->h_cum_n[(size_t)col_begin]
+                                   : mode == COLS_FULL ? ctx->h_cum_n[(size_t)n] : mode == COLS_DIAGONAL ? na
+                                   : ctx->h_cum_n[(size_t)rows[i] + 1]);
     }
-    out.write_all = mode == COLS_FULL ? 1 : 0;
+    out.write_all = mode == COLS_FULL || mode == COLS_RANGE ? 1 : 0;
+    out.col0 = mode == COLS_RANGE ? col_begin : 0;
     /* (W = 10 words per lane; W = 20 was measured too -- config 2: 121 vs 118 ms, 150 bp: 56 vs 31 ms in round 1: the longer
      * per-shift chain does not pay for the registers it costs) */
     if (ctx->kernel_pref == GKMHIP_KERNEL_BITSLICE && !gkm_pick_bitslice(2, L, d))
@@ -553,10 +569,10 @@ static int gram_launch(gkmhip_ctx *ctx, const int *rows, int nrows, int mode, Gr
         /* the per-sequence tables (normally built by gkmhip_set_sequences); ctx->pkw and ctx->ptw size the plan's dynamic LDS */
         if (ensure_sb(ctx, 10, stream) || ensure_colpk(ctx, stream) || ensure_postab(ctx, stream)) return 4;
         BitslicePlan P;
-        rc = plan_bitslice(ctx, rows, nrows, mode, P);
+        rc = plan_bitslice(ctx, rows, nrows, mode, col_begin, col_end, P);
         if (!rc) rc = enqueue_bitslice(ctx, P, nrows, out, stream);
     } else {
-        rc = enqueue_direct(ctx, rows, nrows, mode, out, stream);
+        rc = enqueue_direct(ctx, rows, nrows, mode, col_begin, col_end, out, stream);
     }
     if (rc) return rc;
     ctx->ev_valid = true;
@@ -574,7 +590,7 @@ extern "C" int gkmhip_gram_rows(gkmhip_ctx *ctx, const int *rows, int nrows, int
     if (!G || !rows || nrows <= 0) return set_err_msg("gkmhip_gram_rows: bad arguments", 2);
     if (ld <= rows[nrows - 1]) return set_err_msg("leading dimension too small", 2);
     GramOut out;
-    out.G = G; out.ld = ld; out.P = P; out.ldp = ldp; out.local_rows = local_rows; out.write_all = 0; out.diag = nullptr; out.row_off = nullptr;
+    out.G = G; out.ld = ld; out.P = P; out.ldp = ldp; out.local_rows = local_rows; out.write_all = 0; out.diag = nullptr; out.row_off = nullptr; out.col0 = 0;
     return gram_launch(ctx, rows, nrows, COLS_TRIANGLE, out, (hipStream_t)stream_);
 }
 
@@ -587,7 +603,7 @@ extern "C" int gkmhip_gram_rows_packed(gkmhip_ctx *ctx, const int *rows, int nro
             return set_err_msg("gkmhip_gram_rows_packed: row offsets must leave rows[i] + 1 doubles per row", 2);
     GramOut out;
     out.G = G; out.ld = 0; out.P = nullptr; out.ldp = 0; out.local_rows = 1; out.write_all = 0; out.diag = nullptr;
-    out.row_off = row_off;
+    out.row_off = row_off; out.col0 = 0;
     return gram_launch(ctx, rows, nrows, COLS_TRIANGLE, out, (hipStream_t)stream_);
 }
 
@@ -597,8 +613,20 @@ extern "C" int gkmhip_gram_rows_full(gkmhip_ctx *ctx, const int *rows, int nrows
     if (!ctx || !G || !rows || nrows <= 0) return set_err_msg("gkmhip_gram_rows_full: bad arguments", 2);
     if (ld < ctx->n) return set_err_msg("leading dimension too small", 2);
     GramOut out;
-    out.G = G; out.ld = ld; out.P = nullptr; out.ldp = 0; out.local_rows = local_rows; out.write_all = 1; out.diag = nullptr; out.row_off = nullptr;
+    out.G = G; out.ld = ld; out.P = nullptr; out.ldp = 0; out.local_rows = local_rows; out.write_all = 1; out.diag = nullptr; out.row_off = nullptr; out.col0 = 0;
     return gram_launch(ctx, rows, nrows, COLS_FULL, out, (hipStream_t)stream_);
+}
+
+extern "C" int gkmhip_gram_block(gkmhip_ctx *ctx, const int *rows, int nrows, int col_begin, int col_end, double *G,
+                                 int64_t ld, void *stream_)
+{
+    if (!ctx || !G || !rows || nrows <= 0) return set_err_msg("gkmhip_gram_block: bad arguments", 2);
+    if (col_begin < 0 || col_end > ctx->n || col_begin >= col_end)
+        return set_err_msg("gkmhip_gram_block: the column range must satisfy 0 <= col_begin < col_end <= n", 2);
+    if (ld < col_end - col_begin) return set_err_msg("leading dimension too small", 2);
+    GramOut out;
+    out.G = G; out.ld = ld; out.P = nullptr; out.ldp = 0; out.local_rows = 1; out.write_all = 1; out.diag = nullptr; out.row_off = nullptr; out.col0 = col_begin;
+    return gram_launch(ctx, rows, nrows, COLS_RANGE, out, (hipStream_t)stream_, col_begin, col_end);
 }
 
 __global__ void k_sqrt_inplace(double *__restrict__ v, int n)
@@ -614,7 +642,7 @@ extern "C" int gkmhip_self_norms(gkmhip_ctx *ctx, double *sqnorm, void *stream_)
     std::vector<int> all((size_t)ctx->n);
     for (int i = 0; i < ctx->n; i++) all[(size_t)i] = i;
     GramOut out;
-    out.G = nullptr; out.ld = 0; out.P = nullptr; out.ldp = 0; out.local_rows = 0; out.write_all = 0; out.diag = sqnorm; out.row_off = nullptr;
+    out.G = nullptr; out.ld = 0; out.P = nullptr; out.ldp = 0; out.local_rows = 0; out.write_all = 0; out.diag = sqnorm; out.row_off = nullptr; out.col0 = 0;
     const int rc = gram_launch(ctx, all.data(), ctx->n, COLS_DIAGONAL, out, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(k_sqrt_inplace, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, stream, sqnorm, ctx->n);

@@ -187,6 +187,11 @@ struct gkm_problem {
     uint8_t *codes;  /* concatenated base codes 0..3 */
     int64_t used, codes_cap;
     long invalid, truncated;
+    /* headers (gkm_problem_read_one only): record i's is names + name_off[i], NUL-terminated */
+    int keep_names;
+    char *names;
+    int64_t *name_off;
+    int64_t names_used, names_cap;
 };
 
 static int problem_reserve(gkm_problem *p, int64_t extra)
@@ -196,6 +201,11 @@ static int problem_reserve(gkm_problem *p, int64_t extra)
         int64_t *no = (int64_t *)realloc(p->off, sizeof(int64_t) * (size_t)(ncap + 1));
         if (!no) return 1;
         p->off = no;
+        if (p->keep_names) {
+            int64_t *nn = (int64_t *)realloc(p->name_off, sizeof(int64_t) * (size_t)(ncap + 1));
+            if (!nn) return 1;
+            p->name_off = nn;
+        }
         p->cap = ncap;
     }
     if (p->used + extra > p->codes_cap) {
@@ -254,6 +264,21 @@ static int parse_fasta(const char *path, gkm_problem *p)
             open_record = 1;
             cur = 0;
             p->off[p->n] = p->used;
+            if (p->keep_names) { /* the header after '>', up to the end of the logical line */
+                const size_t len = end - pos - 1;
+                if (p->names_used + (int64_t)len + 1 > p->names_cap) {
+                    int64_t ncap = p->names_cap ? p->names_cap * 2 : (1 << 16);
+                    while (ncap < p->names_used + (int64_t)len + 1) ncap *= 2;
+                    char *nn = (char *)realloc(p->names, (size_t)ncap);
+                    if (!nn) { munmap((void *)buf, size); return 1; }
+                    p->names = nn;
+                    p->names_cap = ncap;
+                }
+                memcpy(p->names + p->names_used, buf + pos + 1, len);
+                p->name_off[p->n] = p->names_used;
+                p->names_used += (int64_t)len;
+                p->names[p->names_used++] = '\0';
+            }
         } else if (open_record && cur < GKM_MAX_SEQ) {
             size_t take = end - pos;
             if ((size_t)cur + take > GKM_MAX_SEQ) { /* libgkm.c:1294-1299 */
@@ -335,12 +360,38 @@ fail:
     return NULL;
 }
 
+gkm_problem *gkm_problem_read_one(const char *path)
+{
+    gkm_problem *p = (gkm_problem *)calloc(1, sizeof *p);
+    if (!p) return NULL;
+    p->keep_names = 1;
+    if (problem_reserve(p, GKM_MAX_SEQ)) {
+        gkm_problem_free(p);
+        return NULL;
+    }
+    p->off[0] = 0;
+    if (parse_fasta(path, p)) {
+        gkm_problem_free(p);
+        return NULL;
+    }
+    p->n_pos = p->n;
+    return p;
+}
+
 void gkm_problem_free(gkm_problem *p)
 {
     if (!p) return;
     free(p->off);
     free(p->codes);
+    free(p->names);
+    free(p->name_off);
     free(p);
+}
+
+const char *gkm_problem_name(const gkm_problem *p, int i)
+{
+    if (!p->keep_names || i < 0 || i >= p->n) return NULL;
+    return p->names + p->name_off[i];
 }
 
 int gkm_problem_size(const gkm_problem *p) { return p->n; }

@@ -166,15 +166,17 @@ struct GramOut {
     /* if set (packed row slabs, gkm_shard.h): local row r starts at G + row_off[r] instead of G + r * ld.
      * gram_launch() receives the HOST array and replaces it by its device copy. */
     const int64_t *row_off;
+    /* the column that lands at offset 0 of a row: col_begin of a COLS_RANGE launch, 0 for every other mode */
+    int col0;
 };
 
 __device__ __forceinline__ double *gram_cell(const GramOut &out, int64_t r, int j)
 {
-    return out.G + (out.row_off ? out.row_off[r] : r * out.ld) + j;
+    return out.G + (out.row_off ? out.row_off[r] : r * out.ld) + (j - out.col0);
 }
 
 /* which columns a tile of rows visits */
-enum { COLS_TRIANGLE = 0, COLS_FULL = 1, COLS_DIAGONAL = 2 };
+enum { COLS_TRIANGLE = 0, COLS_FULL = 1, COLS_DIAGONAL = 2, COLS_RANGE = 3 /* [col_begin, col_end) of the launch */ };
 
 /* rows r0..r1-1 of a matrix whose rows < r1 hold raw values (gkm_normalize.hip) */
 int normalize_rows(gkmhip_ctx *ctx, double *G, int64_t ld, int r0, int r1, double *sq, int symmetric, hipStream_t stream,

@@ -31,14 +31,16 @@ __global__ void k_normalize(double *__restrict__ G, int64_t ld, int r0, const do
     G[(int64_t)a * ld + j] = v;
 }
 
-/* K(rows[i], j) = G / (sq[rows[i]] * sq[j]) for every column j of a block of full rows */
-__global__ void k_normalize_full(double *__restrict__ G, int64_t ld, const int *__restrict__ rows, int local_rows, int n,
-                                 const double *__restrict__ sq, int rbf, double gamma)
+/* K(rows[i], j) = G / (sq[rows[i]] * sq[j]) for the columns col_begin <= j < col_begin + ncols of a block of rows; column j
+ * of a row sits at offset j - col_begin (full rows: col_begin = 0, ncols = n) */
+__global__ void k_normalize_full(double *__restrict__ G, int64_t ld, const int *__restrict__ rows, int local_rows, int col_begin,
+                                 int ncols, const double *__restrict__ sq, int rbf, double gamma)
 {
     const int a = rows[blockIdx.y];
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    double *cell = G + (int64_t)(local_rows ? (int)blockIdx.y : a) * ld + j;
+    const int jl = blockIdx.x * blockDim.x + threadIdx.x;
+    if (jl >= ncols) return;
+    const int j = col_begin + jl;
+    double *cell = G + (int64_t)(local_rows ? (int)blockIdx.y : a) * ld + jl;
     double v = 1.0;
     if (j != a) {
         v = *cell / (sq[a] * sq[j]);
@@ -47,19 +49,37 @@ __global__ void k_normalize_full(double *__restrict__ G, int64_t ld, const int *
     *cell = v;
 }
 
+static int normalize_block(gkmhip_ctx *ctx, const int *rows, int nrows, int local_rows, int col_begin, int col_end, double *G,
+                           int64_t ld, const double *sqnorm, hipStream_t stream)
+{
+    HIPCHK(hipSetDevice(ctx->device));
+    for (int i = 0; i < nrows; i++)
+        if (rows[i] < 0 || rows[i] >= ctx->n) return set_err_msg("normalize: row index out of range", 2);
+    if (ctx->scratch[ctx->sel].rows.ensure((size_t)nrows)) return 4;
+    HIPCHK(hipMemcpyAsync(ctx->scratch[ctx->sel].rows.p, rows, (size_t)nrows * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream)); /* `rows` is the caller's: see gkmhip_set_sequences */
+    const int ncols = col_end - col_begin;
+    hipLaunchKernelGGL(k_normalize_full, dim3((unsigned)((ncols + 255) / 256), (unsigned)nrows), dim3(256), 0, stream, G, ld,
+                       ctx->scratch[ctx->sel].rows.p, local_rows, col_begin, ncols, sqnorm, ctx->rbf, ctx->gamma);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int gkmhip_normalize_rows_full(gkmhip_ctx *ctx, const int *rows, int nrows, int local_rows, double *G,
                                           int64_t ld, const double *sqnorm, void *stream_)
 {
     if (!ctx || !rows || nrows <= 0 || !G || !sqnorm) return set_err_msg("gkmhip_normalize_rows_full: bad arguments", 2);
-    hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(hipSetDevice(ctx->device));
-    if (ctx->scratch[ctx->sel].rows.ensure((size_t)nrows)) return 4;
-    HIPCHK(hipMemcpyAsync(ctx->scratch[ctx->sel].rows.p, rows, (size_t)nrows * sizeof(int), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipStreamSynchronize(stream)); /* `rows` is the caller's: see gkmhip_set_sequences */
-    hipLaunchKernelGGL(k_normalize_full, dim3((unsigned)((ctx->n + 255) / 256), (unsigned)nrows), dim3(256), 0, stream, G, ld,
-                       ctx->scratch[ctx->sel].rows.p, local_rows, ctx->n, sqnorm, ctx->rbf, ctx->gamma);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return normalize_block(ctx, rows, nrows, local_rows, 0, ctx->n, G, ld, sqnorm, (hipStream_t)stream_);
+}
+
+extern "C" int gkmhip_normalize_block(gkmhip_ctx *ctx, const int *rows, int nrows, int col_begin, int col_end, double *G,
+                                      int64_t ld, const double *sqnorm, void *stream_)
+{
+    if (!ctx || !rows || nrows <= 0 || !G || !sqnorm) return set_err_msg("gkmhip_normalize_block: bad arguments", 2);
+    if (col_begin < 0 || col_end > ctx->n || col_begin >= col_end)
+        return set_err_msg("gkmhip_normalize_block: the column range must satisfy 0 <= col_begin < col_end <= n", 2);
+    if (ld < col_end - col_begin) return set_err_msg("leading dimension too small", 2);
+    return normalize_block(ctx, rows, nrows, 1, col_begin, col_end, G, ld, sqnorm, (hipStream_t)stream_);
 }
 
 /* rows r0..r1-1 of a matrix whose rows < r1 hold raw values: needs sqrt(G(j,j)) for j < r1 only,

@@ -70,6 +70,10 @@ def load():
     L.gkm_position_weights.argtypes = (i32, i32, ctypes.c_uint8, dbl, vp)
     L.gkm_problem_read.restype = vp
     L.gkm_problem_read.argtypes = (ctypes.c_char_p, ctypes.c_char_p)
+    L.gkm_problem_read_one.restype = vp
+    L.gkm_problem_read_one.argtypes = (ctypes.c_char_p,)
+    L.gkm_problem_name.restype = ctypes.c_char_p
+    L.gkm_problem_name.argtypes = (vp, i32)
     L.gkm_problem_free.restype = None
     L.gkm_problem_free.argtypes = (vp,)
     for name in ("gkm_problem_size", "gkm_problem_npos"):
@@ -107,6 +111,10 @@ def load():
         L.gkmhip_allgather_bytes_per_rank.restype = ctypes.c_longlong
     L.gkmhip_gram_rows_full.restype = i32
     L.gkmhip_gram_rows_full.argtypes = (vp, vp, i32, i32, vp, i64, vp)
+    L.gkmhip_gram_block.restype = i32
+    L.gkmhip_gram_block.argtypes = (vp, vp, i32, i32, i32, vp, i64, vp)
+    L.gkmhip_normalize_block.restype = i32
+    L.gkmhip_normalize_block.argtypes = (vp, vp, i32, i32, i32, vp, i64, vp, vp)
     L.gkmhip_self_norms.restype = i32
     L.gkmhip_self_norms.argtypes = (vp, vp, vp)
     L.gkmhip_normalize_rows_full.restype = i32
@@ -239,6 +247,26 @@ def read_problem(posfile, negfile):
         L.gkm_problem_free(h)
 
 
+def read_fasta(path):
+    """One FASTA file -> (FlatSequences of base codes, header names, n_invalid_chars, n_truncated), with the record
+    rules, invalid characters and truncation of `read_problem` (the same C parser), so that a query is encoded exactly
+    as it would have been for training."""
+    L = load()
+    h = L.gkm_problem_read_one(os.fsencode(path))
+    if not h:
+        raise GkmError("cannot read %s" % path)
+    try:
+        n = L.gkm_problem_size(h)
+        off = np.ctypeslib.as_array(L.gkm_problem_offsets(h), shape=(n + 1,)).copy()
+        total = int(off[-1])
+        codes = (np.ctypeslib.as_array(L.gkm_problem_all_codes(h), shape=(total,)).copy() if total
+                 else np.zeros(0, np.uint8))
+        names = [L.gkm_problem_name(h, i).decode("utf-8", "replace") for i in range(n)]
+        return FlatSequences(codes, off), names, L.gkm_problem_invalid_chars(h), L.gkm_problem_truncated(h)
+    finally:
+        L.gkm_problem_free(h)
+
+
 def encode(seq):
     """bytes/str of ACGT (any case; other characters count as A) -> uint8 codes 0..3."""
     if isinstance(seq, str):
@@ -331,6 +359,18 @@ class GramContext:
         rows = np.ascontiguousarray(rows, dtype=np.int32)
         self._chk(self.lib.gkmhip_gram_rows_full(self.handle, rows.ctypes.data, len(rows), int(local_rows), G_ptr, ld,
                                                  stream), "gkmhip_gram_rows_full")
+
+    def gram_block(self, rows, col_begin, col_end, G_ptr, ld, stream=0):
+        """Raw G(rows[i], j) for col_begin <= j < col_end into G_ptr[i*ld + (j - col_begin)] (include/gkm_hip.h)."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        self._chk(self.lib.gkmhip_gram_block(self.handle, rows.ctypes.data, len(rows), int(col_begin), int(col_end), G_ptr,
+                                             ld, stream), "gkmhip_gram_block")
+
+    def normalize_block(self, rows, col_begin, col_end, G_ptr, ld, sq_ptr, stream=0):
+        """Kernel values in place on a block written by gram_block with the same rows and range."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        self._chk(self.lib.gkmhip_normalize_block(self.handle, rows.ctypes.data, len(rows), int(col_begin), int(col_end),
+                                                  G_ptr, ld, sq_ptr, stream), "gkmhip_normalize_block")
 
     def self_norms(self, sq_ptr, stream=0):
         self._chk(self.lib.gkmhip_self_norms(self.handle, sq_ptr, stream), "gkmhip_self_norms")

@@ -1,0 +1,373 @@
+"""Train a gkm-SVM on all sequences, keep it in a model file, and score new sequences with it on the GPU.
+
+The other half of a gkm-SVM next to the cross-validation of `gkmsvm.py` (the counterparts of LS-GKM's `gkmtrain` and
+`gkmpredict`; the model file is this project's own):
+
+  * `train` builds the Gram matrix of pos + neg on the device (device.gram_matrix, the resident path), solves ONE C-SVC on
+    every sample with the GPU solver (svmcv.train_folds; scikit-learn if the solver stops at its iteration cap) and
+    keeps the support vectors in LIBSVM's internal order;
+  * `score` uploads [support vectors; a block of queries] into one cached context, takes the self norms of that set,
+    computes the S x Qb block of kernel values (gkmhip_gram_block: SVs as rows, queries as columns) and its
+    normalisation (gkmhip_normalize_block), and sums the decision values with k_decision (gkmsvm_decision_batch) --
+    scikit-learn's `decision_function` of the trained SVC, bit for bit, for every block size.
+
+    python -m gkmqc_amd.gkmpredict train [-t -L -k -d -M -H -G -C -e -u] pos.fa neg.fa model.txt
+    python -m gkmqc_amd.gkmpredict predict query.fa model.txt out.txt
+"""
+import argparse
+import logging
+import os
+import sys
+import time
+
+import numpy as np
+
+from . import device as dv
+from . import svmcv
+
+FORMAT = "gkmqc-model-1"
+_INT_KEYS = ("kernel_type", "L", "k", "d", "M", "shrinking", "n0", "n_sv")
+_FLOAT_KEYS = ("H", "gamma", "C", "tol", "rho")
+_KEYS = ("format", "kernel_type", "L", "k", "d", "M", "H", "gamma", "C", "tol", "shrinking", "rho", "n0", "n_sv")
+BLOCK_BYTES = 2 << 30     # device memory one block of queries may take: S x Qb kernel values + the kernel's own output
+_ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
+
+
+class ModelError(ValueError):
+    pass
+
+
+def codes_to_text(codes):
+    return _ACGT[np.asarray(codes, dtype=np.uint8)].tobytes().decode()
+
+
+def text_to_codes(text):
+    raw = np.frombuffer(text.encode(), dtype=np.uint8)
+    lut = np.full(256, 255, dtype=np.uint8)
+    lut[_ACGT] = np.arange(4, dtype=np.uint8)
+    codes = lut[raw]
+    if (codes == 255).any():
+        raise ModelError("a stored sequence holds a character other than A, C, G, T")
+    return codes
+
+
+class Model:
+    """A trained gkm-SVM: kernel and SVM parameters, rho, and the support vectors in LIBSVM's internal order (class 0 --
+    the negatives -- first, n0 of them), each with its alpha (> 0), FASTA name and base codes."""
+
+    def __init__(self, kernel_type, L, k, d, M, H, gamma, C, tol, shrinking, rho, n0, alpha, names, seqs):
+        self.kernel_type, self.L, self.k, self.d, self.M = int(kernel_type), int(L), int(k), int(d), int(M)
+        self.H, self.gamma, self.C, self.tol = float(H), float(gamma), float(C), float(tol)
+        self.shrinking = bool(shrinking)
+        self.rho, self.n0 = float(rho), int(n0)
+        self.alpha = np.ascontiguousarray(alpha, dtype=np.float64)
+        self.names = list(names)
+        self.seqs = [np.ascontiguousarray(s, dtype=np.uint8) for s in seqs]
+        _validate(self)
+
+    @property
+    def n_sv(self):
+        return len(self.alpha)
+
+    def kernel_params(self):
+        return (self.kernel_type, self.L, self.k, self.d, self.M, self.H, self.gamma)
+
+    def dual_coef(self):
+        """scikit-learn's `dual_coef_[0]` (labels 0 / 1: class 0 first with a negative sign)."""
+        return np.where(np.arange(self.n_sv) < self.n0, -self.alpha, self.alpha)
+
+    def save(self, path):
+        """Write the model file (format: INTEGRATION.md).  Floats as repr(), which reads back to the same double."""
+        head = [("format", FORMAT), ("kernel_type", self.kernel_type), ("L", self.L), ("k", self.k), ("d", self.d),
+                ("M", self.M), ("H", repr(self.H)), ("gamma", repr(self.gamma)), ("C", repr(self.C)),
+                ("tol", repr(self.tol)), ("shrinking", int(self.shrinking)), ("rho", repr(self.rho)), ("n0", self.n0),
+                ("n_sv", self.n_sv)]
+        tmp = path + ".tmp"
+        with open(tmp, "w") as f:
+            for key, val in head:
+                f.write("%s %s\n" % (key, val))
+            f.write("SV\n")
+            for a, name, s in zip(self.alpha, self.names, self.seqs):
+                f.write("%r\t%s\t%s\n" % (float(a), name, codes_to_text(s)))
+        os.replace(tmp, path)
+
+
+def _validate(m):
+    bad = dv.check_parameters(m.kernel_type, m.L, m.k, m.d)
+    if bad:
+        raise ModelError("kernel parameters rejected: %s" % bad)
+    if not 0 <= m.M <= 255:
+        raise ModelError("M must lie in 0..255")
+    if not (np.isfinite(m.H) and np.isfinite(m.gamma) and np.isfinite(m.rho) and m.C > 0 and m.tol > 0):
+        raise ModelError("H, gamma and rho must be finite, C and tol positive")
+    if not (len(m.alpha) == len(m.names) == len(m.seqs)) or len(m.alpha) == 0:
+        raise ModelError("a model needs at least one support vector, each with alpha, name and sequence")
+    if not 0 <= m.n0 <= len(m.alpha):
+        raise ModelError("n0 must lie in 0..n_sv")
+    if not (np.isfinite(m.alpha).all() and (m.alpha > 0).all()):
+        raise ModelError("every alpha must be positive and finite")
+    if any(len(s) < m.L for s in m.seqs):
+        raise ModelError("a stored sequence is shorter than L")
+    if any("\n" in nm or "\r" in nm for nm in m.names):
+        raise ModelError("a name holds a line break")
+
+
+def load(path):
+    """Read a model file written by Model.save; anything malformed raises ModelError with the reason."""
+    with open(path) as f:
+        lines = f.read().split("\n")
+    if lines and lines[-1] == "":
+        lines.pop()
+    head, i = {}, 0
+    while i < len(lines) and lines[i] != "SV":
+        parts = lines[i].split(" ", 1)
+        if len(parts) != 2 or parts[0] not in _KEYS:
+            raise ModelError("%s:%d: not a `key value` line of the header: %r" % (path, i + 1, lines[i]))
+        if parts[0] in head:
+            raise ModelError("%s:%d: key %s given twice" % (path, i + 1, parts[0]))
+        head[parts[0]] = parts[1]
+        i += 1
+    if i == len(lines):
+        raise ModelError("%s: no SV line" % path)
+    missing = [key for key in _KEYS if key not in head]
+    if missing:
+        raise ModelError("%s: missing key(s): %s" % (path, ", ".join(missing)))
+    if head["format"] != FORMAT:
+        raise ModelError("%s: format %r, expected %r" % (path, head["format"], FORMAT))
+    try:
+        val = {key: int(head[key]) for key in _INT_KEYS}
+        val.update({key: float(head[key]) for key in _FLOAT_KEYS})
+    except ValueError as e:
+        raise ModelError("%s: %s" % (path, e))
+    body = lines[i + 1:]
+    if len(body) != val["n_sv"]:
+        raise ModelError("%s: n_sv is %d but %d support vector lines follow" % (path, val["n_sv"], len(body)))
+    alpha, names, seqs = np.zeros(len(body)), [], []
+    for j, line in enumerate(body):
+        parts = line.split("\t", 1)
+        rest = parts[1].rsplit("\t", 1) if len(parts) == 2 else []
+        if len(rest) != 2:
+            raise ModelError("%s:%d: expected alpha<TAB>name<TAB>sequence" % (path, i + 2 + j))
+        try:
+            alpha[j] = float(parts[0])
+            seqs.append(text_to_codes(rest[1]))
+        except ValueError as e:
+            raise ModelError("%s:%d: %s" % (path, i + 2 + j, e))
+        names.append(rest[0])
+    return Model(val["kernel_type"], val["L"], val["k"], val["d"], val["M"], val["H"], val["gamma"], val["C"], val["tol"],
+                 val["shrinking"], val["rho"], val["n0"], alpha, names, seqs)
+
+
+# ------------------------------------------------------------------ training
+def train(pos_fa, neg_fa, kernel_type=4, L=10, k=6, d=3, M=50, H=50, gamma=1.0, C=1.0, tol=1e-3, shrinking=False,
+          device=0, kernel=dv.KERNEL_AUTO):
+    """One C-SVC on every sequence of pos_fa (label 1) and neg_fa (label 0) -> Model."""
+    import torch
+    bad = dv.check_parameters(kernel_type, L, k, d)
+    if bad:
+        raise ModelError("kernel parameters rejected: %s" % bad)
+    pos, pos_names, _, _ = dv.read_fasta(pos_fa)
+    neg, neg_names, _, _ = dv.read_fasta(neg_fa)
+    if len(pos) == 0 or len(neg) == 0:
+        raise ModelError("training needs at least one positive and one negative sequence")
+    seqs = dv.FlatSequences(np.concatenate((pos.codes, neg.codes)),
+                            np.concatenate((pos.off, pos.off[-1] + neg.off[1:])))
+    names = pos_names + neg_names
+    y = np.concatenate((np.repeat(1, len(pos)), np.repeat(0, len(neg))))
+    res = dv.gram_matrix(seqs, kernel_type, L, k, d, M, H, gamma, device, kernel=kernel, symmetric=True,
+                         keep_context=True)
+    K = res["K"]
+    sol, _ = svmcv.train_folds(K, [np.arange(len(y))], y, C, tol, shrinking)
+    if sol.iters[0] >= 0:
+        a, order = sol.alpha[0], sol.idx[0]
+        sv = np.nonzero(a > 0)[0]
+        idx, alpha, rho = order[sv], a[sv], float(sol.rho[0])
+    else:   # the GPU solver's iteration cap: the reference's solver has none (as svmcv.crossValidate)
+        from sklearn.svm import SVC
+        logging.warning("training re-solved with scikit-learn (iteration cap of the GPU solver)")
+        m = SVC(kernel="precomputed", C=C, tol=tol, shrinking=bool(shrinking)).fit(K.cpu().numpy(), y)
+        # (for two classes scikit-learn negates LIBSVM's coefficients and decision value, so intercept_ is LIBSVM's rho)
+        idx, alpha, rho = m.support_, np.abs(m.dual_coef_[0]), float(m.intercept_[0])
+    del K, res
+    torch.cuda.empty_cache()
+    return Model(kernel_type, L, k, d, M, H, gamma, C, tol, shrinking, rho, int((y[idx] == 0).sum()), alpha,
+                 [names[i] for i in idx], [seqs[i] for i in idx])
+
+
+# ------------------------------------------------------------------ scoring
+def default_block(n_sv, budget=BLOCK_BYTES):
+    """Queries per block: the S x Qb kernel values and the Gram kernel's tile-transposed output (about as big) within
+    `budget` bytes of device memory, whatever the number of queries."""
+    return int(max(1, min(1 << 20, budget // (16 * max(n_sv, 64)))))
+
+
+def _as_queries(fasta_or_sequences):
+    if isinstance(fasta_or_sequences, (str, bytes, os.PathLike)):
+        seqs, names, _, _ = dv.read_fasta(fasta_or_sequences)
+        return seqs, names
+    seqs = fasta_or_sequences
+    if not isinstance(seqs, dv.FlatSequences):
+        seqs = [np.asarray(s, dtype=np.uint8) for s in seqs]
+        lens = np.array([len(s) for s in seqs], dtype=np.int64)
+        off = np.zeros(len(seqs) + 1, dtype=np.int64)
+        np.cumsum(lens, out=off[1:])
+        seqs = dv.FlatSequences(np.concatenate(seqs) if seqs else np.zeros(0, np.uint8), off)
+    return seqs, ["seq%d" % i for i in range(len(seqs))]
+
+
+def check_queries(model, seqs):
+    if len(seqs) == 0:
+        raise ModelError("no query sequences")
+    short = np.nonzero(np.diff(seqs.off) < model.L)[0]
+    if len(short):
+        raise ModelError("query %d is shorter than L = %d" % (int(short[0]), model.L))
+
+
+def score(model, fasta_or_sequences, device=0, block=None, kernel=dv.KERNEL_AUTO, on_block=None):
+    """Decision values of `model` for a FASTA file (or a list / FlatSequences of base codes) -> (names, scores):
+    scikit-learn's `decision_function` sign, positive = like the positive set.  block: queries per device block
+    (default_block).  on_block(dict) (measurements): called after every block with its size and timings."""
+    seqs, names = _as_queries(fasta_or_sequences)
+    check_queries(model, seqs)
+    return names, _score_flat(model, seqs, device, block, kernel, on_block)
+
+
+def _score_flat(model, seqs, device, block, kernel, on_block):
+    import torch
+    lib = svmcv._lib()
+    S, Q = model.n_sv, len(seqs)
+    qb_max = min(Q, int(block) if block else default_block(S))
+    if qb_max < 1:
+        raise ModelError("block must be at least 1")
+    ctx = dv.cached_context(*model.kernel_params(), device=device)
+    ctx.set_kernel(kernel)
+    sv_codes = np.concatenate(model.seqs)
+    sv_off = np.zeros(S + 1, dtype=np.int64)
+    np.cumsum([len(s) for s in model.seqs], out=sv_off[1:])
+    rows = np.arange(S, dtype=np.int32)
+    dev = torch.device("cuda", device)
+    out = np.empty(Q)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        G = torch.empty((S, qb_max), dtype=torch.float64, device=dev)
+        sq = torch.empty(S + qb_max, dtype=torch.float64, device=dev)
+        d_idx = torch.from_numpy(rows).to(dev)
+        d_alpha = torch.from_numpy(model.alpha).to(dev)
+        d_rho = torch.tensor([model.rho], dtype=torch.float64, device=dev)
+        d_test = torch.arange(qb_max, dtype=torch.int32, device=dev)
+        d_dec = torch.empty(qb_max, dtype=torch.float64, device=dev)
+        off_sv = np.array([0, S], dtype=np.int64)
+        n0 = np.array([model.n0], dtype=np.int32)
+        for q0 in range(0, Q, qb_max):
+            q1 = min(Q, q0 + qb_max)
+            qb = q1 - q0
+            t0 = time.perf_counter()
+            qoff = seqs.off[q0:q1 + 1]
+            union = dv.FlatSequences(np.concatenate((sv_codes, seqs.codes[qoff[0]:qoff[-1]])),
+                                     np.concatenate((sv_off, sv_off[-1] + (qoff[1:] - qoff[0]))))
+            ctx.set_sequences(union, stream)     # (complete on return)
+            t1 = time.perf_counter()
+            ctx.self_norms(sq.data_ptr(), stream)
+            ctx.gram_block(rows, S, S + qb, G.data_ptr(), qb_max, stream)
+            if on_block is not None:
+                torch.cuda.current_stream().synchronize()
+            t2 = time.perf_counter()
+            gram_ms = ctx.last_kernel_ms() if on_block is not None else None
+            ctx.normalize_block(rows, S, S + qb, G.data_ptr(), qb_max, sq.data_ptr(), stream)
+            if on_block is not None:
+                torch.cuda.current_stream().synchronize()
+            t3 = time.perf_counter()
+            rc = lib.gkmsvm_decision_batch(device, G.data_ptr(), qb_max, 1, d_idx.data_ptr(), off_sv.ctypes.data,
+                                           n0.ctypes.data, d_alpha.data_ptr(), d_rho.data_ptr(), d_test.data_ptr(),
+                                           np.array([0, qb], dtype=np.int64).ctypes.data, d_dec.data_ptr(), stream)
+            if rc:
+                raise svmcv.SvmError("gkmsvm_decision_batch: %s" % lib.gkmsvm_last_error().decode())
+            # LIBSVM's decision value for labels (0, 1) has the opposite sign of scikit-learn's
+            out[q0:q1] = -d_dec[:qb].cpu().numpy()
+            t4 = time.perf_counter()
+            if on_block is not None:
+                on_block(dict(queries=qb, upload_ms=(t1 - t0) * 1e3, norms_gram_ms=(t2 - t1) * 1e3, gram_kernel_ms=gram_ms,
+                              normalize_ms=(t3 - t2) * 1e3, decision_ms=(t4 - t3) * 1e3, wall_ms=(t4 - t0) * 1e3,
+                              comparisons=ctx.last_comparisons(), kernel=ctx.last_kernel_name()))
+    return out
+
+
+# ------------------------------------------------------------------ command line
+def build_parser():
+    p = argparse.ArgumentParser(prog="python -m gkmqc_amd.gkmpredict",
+                                description="train a gkm-SVM on all sequences / score FASTA sequences with it (MI355X)")
+    sub = p.add_subparsers(dest="cmd", required=True)
+    t = sub.add_parser("train", help="train on pos.fa + neg.fa and write a model file")
+    t.add_argument("-t", "--kernel-type", type=int, default=4, help="kernel type 0..5 (default: 4)")
+    t.add_argument("-L", "--full-word-length", type=int, default=10, help="full word length (default: 10)")
+    t.add_argument("-k", "--non-gap-length", type=int, default=6, help="non-gap positions (default: 6)")
+    t.add_argument("-d", "--max-num-gaps", type=int, default=3, help="max gaps (default: 3)")
+    t.add_argument("-M", "--init-decay", type=int, default=50, help="initial value of the decay, -t 4/5 (default: 50)")
+    t.add_argument("-H", "--half-life-decay", type=float, default=50, help="half life of the decay, -t 4/5 (default: 50)")
+    t.add_argument("-G", "--rbf-gamma", type=float, default=1.0, help="gamma for RBF kernels, -t 3/5 (default: 1.0)")
+    t.add_argument("-C", "--regularization", type=float, default=1.0, help="regularization parameter C (default: 1.0)")
+    t.add_argument("-e", "--precision", type=float, default=0.001, help="precision parameter epsilon (default: 0.001)")
+    t.add_argument("-u", "--shrinking", type=int, choices=(0, 1), default=0, help="shrinking heuristics (default: 0)")
+    t.add_argument("--device", type=int, default=0, help="GPU (default: 0)")
+    t.add_argument("pos_fa")
+    t.add_argument("neg_fa")
+    t.add_argument("model")
+    q = sub.add_parser("predict", help="score the sequences of query.fa: name<TAB>score per line, in file order")
+    q.add_argument("--device", type=int, default=0, help="GPU (default: 0)")
+    q.add_argument("--block", type=int, default=None, help="queries per device block (default: from device memory)")
+    q.add_argument("query_fa")
+    q.add_argument("model")
+    q.add_argument("output")
+    return p
+
+
+def check_train_args(a):
+    """The argument checks `train` makes before it reads anything; an error message or None."""
+    bad = dv.check_parameters(a.kernel_type, a.full_word_length, a.non_gap_length, a.max_num_gaps)
+    if bad:
+        return bad
+    if not 0 <= a.init_decay <= 255:
+        return "-M must lie in 0..255"
+    if not (a.regularization > 0 and a.precision > 0):
+        return "-C and -e must be positive"
+    return None
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    try:
+        if a.cmd == "train":
+            bad = check_train_args(a)
+            if bad:
+                raise ModelError(bad)
+            for path in (a.pos_fa, a.neg_fa):
+                if not os.path.isfile(path):
+                    raise ModelError("cannot read %s" % path)
+            m = train(a.pos_fa, a.neg_fa, a.kernel_type, a.full_word_length, a.non_gap_length, a.max_num_gaps,
+                      a.init_decay, a.half_life_decay, a.rbf_gamma, a.regularization, a.precision, bool(a.shrinking),
+                      a.device)
+            m.save(a.model)
+            print("%d support vectors (%d negative, %d positive), rho %r -> %s"
+                  % (m.n_sv, m.n0, m.n_sv - m.n0, m.rho, a.model), file=sys.stderr)
+        else:
+            if a.block is not None and a.block < 1:
+                raise ModelError("--block must be at least 1")
+            if not os.path.isfile(a.query_fa):
+                raise ModelError("cannot read %s" % a.query_fa)
+            m = load(a.model)
+            seqs, names = _as_queries(a.query_fa)
+            check_queries(m, seqs)
+            scores = _score_flat(m, seqs, a.device, a.block, dv.KERNEL_AUTO, None)
+            tmp = a.output + ".tmp"
+            with open(tmp, "w") as f:
+                for name, s in zip(names, scores):
+                    f.write("%s\t%r\n" % (name, float(s)))
+            os.replace(tmp, a.output)
+    except (ModelError, dv.GkmError, svmcv.SvmError, OSError) as e:
+        print("gkmpredict: error: %s" % e, file=sys.stderr)
+        return 1
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

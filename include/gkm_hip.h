@@ -97,6 +97,13 @@ int gkmhip_gram_rows_packed(gkmhip_ctx *ctx, const int *rows, int nrows, double 
 int gkmhip_gram_rows_full(gkmhip_ctx *ctx, const int *rows, int nrows, int local_rows, double *G, int64_t ld,
                           void *stream);
 
+/* A block of columns (scoring: the support vectors as rows, a block of queries as the columns): raw G(rows[i], j) for
+ * col_begin <= j < col_end, stored at G[i*ld + (j - col_begin)]; every (row, column) pair of the range, no triangle; the
+ * rows (host array, strictly ascending) may lie inside or outside the range.  ld >= col_end - col_begin.  G is a DEVICE
+ * pointer; the work is enqueued on `stream`.  Served by the same kernels as gkmhip_gram_rows. */
+int gkmhip_gram_block(gkmhip_ctx *ctx, const int *rows, int nrows, int col_begin, int col_end, double *G, int64_t ld,
+                      void *stream);
+
 /* sqnorm[i] = sqrt(G(i,i)) for all uploaded sequences (device array of n doubles), computed
  * from the diagonal band only (~1 % of the work of the whole matrix).  Replaces
  * gkmkernel_kernelfunc_sqnorm_single, src/libgkm.c:723-759. */
@@ -106,6 +113,11 @@ int gkmhip_self_norms(gkmhip_ctx *ctx, double *sqnorm, void *stream);
  * gkmhip_gram_rows_full with the same rows / local_rows. */
 int gkmhip_normalize_rows_full(gkmhip_ctx *ctx, const int *rows, int nrows, int local_rows, double *G, int64_t ld,
                                const double *sqnorm, void *stream);
+
+/* K = G / (sqnorm[rows[i]] * sqnorm[j]) (+ RBF) in place on a block written by gkmhip_gram_block with the same rows and
+ * range; 1.0 where j == rows[i].  The same kernel and operation order as gkmhip_normalize_rows_full. */
+int gkmhip_normalize_block(gkmhip_ctx *ctx, const int *rows, int nrows, int col_begin, int col_end, double *G, int64_t ld,
+                           const double *sqnorm, void *stream);
 
 /* In place on a device matrix holding raw values for ALL n rows (lower triangle +
  * diagonal): K(a,j) = G(a,j) / (sqrt(G(a,a)) sqrt(G(j,j))), optional RBF, K(a,a)=1.

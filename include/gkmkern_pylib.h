@@ -105,6 +105,11 @@ const int64_t *gkm_problem_offsets(const gkm_problem *p);      /* [n+1] offsets 
 const uint8_t *gkm_problem_all_codes(const gkm_problem *p);    /* all sequences back to back (gkmhip_set_sequences) */
 long gkm_problem_invalid_chars(const gkm_problem *p);          /* mapped to 'A' */
 long gkm_problem_truncated(const gkm_problem *p);              /* cut at 2047 nt */
+/* ONE FASTA file with the same record rules, invalid characters and truncation (scoring queries), keeping every record's
+ * header: gkm_problem_name(p, i) is the text after '>' up to the end of its line (NUL-terminated, owned by p).  npos = n.
+ * gkm_problem_name returns NULL for a problem read by gkm_problem_read, which drops the headers. */
+gkm_problem *gkm_problem_read_one(const char *path);
+const char *gkm_problem_name(const gkm_problem *p, int i);
 
 #ifdef __cplusplus
 }
