@@ -101,3 +101,61 @@ def batch_rows_expected():
                               M=int(M), H=float(H), gamma=float(g), K=z["%s_p%d_K" % (name, i)]))
             i += 1
     return cases
+
+
+# every (L, d) the bit-sliced Gram kernel is instantiated for (the instantiation table of gkmqc_amd/csrc/gkm_gram_bitslice.hip)
+ALL_LD = [(L, d) for L in range(5, 13) for d in range(0, 5)] + [(11, 5), (12, 5), (12, 6)]
+
+
+def raw_from_profiles(P, c):
+    """Raw G(a, j) = sum_m c_m P_m(a, j), ascending m from 0.0 -- the Gram kernels' accumulation order."""
+    G = np.zeros(P.shape[:2])
+    for m in range(P.shape[2]):
+        G = G + c[m] * P[:, :, m].astype(np.float64)
+    return G
+
+
+def oracle_raw(O, t, L, k, d, pf, nf):
+    """Raw G(a, j) for every pair of the problem in pf + nf through the CPU oracle."""
+    r = O.gram(O.make_opt(t, L, k, d, posfile=pf, negfile=nf, nthreads=8), want_profiles=True)
+    P = r["P"]
+    i, j = np.triu_indices(r["n"], 1)
+    P[i, j] = P[j, i]
+    return raw_from_profiles(P, O.mismatch_weights(t, L, k)[: d + 1])
+
+
+def oracle_problem(seqs, params):
+    """The CPU oracle on a list of base-code arrays (at least two), params = (t, L, k, d, M, H, gamma)
+    -> dict(P [n, n, d + 1], G raw, K), all symmetric."""
+    import tempfile
+    from oracle import oracle as O
+    t, L, k, d, M, H, gamma = params
+    letters = np.frombuffer(b"ACGT", dtype=np.uint8)
+    with tempfile.TemporaryDirectory() as tmp:
+        pf, nf = os.path.join(tmp, "p.fa"), os.path.join(tmp, "n.fa")
+        half = max(1, len(seqs) // 2)          # (the oracle's reader wants both files non-empty)
+        for path, part in ((pf, seqs[:half]), (nf, seqs[half:])):
+            with open(path, "wb") as f:
+                for i, s in enumerate(part):
+                    f.write(b">s%d\n" % i + letters[np.asarray(s)].tobytes() + b"\n")
+        r = O.gram(O.make_opt(t, L, k, d, M, H, gamma, pf, nf), want_profiles=True, nthreads=8)
+    n = r["n"]
+    assert n == len(seqs)
+    P, K = r["P"], r["K"]
+    i, j = np.triu_indices(n, 1)
+    P[i, j] = P[j, i]
+    K[i, j] = K[j, i]
+    return dict(P=P, G=raw_from_profiles(P, O.mismatch_weights(t, L, k)[: d + 1]), K=K)
+
+
+def oracle_cells(seqs, rows, cols, params):
+    """Oracle raw G and K at [rows][:, cols] of the problem `seqs`, from the oracle run on only the sequences these
+    cells name (a cell depends on its two sequences alone: tests/test_oracle_golden.py pins that)."""
+    rows, cols = np.asarray(rows), np.asarray(cols)
+    sub = np.unique(np.concatenate((rows, cols)))
+    pick = list(sub) if len(sub) > 1 else [sub[0], sub[0]]
+    r = oracle_problem([seqs[int(s)] for s in pick], params)
+    at = {int(s): i for i, s in enumerate(sub)}
+    ri = np.array([at[int(a)] for a in rows])
+    ci = np.array([at[int(j)] for j in cols])
+    return r["G"][np.ix_(ri, ci)], r["K"][np.ix_(ri, ci)]

@@ -32,3 +32,18 @@ def test_random_svm_problems(built, monkeypatch, capsys):
     monkeypatch.setattr(sys, "argv", ["fuzz_svm.py", "--seconds", "15", "--seed", "21"])
     mod.main()
     assert "svm fuzz ok" in capsys.readouterr().out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", [13, 14])
+def test_random_block_sweep(built, seed, monkeypatch, capsys):
+    """tools/fuzz_block.py: the column-range launch of the scoring path (random rows, ranges, leading dimensions,
+    kernels, GKM_FORCE_PACKED / GKM_COL_CHUNK) -- raw values bit for bit, kernel values and untouched sentinels."""
+    spec = importlib.util.spec_from_file_location("fuzz_block", os.path.join(ROOT, "tools", "fuzz_block.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    monkeypatch.delenv("GKM_FORCE_PACKED", raising=False)
+    monkeypatch.delenv("GKM_COL_CHUNK", raising=False)
+    monkeypatch.setattr(sys, "argv", ["fuzz_block.py", "--seconds", "12", "--seed", str(seed)])
+    mod.main()
+    assert "block fuzz ok" in capsys.readouterr().out

@@ -303,7 +303,7 @@ def test_int32_wraparound_matches_wrapping_arithmetic(dev):
         assert (res["P"].cpu().numpy()[il] == want[il]).all()
 
 
-ALL_LD = [(L, d) for L in range(5, 13) for d in range(0, 5)] + [(11, 5), (12, 5), (12, 6)]
+ALL_LD = helpers.ALL_LD
 
 
 @pytest.mark.parametrize("L,d", ALL_LD)

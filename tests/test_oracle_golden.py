@@ -132,3 +132,33 @@ def test_batch_rows_fixture_is_the_symmetric_completion(O, tmp_path):
             off = np.arange(n) != a
             assert helpers.max_rel_err(c["K"][i][off], K[a][off]) < 1e-12, (c["name"], a)
             assert abs(c["K"][i][a] - 1.0) < 1e-12      # G / sqnorm^2, not forced to 1.0 by this entry
+
+
+def test_a_cell_depends_on_its_two_sequences_only(O):
+    """The GPU block tests take oracle values for a few cells of a large block from the oracle run on just the sequences
+    those cells name (helpers.oracle_cells).  That is right only if a raw cell G(a, j) depends on sequences a and j
+    alone -- the wgkm position weights are per sequence, not per problem.  A ragged problem of 60 sequences (40-900 bp,
+    a duplicate, a poly-A sequence and a reverse complement) against a random subset of 15 of them: the same integer
+    profiles, raw values and kernel values, bit for bit, for every kernel type."""
+    rng = np.random.default_rng(5)
+    seqs = [rng.integers(0, 4, int(n)).astype(np.uint8) for n in rng.integers(40, 901, 60)]
+    seqs[9] = seqs[4].copy()                                  # duplicate
+    seqs[13] = np.zeros(len(seqs[13]), dtype=np.uint8)        # poly-A
+    seqs[21] = (3 - seqs[30][::-1]).astype(np.uint8)          # reverse complement
+    sub = np.sort(np.concatenate(([4, 9, 13, 21, 30], rng.choice(np.setdiff1d(np.arange(60), [4, 9, 13, 21, 30]), 10,
+                                                                 replace=False))))
+    assert len(sub) == 15
+    for params in ((0, 10, 6, 3, 50, 50.0, 1.0), (1, 10, 6, 3, 50, 50.0, 1.0), (2, 10, 6, 3, 50, 50.0, 1.0),
+                   (3, 10, 6, 3, 50, 50.0, 2.0), (4, 10, 6, 3, 37, 23.0, 1.0), (5, 10, 6, 3, 200, 120.0, 0.5)):
+        full = helpers.oracle_problem(seqs, params)
+        part = helpers.oracle_problem([seqs[i] for i in sub], params)
+        ix = np.ix_(sub, sub)
+        assert np.array_equal(part["P"], full["P"][ix]), params
+        assert part["G"].tobytes() == full["G"][ix].tobytes(), params
+        assert part["K"].tobytes() == full["K"][ix].tobytes(), params
+        # and the cell helper on a rectangle of rows and columns (with a row that is also a column)
+        rows, cols = np.array([2, 9, 30, 41]), np.array([0, 9, 13, 21, 59])
+        G, K = helpers.oracle_cells(seqs, rows, cols, params)
+        assert G.tobytes() == full["G"][np.ix_(rows, cols)].tobytes(), params
+        assert K.tobytes() == full["K"][np.ix_(rows, cols)].tobytes(), params
+        assert K[1, 1] == 1.0

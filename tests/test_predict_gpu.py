@@ -69,19 +69,6 @@ def test_block_matches_the_reference_batch_output(dv, kernel):
             assert np.array_equal(got, want), (c["name"], helpers.max_rel_err(got, want))
 
 
-def _oracle_raw(O, t, L, k, d, pf, nf):
-    """Raw G(a, j) = sum_m c_m P_m(a, j), ascending m from 0.0, for every pair of the problem (CPU oracle)."""
-    r = O.gram(O.make_opt(t, L, k, d, posfile=pf, negfile=nf, nthreads=8), want_profiles=True)
-    P = r["P"]
-    i, j = np.triu_indices(r["n"], 1)
-    P[i, j] = P[j, i]
-    c = O.mismatch_weights(t, L, k)[: d + 1]
-    G = np.zeros(P.shape[:2])
-    for m in range(d + 1):
-        G = G + c[m] * P[:, :, m].astype(np.float64)
-    return G
-
-
 @pytest.mark.parametrize("kernel", KERNELS)
 def test_range_away_from_zero_with_rows_inside_and_outside(dv, kernel, tmp_path):
     """Raw values of a column range in the middle of a ragged set, rows before, inside and after it, against the oracle;
@@ -92,7 +79,7 @@ def test_range_away_from_zero_with_rows_inside_and_outside(dv, kernel, tmp_path)
     synth.write_problem(pf, nf, 40, 37, 300, (40, 500))
     seqs, _, _, _ = dv.read_problem(pf, nf)
     t, L, k, d = 4, 10, 6, 3
-    G_ref = _oracle_raw(O, t, L, k, d, pf, nf)
+    G_ref = helpers.oracle_raw(O, t, L, k, d, pf, nf)
     rows = np.array([0, 3, 17, 30, 31, 44, 50, 76])
     c0, c1, ld, sentinel = 30, 51, 27, -7.25
     got, _ = _block(dv, seqs, (t, L, k, d, 50, 50.0, 1.0), rows, c0, c1, _kern(dv, kernel), normalize=False, ld=ld,
@@ -232,3 +219,244 @@ def test_save_load_and_cli(dv, files, tmp_path):
     assert K_train.shape[0] == len(y)
     _, want = _sklearn_scores(K_train, y, K_query, 0.5, 1e-3, False)
     assert np.array_equal(scores, want)
+
+
+# ------------------------------------------------------------------ the column-range launch, kernel by kernel
+def _raw_and_norm(dv, seqs, params, rows, c0, c1, kernel, ld=None, extra_rows=0, sentinel=-5.5):
+    """gram_block, then self_norms + normalize_block, on one fresh context -> (raw, normalised, kernel name); both
+    [len(rows) + extra_rows, ld] host arrays of a buffer prefilled with `sentinel`."""
+    import torch
+    ctx = dv.GramContext(*params)
+    try:
+        ctx.set_kernel(kernel)
+        stream = torch.cuda.current_stream().cuda_stream
+        ctx.set_sequences(seqs, stream)
+        ld = ld or (c1 - c0)
+        G = torch.full((len(rows) + extra_rows, ld), sentinel, dtype=torch.float64, device="cuda")
+        rows = np.asarray(rows, dtype=np.int32)
+        ctx.gram_block(rows, c0, c1, G.data_ptr(), ld, stream)
+        torch.cuda.synchronize()
+        raw = G.cpu().numpy()
+        sq = torch.zeros(len(seqs), dtype=torch.float64, device="cuda")
+        ctx.self_norms(sq.data_ptr(), stream)
+        ctx.normalize_block(rows, c0, c1, G.data_ptr(), ld, sq.data_ptr(), stream)
+        torch.cuda.synchronize()
+        return raw, G.cpu().numpy(), ctx.last_kernel_name()
+    finally:
+        ctx.close()
+
+
+def _same(a, b):
+    return a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+@pytest.mark.parametrize("L,d", helpers.ALL_LD)
+def test_every_bitslice_instantiation_in_a_range(dv, L, d):
+    """Every (L, d) the bit-sliced kernel is instantiated for, in the column-range launch: mixed-length input, a row set
+    with jumps, a range that starts off an 8-column boundary and holds some of the rows.  Bit for bit the general
+    kernel's block, raw and normalised, and on 14 sampled sequences the oracle's raw values."""
+    rng = np.random.default_rng(100 * L + d + 7)
+    seqs = [rng.integers(0, 4, int(n)).astype(np.uint8) for n in rng.integers(L, 900, 70)]
+    seqs[3] = seqs[7].copy()
+    seqs[11] = (3 - seqs[20][::-1]).astype(np.uint8)      # reverse complement of another sequence
+    rows = np.r_[0:9, 30:41, 60:64]
+    c0, c1 = 13, 59
+    for t in (2, 4):
+        params = (t, L, L - d, d, 50, 50.0, 1.0)
+        a_raw, a_k, a_name = _raw_and_norm(dv, seqs, params, rows, c0, c1, dv.KERNEL_BITSLICE)
+        b_raw, b_k, b_name = _raw_and_norm(dv, seqs, params, rows, c0, c1, dv.KERNEL_DIRECT)
+        assert a_name.startswith("k_gram_bitslice") and b_name == "k_gram_direct"
+        assert _same(a_raw, b_raw), (t, helpers.max_rel_err(a_raw, b_raw))
+        assert _same(a_k, b_k), t
+        ri = np.array([0, 4, 8, 9, 12, 19, 22])              # (positions in `rows`: rows 30, 33 and 40 lie in the range)
+        cj = np.array([13, 14, 20, 30, 33, 45, 50, 57, 58])
+        G, _ = helpers.oracle_cells(seqs, rows[ri], cj, params)
+        assert len(np.unique(np.concatenate((rows[ri], cj)))) == 14
+        assert _same(a_raw[np.ix_(ri, cj - c0)], G), t
+
+
+def _sampled_oracle_check(seqs, params, raw, rows, c0, ri, cj):
+    """raw[ri, cj - c0] (row positions ri, sequence columns cj) against the oracle on just those sequences"""
+    G, _ = helpers.oracle_cells(seqs, rows[ri], cj, params)
+    got = raw[np.ix_(ri, cj - c0)]
+    assert _same(got, G), helpers.max_rel_err(got, G)
+
+
+@pytest.mark.parametrize("shape,want", [("same", "k_gram_bitslice<same length>"), ("ragged", "k_gram_bitslice<packed>"),
+                                        ("short", "k_gram_bitslice<packed,128>")])
+def test_each_bitslice_variant_in_a_range(dv, shape, want):
+    """Same-length 300-bp rows take `<same length>`, ragged 150-600 bp rows `<packed>`, many 60-110 bp rows
+    `<packed,128>` (test_gpu_parity.py has the same rule for the triangle).  In a range off an 8-column boundary: the
+    general kernel's block bit for bit and the oracle's raw values on a sampled sub-problem."""
+    seqs = {"same": lambda: helpers.synth_codes(100, 100, 300),
+            "ragged": lambda: helpers.synth_codes(100, 100, 300, (150, 600)),
+            "short": lambda: helpers.synth_codes(150, 150, 300, (60, 110))}[shape]()
+    n = len(seqs)
+    params = (4, 12, 8, 4, 50, 50.0, 1.0) if shape == "ragged" else (4, 10, 6, 3, 50, 50.0, 1.0)
+    rows = np.arange(n, dtype=np.int32)
+    c0, c1 = 45, n - 3
+    raw, K, name = _raw_and_norm(dv, seqs, params, rows, c0, c1, dv.KERNEL_BITSLICE)
+    assert name == want
+    d_raw, d_K, _ = _raw_and_norm(dv, seqs, params, rows, c0, c1, dv.KERNEL_DIRECT)
+    assert _same(raw, d_raw) and _same(K, d_K)
+    rng = np.random.default_rng(3)
+    ri = np.sort(rng.choice(n, 10, replace=False))
+    cj = np.sort(np.concatenate(([c0, c1 - 1], rng.choice(np.arange(c0 + 1, c1 - 1), 10, replace=False))))
+    _sampled_oracle_check(seqs, params, raw, rows, c0, ri, cj)
+
+
+@pytest.mark.parametrize("chunk", ["8", "40", "64"])
+def test_column_chunked_order_in_a_range(dv, monkeypatch, chunk):
+    """The (column chunk, tile) work order in a column-range launch: chunks of 8, 40 and 64 columns against the plain
+    order on ragged data, a range that starts off an 8-column boundary and whose width is no multiple of the chunk (so
+    the entries start at col_begin, not at a multiple of 8, and carry padding items).  Raw and normalised blocks bit
+    for bit."""
+    ragged = helpers.synth_codes(150, 150, 300, (150, 700))
+    rows = np.r_[0:300:3, 101:104]
+    rows = np.unique(rows).astype(np.int32)
+    c0, c1 = 37, 240
+    assert c0 % 8 and (c1 - c0) % int(chunk)
+    for params in ((4, 12, 8, 4, 50, 50.0, 1.0), (2, 11, 7, 3, 50, 50.0, 1.0)):
+        monkeypatch.setenv("GKM_COL_CHUNK", "0")
+        want_raw, want_K, name = _raw_and_norm(dv, ragged, params, rows, c0, c1, dv.KERNEL_BITSLICE, ld=211, extra_rows=1)
+        assert name.startswith("k_gram_bitslice")
+        monkeypatch.setenv("GKM_COL_CHUNK", chunk)
+        raw, K, _ = _raw_and_norm(dv, ragged, params, rows, c0, c1, dv.KERNEL_BITSLICE, ld=211, extra_rows=1)
+        assert _same(raw, want_raw) and _same(K, want_K), params
+        assert (raw[len(rows):] == -5.5).all() and (raw[:, c1 - c0:] == -5.5).all()
+
+
+def _default_chunk(lens, L, W=10):
+    """Restates plan_bitslice's default column chunk (gkmqc_amd/csrc/gkm_gram.hip, "work-item order"): chunks of 4 096
+    columns where a chunk's column tables fit 3 MiB per XCD, over the mean length of ALL uploaded sequences."""
+    mean_len = float(np.sum(np.asarray(lens) - L + 1)) / len(lens) + (L - 1)
+    col_bytes = (4.0 * (mean_len + W) + 2.0 * (mean_len / 16.0 + 1.0)) * 4
+    return 4096 if col_bytes * 4096.0 / 8.0 <= 3.0 * 1048576.0 else 0
+
+
+def test_default_column_chunks_in_a_range(dv, monkeypatch):
+    """The work order scoring takes at default settings: ~100 support-vector-like rows and a range of 4 600 ~300-bp
+    columns, so plan_bitslice cuts the range into chunks of 4 096 columns by its own rule.  The block equals the plain
+    order's and the general kernel's bit for bit, and 40 sampled columns on both sides of the chunk boundary (the last
+    column among them) equal the oracle's raw values."""
+    monkeypatch.delenv("GKM_COL_CHUNK", raising=False)
+    monkeypatch.delenv("GKM_FORCE_PACKED", raising=False)
+    seqs = helpers.synth_codes(103, 4600, 300, (240, 360))
+    S, n = 103, len(seqs)
+    c0, c1 = S, n
+    params = (4, 10, 6, 3, 50, 50.0, 1.0)
+    # the shape must keep meeting the rule, or this test would quietly stop covering the chunked order
+    assert _default_chunk([len(s) for s in seqs], 10) == 4096 and c1 - c0 > 4096 and c0 % 8
+    rows = np.arange(S, dtype=np.int32)
+    raw, K, name = _raw_and_norm(dv, seqs, params, rows, c0, c1, dv.KERNEL_BITSLICE)
+    assert name.startswith("k_gram_bitslice")
+    monkeypatch.setenv("GKM_COL_CHUNK", "0")
+    p_raw, p_K, _ = _raw_and_norm(dv, seqs, params, rows, c0, c1, dv.KERNEL_BITSLICE)
+    monkeypatch.delenv("GKM_COL_CHUNK")
+    d_raw, d_K, d_name = _raw_and_norm(dv, seqs, params, rows, c0, c1, dv.KERNEL_DIRECT)
+    assert d_name == "k_gram_direct"
+    assert _same(raw, p_raw) and _same(K, p_K)
+    assert _same(raw, d_raw) and _same(K, d_K)
+    rng = np.random.default_rng(8)
+    edge = c0 + 4096
+    cj = np.unique(np.concatenate((np.arange(edge - 6, edge + 6), [c0, c1 - 1], rng.choice(np.arange(c0, c1), 26, replace=False))))
+    ri = np.array([0, 1, 50, 101, 102])
+    assert len(cj) >= 40 and (cj < edge).any() and (cj >= edge).any()
+    _sampled_oracle_check(seqs, params, raw, rows, c0, ri, cj)
+
+
+def test_scores_at_a_production_sized_block(dv, files):
+    """Training on the motif sets (type 4) and scoring 4 500 synthetic 300-bp queries: the default block takes them in
+    one launch, in the chunked work order; block=1000 and either kernel give the same scores bit for bit.  60 sampled
+    queries score as scikit-learn's decision_function does on the oracle's kernel values."""
+    from gkmqc_amd import gkmpredict as gp
+    from gkmqc_amd import synth
+    from oracle import oracle as O
+    model = gp.train(POS, NEG, kernel_type=4)
+    qs = [dv.encode(s) for s in synth.make_sequences(41, 4500, 300, (270, 330))]
+    S = model.n_sv
+    assert gp.default_block(S) >= len(qs)
+    lens = [len(s) for s in model.seqs] + [len(q) for q in qs]
+    assert _default_chunk(lens, 10) == 4096 and len(qs) > 4096
+    ref = None
+    for kern in ("bitslice", "direct"):
+        for block in (None, 1000):
+            _, scores = gp.score(model, qs, block=block, kernel=_kern(dv, kern))
+            if ref is None:
+                ref = scores
+            assert _same(scores, ref), (kern, block)
+    # scikit-learn on the oracle's training matrix, its decision values from the oracle's query x support-vector cells
+    # (a two-class LIBSVM model reads only its support vectors' columns)
+    pos, pnames, _, _ = dv.read_fasta(POS)
+    neg, nnames, _, _ = dv.read_fasta(NEG)
+    train = list(pos) + list(neg)
+    y = np.concatenate((np.repeat(1, len(pos)), np.repeat(0, len(neg))))
+    K_train, _ = _oracle_cached(O, files, 4, files["query"])
+    m, _ = _sklearn_scores(K_train, y, K_train[:1], 1.0, 1e-3, False)
+    _check_model_against(model, m, pnames + nnames)
+    sv = np.asarray(m.support_)
+    pick = np.sort(np.random.default_rng(4).choice(len(qs), 60, replace=False))
+    K_query = np.zeros((len(pick), len(train)))
+    step = 200 - len(sv) if len(sv) < 170 else 30
+    for g in range(0, len(pick), step):
+        part = pick[g:g + step]
+        both = [train[i] for i in sv] + [qs[i] for i in part]
+        _, Kc = helpers.oracle_cells(both, np.arange(len(sv), len(both)), np.arange(len(sv)), (4, 10, 6, 3, 50, 50.0, 1.0))
+        K_query[g:g + len(part)][:, sv] = Kc
+    want = m.decision_function(K_query)
+    assert _same(ref[pick], want), helpers.max_rel_err(ref[pick], want)
+
+
+@pytest.mark.parametrize("t", [0, 2, 4, 3, 5])
+def test_normalize_block_on_given_raw_values(dv, t):
+    """gkmhip_normalize_block alone, on raw values and norms the test chooses: G / (sq[a] * sq[j]) -- the product
+    first, one division -- bit for bit, RBF types exp(gamma (v - 1)) within 2 ulp of numpy, exactly 1.0 where the
+    column is the row's own sequence (whatever the raw value there), NaN where the raw value is NaN, and every cell
+    past the range's width or past the last row left alone."""
+    import torch
+    rng = np.random.default_rng(40 + t)
+    n = 40
+    seqs = [rng.integers(0, 4, 50).astype(np.uint8) for _ in range(n)]
+    rows = np.array([1, 5, 12, 13, 20, 28, 31, 39], dtype=np.int32)
+    c0, c1, ld, sentinel = 11, 29, 23, -7.25
+    w = c1 - c0
+    gamma = 0.7
+    sq = rng.uniform(0.5, 3.0, n) * 10.0 ** rng.integers(-3, 4, n)
+    raw = rng.uniform(-1.0, 1.0, (len(rows), w)) * np.outer(sq[rows], sq[c0:c1]) * rng.uniform(0.2, 1.5, (len(rows), w))
+    raw[0, 3] = np.nan
+    raw[2, 5] = -abs(raw[2, 5]) - 1e9                      # a wrapped (negative) profile
+    raw[3, 1] = 1e-300                                      # a subnormal quotient
+    own = [(i, a - c0) for i, a in enumerate(rows) if c0 <= a < c1]
+    assert len(own) == 4                                    # rows 12, 13, 20, 28 meet their own column
+    for i, jl in own:
+        raw[i, jl] = 0.5 * sq[rows[i]] ** 2                 # not 1.0 if divided
+    want = raw / (sq[rows][:, None] * sq[c0:c1][None, :])
+    # (the test has teeth: dividing by one norm at a time rounds some cells differently)
+    assert (want != raw / sq[rows][:, None] / sq[c0:c1][None, :]).sum() > 5
+    if t in (3, 5):
+        want = np.exp(gamma * (want - 1))
+    for i, jl in own:
+        want[i, jl] = 1.0
+    ctx = dv.GramContext(t, 10, 6, 3, 50, 50.0, gamma)
+    try:
+        stream = torch.cuda.current_stream().cuda_stream
+        ctx.set_sequences(seqs, stream)
+        G = torch.full((len(rows) + 2, ld), sentinel, dtype=torch.float64, device="cuda")
+        G[:len(rows), :w] = torch.from_numpy(raw)
+        d_sq = torch.from_numpy(sq).cuda()
+        ctx.normalize_block(rows, c0, c1, G.data_ptr(), ld, d_sq.data_ptr(), stream)
+        torch.cuda.synchronize()
+        got = G.cpu().numpy()
+    finally:
+        ctx.close()
+    assert (got[:len(rows), w:] == sentinel).all() and (got[len(rows):] == sentinel).all()
+    blk = got[:len(rows), :w]
+    assert np.array_equal(np.isnan(blk), np.isnan(want)) and np.isnan(blk).sum() == 1
+    for i, jl in own:
+        assert blk[i, jl] == 1.0
+    fin = ~np.isnan(want)
+    if t in (3, 5):
+        ulp = np.abs(blk[fin] - want[fin]) / np.spacing(np.abs(want[fin]))
+        assert ulp.max() <= 2, ulp.max()
+    else:
+        assert blk[fin].tobytes() == want[fin].tobytes()

@@ -286,3 +286,82 @@ def test_refused_launch_shape_falls_back_to_the_general_solver(built, monkeypatc
     with pytest.raises(svmcv.SvmError) as e:                 # a fold without samples: an argument error, no retry
         svmcv.train_folds(torch.from_numpy(K).cuda(), [trains[0], np.zeros(0, dtype=np.int64)], y, 1.0, 1e-3)
     assert "general" not in str(e.value)
+
+
+def _decision_reference(K, idx, n0, alpha, rho, test):
+    """LIBSVM's order: from 0.0, add (+a if k < n0 else -a) * K[idx[k], test] for a > 0 only, then subtract rho
+    (element-wise over the test samples, so each one is its own sequential sum)"""
+    s = np.zeros(len(test))
+    for k in range(len(idx)):
+        a = alpha[k]
+        if a > 0:
+            s = s + (a if k < n0 else -a) * K[idx[k], test]
+    return s - rho
+
+
+@pytest.mark.parametrize("l", [1, 15, 16, 17, 33, 2049])
+def test_decision_batch_edges(built, l):
+    """gkmsvm_decision_batch (k_decision) called directly, three problems per call: training sets of l samples (around
+    the 16 loads the kernel keeps in flight, and far beyond), 0-3 000 test samples (around the 128-thread workgroup,
+    none at all beside problems that have some), the class boundary n0 at 0, at l and at an odd split, scattered train
+    and test indices into a bit-symmetric matrix with a padded row, alphas of mixed magnitude with exact zeros and
+    kernel values of both signs and mixed magnitude, some near the bottom of the double range, and a problem without a
+    single positive alpha -- so a reordered or blocked sum, a sign boundary off by one, or a sum that does not start
+    from +0.0 changes bits.  Equal bit for bit to
+    LIBSVM's loop, which is itself within l eps sum|a K| of the exact sum."""
+    import math
+    import torch
+    from gkmqc_amd import svmcv
+    lib = svmcv._lib()
+    rng = np.random.default_rng(l)
+    n, ld = 3200, 3211
+    X = rng.uniform(-1, 1, (n, n)) * 10.0 ** rng.integers(-6, 7, (n, n))
+    scale = np.where(rng.random(n) < 0.05, 1e-300, 1.0)      # rows / columns of tiny values
+    X = X * scale[:, None]
+    K = np.triu(X) + np.triu(X, 1).T
+    assert (K == K.T).all()
+    Kp = np.zeros((n, ld))
+    Kp[:, :n] = K
+    Kp[:, n:] = np.nan                                       # (the padding is never read)
+    Kd = torch.from_numpy(Kp).cuda()
+    ntests = [0, 1, 127, 128, 129, 3000]
+    split = min(l, (2 * l) // 3 | 1)
+    for i in range(len(ntests)):
+        probs = []
+        for p, n0 in enumerate((0, l, split)):
+            idx = np.sort(rng.choice(n, l, replace=False)) if p == 1 else rng.choice(n, l, replace=False)
+            alpha = rng.uniform(0, 1, l) * 10.0 ** rng.integers(-4, 3, l)
+            alpha[rng.random(l) < 0.25] = 0.0
+            for k in (n0 - 1, n0):                           # the samples either side of the class boundary count
+                if 0 <= k < l:
+                    alpha[k] = 0.75
+            if p == 0 and i == 2:
+                alpha[:] = 0.0                                # no support vectors: +0.0 - rho, rho = +0.0
+            rho = (0.0, -1.25, 0.3)[p] if l > 1 else 0.0
+            test = rng.choice(n, ntests[(i + p) % len(ntests)], replace=False).astype(np.int32)
+            probs.append((idx.astype(np.int32), n0, alpha, rho, test))
+        off = np.array([0, l, 2 * l, 3 * l], dtype=np.int64)
+        toff = np.zeros(4, dtype=np.int64)
+        toff[1:] = np.cumsum([len(pr[4]) for pr in probs])
+        d_idx = torch.from_numpy(np.concatenate([pr[0] for pr in probs])).cuda()
+        d_alpha = torch.from_numpy(np.concatenate([pr[2] for pr in probs])).cuda()
+        d_rho = torch.tensor([pr[3] for pr in probs], dtype=torch.float64).cuda()
+        d_test = torch.from_numpy(np.concatenate([pr[4] for pr in probs] + [np.zeros(1, np.int32)])).cuda()
+        d_dec = torch.full((int(toff[-1]) + 4,), 123.5, dtype=torch.float64).cuda()
+        n0s = np.array([pr[1] for pr in probs], dtype=np.int32)
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = lib.gkmsvm_decision_batch(0, Kd.data_ptr(), ld, 3, d_idx.data_ptr(), off.ctypes.data, n0s.ctypes.data,
+                                       d_alpha.data_ptr(), d_rho.data_ptr(), d_test.data_ptr(), toff.ctypes.data,
+                                       d_dec.data_ptr(), stream)
+        assert rc == 0, lib.gkmsvm_last_error().decode()
+        dec = d_dec.cpu().numpy()
+        assert (dec[toff[-1]:] == 123.5).all()
+        for p, (idx, n0, alpha, rho, test) in enumerate(probs):
+            want = _decision_reference(K, idx, n0, alpha, rho, test)
+            got = dec[toff[p]:toff[p + 1]]
+            assert got.tobytes() == want.tobytes(), (l, len(test), n0, np.abs(got - want).max() if len(test) else 0)
+            for t in range(0, len(test), 97):                # the reference against the exact sum
+                terms = [(a if k < n0 else -a) * K[idx[k], test[t]] for k, a in enumerate(alpha) if a > 0]
+                exact = math.fsum(terms + [-rho])
+                bound = (l + 1) * np.finfo(float).eps * (sum(abs(x) for x in terms) + abs(rho))
+                assert abs(want[t] - exact) <= bound + 1e-320
