@@ -42,53 +42,13 @@ struct StreamSet { /* destroyed on every path out of the function that owns it *
  * call, the copy stream shared the Gram stream's queue, and every device-to-host copy of the call waited for the LAST
  * Gram kernel (first piece in staging at 84 ms of 92, tools/boundary_ab.py --trace).  So: a candidate stream is kept
  * only if a tiny copy on it completes while a 2-ms spin kernel is still running on the compute stream; candidates
- * that fail stay alive until the search is over, so that the next one lands on another queue. */
+ * that fail stay alive until the search is over, so that the next one lands on another queue.
+ * k_spin is that spin kernel (runs_beside): one wave watching the 100-MHz wall clock for `ticks`. */
 __global__ void k_spin(long long ticks, unsigned *sink)
 {
     const long long t0 = wall_clock64();
     while (wall_clock64() - t0 < ticks) { }
     if (ticks == 1234567) sink[0] = 1u;
-}
-
-/* Keeps `stream` busy for `microseconds` with ONE wave (k_spin): the multi-GPU path puts it in front of chunk c+1's launch
- * so that the transfer of chunk c, which becomes runnable on another stream at the same moment, has its workgroups on the
- * device before the Gram kernel takes every wave slot (gkm_multi.hip; tools/collective_beside_probe.py). */
-extern "C" int gkmhip_pause_stream(void *stream, int microseconds)
-{
-    if (microseconds <= 0) return 0;
-    if (microseconds > 10000) return set_err_msg("gkmhip_pause_stream: more than 10 ms", 2);
-    hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, (hipStream_t)stream, (long long)microseconds * 100, (unsigned *)nullptr); /* 100 MHz */
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-/* Measurement only (tools/collective_beside_probe.py): a device-to-device copy by `blocks` workgroups of `threads` threads,
- * the launch shape of a collective's kernel (a few large, persistent workgroups), to see on ONE GPU whether such
- * workgroups get onto the device while a Gram kernel holds every wave slot. */
-__global__ void k_probe_copy(uint4 *dst, const uint4 *src, size_t n16)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x) dst[i] = src[i];
-}
-
-extern "C" int gkmhip_probe_copy(void *dst, const void *src, size_t bytes, int blocks, int threads, void *stream)
-{
-    if (!dst || !src || blocks < 1 || threads < 64 || threads > 1024 || (bytes & 15)) return set_err_msg("gkmhip_probe_copy: bad arguments", 2);
-    hipLaunchKernelGGL(k_probe_copy, dim3((unsigned)blocks), dim3((unsigned)threads), 0, (hipStream_t)stream, (uint4 *)dst,
-                       (const uint4 *)src, bytes / 16);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-/* Measurement only: `blocks` workgroups of `threads` threads that do nothing but watch the clock for `microseconds` -- a
- * stand-in for a collective's workgroups waiting for their peers while they hold their wave slots. */
-extern "C" int gkmhip_probe_spin(int blocks, int threads, int microseconds, void *stream)
-{
-    if (blocks < 1 || threads < 64 || threads > 1024 || microseconds < 1 || microseconds > 100000)
-        return set_err_msg("gkmhip_probe_spin: bad arguments", 2);
-    hipLaunchKernelGGL(k_spin, dim3((unsigned)blocks), dim3((unsigned)threads), 0, (hipStream_t)stream, (long long)microseconds * 100,
-                       (unsigned *)nullptr);
-    HIPCHK(hipGetLastError());
-    return 0;
 }
 
 /* what the drop-in call's copy-out pipeline measured last time (gram_part_to_host_rows cuts its row blocks by it) */
@@ -120,26 +80,8 @@ static bool runs_beside(hipStream_t busy, hipStream_t other, unsigned *d_word, u
 /* A new non-blocking stream on the current device that runs beside every stream of `busy` (see PipeStreams: streams
  * that share a hardware queue execute in order); after six candidates the last one is returned whatever it shares.
  * *beside says which it was. */
-/* CU mask that leaves `reserve` compute units to other streams, the same number in every XCD whichever way the mask's bits
- * are numbered (XCD = bit / 32 or bit % 8): the j-th reserved CU of XCD k is bit 32 k + (k + 8 j) % 32.  A mask that takes
- * its CUs from ONE XCD slows a machine-filling kernel by 50 % (its workgroups are dealt to the XCDs round robin:
- * profiles/r4_overlap_probe.txt). */
-static std::vector<uint32_t> mask_reserving(int reserve)
+extern "C" void *gkmhip_create_stream_beside(void *const *busy, int nbusy, int *beside)
 {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return {};
-    const int cus = prop.multiProcessorCount;
-    if (cus != 256 || reserve <= 0 || reserve % 8 || reserve > 32) return {}; /* (laid out for the MI355X's 8 x 32 CUs) */
-    std::vector<uint32_t> m((size_t)cus / 32, 0xFFFFFFFFu);
-    for (int j = 0; j < reserve / 8; j++)
-        for (int k = 0; k < 8; k++) m[(size_t)k] &= ~(1u << ((k + 8 * j) % 32));
-    return m;
-}
-
-static void *stream_beside(void *const *busy, int nbusy, int *beside, const int *priority, int reserve_cus = 0)
-{
-    const std::vector<uint32_t> cumask = mask_reserving(reserve_cus);
     unsigned *d_word = nullptr, *h_word = nullptr;
     if (hipMalloc((void **)&d_word, 2 * sizeof(unsigned)) != hipSuccess) return nullptr;
     if (hipHostMalloc((void **)&h_word, sizeof(unsigned), hipHostMallocPortable) != hipSuccess) {
@@ -151,10 +93,7 @@ static void *stream_beside(void *const *busy, int nbusy, int *beside, const int 
     bool ok = false;
     for (int attempt = 0; attempt < 6 && !ok; attempt++) {
         hipStream_t c = nullptr;
-        const hipError_t e = !cumask.empty() ? hipExtStreamCreateWithCUMask(&c, (uint32_t)cumask.size(), cumask.data())
-                             : priority      ? hipStreamCreateWithPriority(&c, hipStreamNonBlocking, *priority)
-                                             : hipStreamCreateWithFlags(&c, hipStreamNonBlocking);
-        if (e != hipSuccess) break;
+        if (hipStreamCreateWithFlags(&c, hipStreamNonBlocking) != hipSuccess) break;
         ok = true;
         for (int i = 0; i < nbusy && ok; i++) ok = runs_beside((hipStream_t)busy[i], c, d_word, h_word);
         if (ok || attempt == 5) got = c;
@@ -165,22 +104,6 @@ static void *stream_beside(void *const *busy, int nbusy, int *beside, const int 
     (void)hipHostFree(h_word);
     if (beside) *beside = ok ? 1 : 0;
     return got;
-}
-
-extern "C" void *gkmhip_create_stream_beside(void *const *busy, int nbusy, int *beside)
-{
-    return stream_beside(busy, nbusy, beside, nullptr);
-}
-
-extern "C" void *gkmhip_create_stream_beside_prio(void *const *busy, int nbusy, int *beside, int priority)
-{
-    return stream_beside(busy, nbusy, beside, &priority);
-}
-
-extern "C" void *gkmhip_create_stream_reserving(void *const *busy, int nbusy, int *beside, int reserve_cus)
-{
-    if (mask_reserving(reserve_cus).empty()) return nullptr;
-    return stream_beside(busy, nbusy, beside, nullptr, reserve_cus);
 }
 
 /* The device's pair of streams, created and probed at the first call; the caller holds it until pipe_streams_done()
@@ -308,16 +231,16 @@ static int gram_part_to_host_rows(gkmhip_ctx *ctx, double *G, int64_t ld, double
      * is cut the same way, down to a last block of ~5 %.  T and S come from what the previous call of the process
      * measured (g_ship), estimates before that.  16 threads, n = 10 000: 0.80 / 0.16 / 0.04 of the area -- 3 launches
      * instead of round 3's 6 halvings, 79.5 instead of 81.7 ms for the call (tools/boundary_ab.py; profiles/r4_boundary_ab*);
-     * one thread: seven blocks from 0.36 down.  (GKM_EQUAL_BLOCKS=1 keeps the equal blocks of round 1, for A/B runs.) */
+     * one thread: seven blocks from 0.36 down. */
     std::vector<RowPiece> blocks, pieces;
     std::vector<int> block_of; /* piece -> block */
-    const bool geometric = nparts == 1 && getenv("GKM_EQUAL_BLOCKS") == nullptr;
+    const bool geometric = nparts == 1;
     /* (whole rows as ONE linear copy per piece instead of a pitched copy of the columns [0, r1) -- twice the bytes --
      * was measured in round 4: 102 instead of 96 ms on the same schedule) */
     const double total_area = (double)n * n / 2.0;
     const double area_cap = total_area / std::max(12, 4 * nparts);
     int index = 0;
-    double left = total_area, target = total_area / 2.0;
+    double left = total_area;
     double ship_ratio; /* S / T */
     {
         std::lock_guard<std::mutex> lock(g_ship.m);
@@ -331,27 +254,10 @@ static int gram_part_to_host_rows(gkmhip_ctx *ctx, double *G, int64_t ld, double
     }
     /* (1.3: a piece is copied, THEN scattered; only the copy of the next piece overlaps the scatter) */
     const double first_share = std::min(0.8, std::max(0.3, 1.0 / (1.0 + 1.3 * ship_ratio)));
-    /* GKM_BLOCK_FRACTIONS="0.7,0.2" (experiments): the blocks' shares of the triangle's area, the last block takes the rest */
-    std::vector<double> fractions;
-    if (const char *bf = getenv("GKM_BLOCK_FRACTIONS"))
-        for (const char *q = bf; *q;) {
-            char *end = nullptr;
-            const double v = strtod(q, &end);
-            if (end == q) break;
-            if (v > 0.0 && v < 1.0) fractions.push_back(v);
-            q = *end ? end + 1 : end;
-        }
-    size_t fi = 0;
     for (int r0 = 0; r0 < n;) {
         int r1 = r0 + 1;
-        if (geometric && !fractions.empty()) {
-            target = fi < fractions.size() ? fractions[fi++] * total_area : left;
-            while (r1 < n && ((double)(r1 + 1) * (r1 + 1) - (double)r0 * r0) / 2.0 <= target) r1++;
-            if (fi > fractions.size() || n - r1 < 32) r1 = n;
-            if (fi == fractions.size()) fi++; /* the next block is the last one */
-            left -= ((double)r1 * r1 - (double)r0 * r0) / 2.0;
-        } else if (geometric) {
-            target = left <= 0.06 * total_area ? left : first_share * left; /* (the rest in one go) */
+        if (geometric) {
+            const double target = left <= 0.06 * total_area ? left : first_share * left; /* (the rest in one go) */
             while (r1 < n && ((double)(r1 + 1) * (r1 + 1) - (double)r0 * r0) / 2.0 <= target) r1++;
             if (n - r1 < 32) r1 = n;
             left -= ((double)r1 * r1 - (double)r0 * r0) / 2.0;

@@ -17,7 +17,7 @@
  * What travels are PACKED slabs (gkm_shard.h): row a as a + 1 doubles -- only j <= a is ever read -- n^2 / (2G)
  * doubles per rank and matrix, half of what full-width rows cost (round 3).
  * The chunks of a rank follow each other on ONE compute stream; the transfer of chunk c runs on a second stream and
- * overlaps the kernel of chunk c+1 (compute_streams() below has the measurement that took the second compute stream away).  Integer profiles are placement-independent,
+ * overlaps the kernel of chunk c+1 (see RankCache for why not two compute streams).  Integer profiles are placement-independent,
  * so the assembled matrix is bit-identical to the single-GPU one for any number of devices.
  */
 #include <hip/hip_runtime.h>
@@ -152,13 +152,19 @@ private:
  * same size per run): the slab of this rank's rows, the gathered slabs of all ranks, the gather index, the self
  * norms, the compute and the transfer stream and the events.  hipMalloc / hipFree synchronise the whole device, so a call that allocated
  * ~1.7 GB and freed it again paid for that beside a ~10 ms kernel on 8 GPUs.  Keyed by (device, n, ranks, chunks);
- * rebuilt when any of them changes, freed by gkmhip_release_comms(). */
+ * rebuilt when any of them changes, freed by gkmhip_release_comms().
+ *
+ * ONE compute stream: two chunk launches on two streams run CONCURRENTLY, workgroup by workgroup, and complete together
+ * (chunk 0 of 2 ended at 8.63 ms of a rank's 8.88, stream priorities do not repair it: tools/rank_alone.py,
+ * profiles/r5_rank_alone_c2_two_streams.txt, r5_rank_alone_stream_policies.txt), so nothing of chunk 0's transfer could
+ * hide behind chunk 1's kernel, which is the only reason to cut a rank's rows into chunks.  On one stream chunk 0 is
+ * complete at 4.5 of 9.0 ms; the drain that is no longer overlapped costs 0.2-0.3 ms per chunk boundary. */
 struct RankCache {
-    int dev = -1, n = 0, G = 0, chunks = 0, nsk = 0;
+    int dev = -1, n = 0, G = 0, chunks = 0;
     int64_t pe = 0; /* doubles per (packed) chunk slab */
     double *slab = nullptr, *gathered = nullptr, *sq = nullptr;
     int64_t *d_slot = nullptr;
-    hipStream_t sk[2] = {nullptr, nullptr}, sc = nullptr;
+    hipStream_t sk = nullptr, sc = nullptr; /* compute, transfer */
     std::vector<hipEvent_t> ready;          /* [chunk] slab complete (no timing: waited for by peers) */
     std::vector<hipEvent_t> k0, k1, a0, a1; /* [chunk] timing: kernel of the chunk, transfer of the chunk */
     hipEvent_t n0 = nullptr, n1 = nullptr;  /* timing: un-permute + normalise */
@@ -181,28 +187,13 @@ void cache_release(RankCache &R)
     }
     if (R.n0) (void)hipEventDestroy(R.n0);
     if (R.n1) (void)hipEventDestroy(R.n1);
-    for (int i = 0; i < 2; i++)
-        if (R.sk[i]) (void)hipStreamDestroy(R.sk[i]);
+    if (R.sk) (void)hipStreamDestroy(R.sk);
     if (R.sc) (void)hipStreamDestroy(R.sc);
     R = RankCache();
 }
 
-/* How many compute streams a rank's chunk launches alternate between: ONE.  Rounds 2-5 used two ("the kernel of chunk c+1
- * overlaps the drain of chunk c"), and round 5 measured what that does (tools/rank_alone.py prints when each chunk ran,
- * profiles/r5_rank_alone_c2_two_streams.txt, r5_rank_alone_stream_policies.txt): two launches on two streams run CONCURRENTLY, workgroup by workgroup, and complete
- * together -- chunk 0 of 2 ended at 8.63 ms of a rank's 8.88 -- so nothing of chunk 0's transfer hid behind chunk 1's
- * kernel, which is the only reason to cut a rank's rows into chunks.  (Stream priorities do not repair it: the
- * higher-priority launch gets ~60 % of the device, and its small kernels that follow ended with the OTHER launch in
- * most runs.)  On one stream chunk 0 is complete at 4.5 of 9.0 ms; the drain that is no longer overlapped costs 0.2-0.3 ms
- * per chunk boundary.  GKM_MULTI_STREAMS=two brings the old behaviour back for measurements. */
-int compute_streams()
-{
-    const char *e = getenv("GKM_MULTI_STREAMS");
-    return (e && !strcmp(e, "two")) ? 2 : 1;
-}
-
 struct Call {
-    int G = 0, n = 0, chunks = 1, symmetric = 0, nsk = 1;
+    int G = 0, n = 0, chunks = 1, symmetric = 0;
     int64_t ld = 0, pe = 0;
     bool use_rccl = false;
     gkmhip_ctx **ctxs = nullptr;
@@ -251,9 +242,9 @@ void rank_thread(Call &C, int g)
 
     /* ---- phase 0: buffers, streams, events (kept from the previous call of the same shape) ---- */
     MCHK(hipSetDevice(dev));
-    if (!fail && !(R.dev == dev && R.n == n && R.G == G && R.chunks == chunks && R.pe == C.pe && R.nsk == C.nsk)) {
+    if (!fail && !(R.dev == dev && R.n == n && R.G == G && R.chunks == chunks && R.pe == C.pe)) {
         cache_release(R);
-        R.dev = dev; R.n = n; R.G = G; R.chunks = chunks; R.pe = C.pe; R.nsk = C.nsk;
+        R.dev = dev; R.n = n; R.G = G; R.chunks = chunks; R.pe = C.pe;
         auto dmalloc = [&](void **p, size_t bytes) { g_allocs++; return hipMalloc(p, bytes); };
         MCHK(dmalloc((void **)&R.slab, (size_t)chunks * slab_elems * sizeof(double)));
         if (!fail) MCHK(dmalloc((void **)&R.gathered, (size_t)chunks * (size_t)G * slab_elems * sizeof(double)));
@@ -261,15 +252,10 @@ void rank_thread(Call &C, int g)
         if (!fail) MCHK(dmalloc((void **)&R.sq, (size_t)n * sizeof(double)));
         /* The transfer stream must not share a hardware queue with the compute stream (streams on one queue execute in
          * order: the all-gather of chunk c would wait for the kernel of chunk c+1), so it is probed against it. */
-        void *busy[3] = {nullptr, nullptr, nullptr};
-        for (int i = 0; i < R.nsk && !fail; i++) {
-            if (i == 0) MCHK(hipStreamCreateWithFlags(&R.sk[0], hipStreamNonBlocking));
-            else R.sk[i] = (hipStream_t)gkmhip_create_stream_beside(busy, i, nullptr);
-            if (!fail && !R.sk[i]) { fail = true; C.err[(size_t)g] = "cannot create the rank's streams"; }
-            busy[i] = R.sk[i];
-        }
+        if (!fail) MCHK(hipStreamCreateWithFlags(&R.sk, hipStreamNonBlocking));
         if (!fail) {
-            R.sc = (hipStream_t)gkmhip_create_stream_beside(busy, R.nsk, nullptr);
+            void *busy[1] = {R.sk};
+            R.sc = (hipStream_t)gkmhip_create_stream_beside(busy, 1, nullptr);
             if (!R.sc) { fail = true; C.err[(size_t)g] = "cannot create the rank's streams"; }
         }
         R.ready.assign((size_t)chunks, nullptr);
@@ -290,7 +276,7 @@ void rank_thread(Call &C, int g)
     }
     if (fail) C.failed = 1;
     C.bar->wait();
-    hipStream_t *sk = R.sk, sc = R.sc;
+    const hipStream_t sk = R.sk, sc = R.sc;
     RankStats st_out;
     timespec ts_step0;
     clock_gettime(CLOCK_MONOTONIC, &ts_step0);
@@ -300,25 +286,25 @@ void rank_thread(Call &C, int g)
         const bool go = !C.failed.load();
         double *my_slab = go ? R.slab + (size_t)c * slab_elems : nullptr;
         if (go) {
-            hipStream_t st = sk[c % R.nsk];
             const std::vector<int> &rows = parts[(size_t)c];
             /* The transfer of chunk c - 1 becomes runnable (stream sc) when this launch group does, and it must be FIRST on
              * the device: a collective's workgroups of 256-512 threads never start beside a running Gram kernel, which holds
              * 7 of 8 wave slots and 504 of 512 VGPRs of every SIMD and replaces each wave that retires at once (round 5, one
-             * GPU, tools/collective_beside_probe.py: a 90-MB copy by 64 x 256 threads enqueued mid-kernel takes 5.3 ms
-             * instead of 0.10 and ends when the kernel does; one that waits for the previous kernel's event takes 0.19).
-             * What gives it the head start is this group's own table upload and row-plane kernel, ~0.1 ms in front of
-             * the Gram kernel: whoever moves them out of the way must put a pause here (gkmhip_pause_stream). */
-            MCHK(hipEventRecord(R.k0[(size_t)c], st));
+             * GPU: a 90-MB copy by 64 x 256 threads enqueued mid-kernel takes 5.3 ms instead of 0.10 and ends when the
+             * kernel does; one that waits for the previous kernel's event takes 0.19: profiles/r5_collective_beside_probe*.txt).
+             * The code relies on this group's own table upload and row-plane kernel, ~0.1 ms in front of the Gram kernel
+             * (profiles/r5_rank_alone_kernel_trace.txt), to give that transfer its head start; nothing else enforces it,
+             * and it has not been verified on more than one GPU. */
+            MCHK(hipEventRecord(R.k0[(size_t)c], sk));
             if (!rows.empty()) {
                 const std::vector<int64_t> roff = gkmshard::packed_row_offsets(rows);
                 int rc = gkmhip_set_scratch_slot(C.ctxs[g], c & 1);
-                if (!rc) rc = gkmhip_gram_rows_packed(C.ctxs[g], rows.data(), (int)rows.size(), my_slab, roff.data(), st);
+                if (!rc) rc = gkmhip_gram_rows_packed(C.ctxs[g], rows.data(), (int)rows.size(), my_slab, roff.data(), sk);
                 if (rc && !fail) { fail = true; C.err[(size_t)g] = gkmhip_last_error(); }
                 if (!rc) st_out.comparisons += gkmhip_last_comparisons(C.ctxs[g]);
             }
-            MCHK(hipEventRecord(R.k1[(size_t)c], st));
-            MCHK(hipEventRecord(R.ready[(size_t)c], st));
+            MCHK(hipEventRecord(R.k1[(size_t)c], sk));
+            MCHK(hipEventRecord(R.ready[(size_t)c], sk));
             if (fail) C.failed = 1;
         }
         if (C.use_rccl) {
@@ -367,8 +353,7 @@ void rank_thread(Call &C, int g)
         MCHK(hipEventRecord(R.n1, sc));
         assembled = !fail;
     }
-    for (int i = 0; i < 2; i++)
-        if (sk[i]) (void)hipStreamSynchronize(sk[i]);
+    if (sk) (void)hipStreamSynchronize(sk);
     if (sc && !C.stuck.load()) {
         hipError_t e = hipStreamSynchronize(sc);
         if (e != hipSuccess && !fail) { fail = true; C.err[(size_t)g] = std::string("hipStreamSynchronize: ") + hipGetErrorString(e); }
@@ -461,8 +446,7 @@ extern "C" int gkmhip_gram_rank_alone(gkmhip_ctx *ctx, int rank, int ranks, int 
     C.chunks = chunks > 0 ? chunks : (ranks == 1 ? 1 : gkmshard::auto_chunks(C.n, ranks));
     C.pe = gkmshard::packed_chunk_elems(C.n, ranks, C.chunks);
     const RankCache &R = g_cache[rank];
-    C.nsk = compute_streams();
-    if (!(R.dev == gkmhip_device_of(ctx) && R.n == C.n && R.G == ranks && R.chunks == C.chunks && R.pe == C.pe && R.nsk == C.nsk))
+    if (!(R.dev == gkmhip_device_of(ctx) && R.n == C.n && R.G == ranks && R.chunks == C.chunks && R.pe == C.pe))
         return fail_with("gkmhip_gram_rank_alone: no gathered slabs of this shape (run gkmhip_gram_allgather with the same "
                          "number of contexts and chunks first)", 2);
     std::vector<gkmhip_ctx *> ctxs((size_t)ranks, nullptr);
@@ -503,7 +487,6 @@ extern "C" int gkmhip_gram_allgather(gkmhip_ctx **ctxs, int nctx, double **K, in
     C.K = K;
     C.ld = ld;
     C.symmetric = symmetric;
-    C.nsk = compute_streams();
     C.n = gkmhip_n_sequences(ctxs[0]);
     bool distinct = true;
     for (int g = 0; g < nctx; g++) {

@@ -211,23 +211,6 @@ int gkmhip_assemble_normalize(gkmhip_ctx *ctx, const double *slabs, int64_t lds,
  * candidate is tried with a 2-ms spin kernel on the busy stream and a 4-byte copy on the candidate; after six
  * candidates the last one is returned anyway (*beside = 0).  NULL on error.  Destroy it with hipStreamDestroy. */
 void *gkmhip_create_stream_beside(void *const *busy, int nbusy, int *beside);
-/* The same with a stream priority (hipStreamCreateWithPriority; hipDeviceGetStreamPriorityRange gives the range, the
- * numerically LOWEST value is the highest priority). */
-void *gkmhip_create_stream_beside_prio(void *const *busy, int nbusy, int *beside, int priority);
-/* A compute stream that leaves `reserve_cus` (8, 16, 24 or 32: the same number in each of the MI355X's 8 XCDs) compute
- * units to OTHER streams (hipExtStreamCreateWithCUMask).  Why: a workgroup of several waves -- a collective's kernel, a
- * blit copy -- cannot start while the Gram kernel holds 7 of 8 wave slots and 504 of 512 VGPRs of every SIMD (each wave
- * that retires is replaced by the kernel's next one-wave workgroup at once); enqueued mid-kernel on a high-priority stream
- * it ends when the kernel does (tools/collective_beside_probe.py).  NULL if the device is not laid out as 8 x 32 CUs. */
-void *gkmhip_create_stream_reserving(void *const *busy, int nbusy, int *beside, int reserve_cus);
-/* Keeps `stream` busy for `microseconds` (at most 10 000) with one wave that does nothing. */
-int gkmhip_pause_stream(void *stream, int microseconds);
-/* Measurement only: `blocks` workgroups of `threads` threads that hold their wave slots for `microseconds` and do nothing
- * (a collective's workgroups waiting for their peers). */
-int gkmhip_probe_spin(int blocks, int threads, int microseconds, void *stream);
-/* Measurement only: copies `bytes` (a multiple of 16) on the device with `blocks` workgroups of `threads` threads on
- * `stream` -- the launch shape of a collective's kernel (tools/collective_beside_probe.py). */
-int gkmhip_probe_copy(void *dst, const void *src, size_t bytes, int blocks, int threads, void *stream);
 
 /* The pinned staging buffers of the copy-out calls (2 x 64 MB) are kept for the life of the
  * process; this releases them (optional). */

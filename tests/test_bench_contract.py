@@ -372,11 +372,11 @@ def test_merge_of_the_two_assemblies():
 def test_committed_pmc_summaries_match_the_kernel_source():
     """The line's roofline.frac comes from profiles/r*_pmc_<workload>.json, which bench.py accepts only if it was taken
     on THIS kernel source (SHA-256 of bench.KERNEL_SOURCES: the hot kernel, its headers, the launch geometry).  An edit to those files after the last
-    tools/finalize_r4.sh run would silently turn frac into null in the driver's line: caught here."""
+    tools/collect_profiles.sh run would silently turn frac into null in the driver's line: caught here."""
     sys.path.insert(0, ROOT)
     import bench
     for wl in ("c2", "peaks", "c5"):
         d, src = bench.pmc_summary(wl)
-        assert d is not None, "%s: %s -- re-run tools/finalize_r4.sh on the GPU box" % (wl, src)
+        assert d is not None, "%s: %s -- re-run tools/collect_profiles.sh on the GPU box" % (wl, src)
         assert d["per_launch"]["SQ_INSTS_VALU"] > 0
         assert bench.issue_model(wl) is not None, "profiles/r*_issue_model.json is stale: python3 tools/issue_model.py --round r4"

@@ -196,9 +196,10 @@ def test_config4_as_the_pipeline_runs_it(built, tmp_path):
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,rng", [(4400, None), (2000, (150, 600))])
 def test_boundary_blocks_and_pieces_against_one_launch(built, tmp_path, monkeypatch, n, rng):
-    """The drop-in call cuts the matrix into geometrically shrinking row blocks (one Gram launch each) that travel
-    to the caller's rows in staging-sized pieces; at 4 400 rows the first block needs two pieces.  Bit for bit the
-    matrix the device layer computes in one launch, also with the equal-area blocks kept for A/B runs."""
+    """The drop-in call cuts the matrix into row blocks (one Gram launch each) that travel to the caller's rows in
+    staging-sized pieces; at 4 400 rows the first block needs two pieces.  Bit for bit the matrix the device layer
+    computes in one launch, whatever the cut: geometrically shrinking blocks sized by the caller's thread count (-@ 1
+    and 16 give different schedules) and equal-area blocks dealt over two device contexts (GKM_DEVICES=0,0)."""
     from gkmqc_amd import gkmsvm, synth
     pos, neg = str(tmp_path / "p.fa"), str(tmp_path / "n.fa")
     synth.write_problem(pos, neg, n // 2, n - n // 2, 300, rng)
@@ -206,15 +207,13 @@ def test_boundary_blocks_and_pieces_against_one_launch(built, tmp_path, monkeypa
     args = [4, L, k, d, 50, 50.0, 1.0, pos, neg, 8, 0]
     want, n_pos, n_neg = gkmsvm.computeGkmKernel(args, backend="device")
     assert (n_pos, n_neg) == (n // 2, n - n // 2)
-    got, _, _ = gkmsvm.computeGkmKernel(args, backend="boundary")
-    assert np.array_equal(got, want)
-    monkeypatch.setenv("GKM_EQUAL_BLOCKS", "1")
-    got, _, _ = gkmsvm.computeGkmKernel(args, backend="boundary")
-    assert np.array_equal(got, want)
-    monkeypatch.delenv("GKM_EQUAL_BLOCKS")
-    monkeypatch.setenv("GKM_BLOCK_FRACTIONS", "0.3,0.3,0.2,0.1")     # any cut of the rows into blocks gives the same matrix
-    got, _, _ = gkmsvm.computeGkmKernel(args, backend="boundary")
-    assert np.array_equal(got, want)
+    for threads, devices in ((1, None), (16, None), (8, "0,0")):
+        if devices:
+            monkeypatch.setenv("GKM_DEVICES", devices)
+        else:
+            monkeypatch.delenv("GKM_DEVICES", raising=False)
+        got, _, _ = gkmsvm.computeGkmKernel(args[:9] + [threads, 0], backend="boundary")
+        assert np.array_equal(got, want), (threads, devices)
 
 
 @pytest.mark.gpu

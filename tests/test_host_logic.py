@@ -35,6 +35,14 @@ def test_every_declared_symbol_is_exported(dev, header, least):
         assert hasattr(lib, name), "%s declared in include/%s but not exported" % (name, header)
 
 
+@pytest.mark.parametrize("name", ["gkmhip_probe_copy", "gkmhip_probe_spin", "gkmhip_pause_stream",
+                                  "gkmhip_create_stream_reserving", "gkmhip_create_stream_beside_prio"])
+def test_measurement_probes_are_not_exported(dev, name):
+    """The one-off probes of the collective-beside-Gram question are answered (profiles/r5_collective_beside_probe*.txt)
+    and are no part of the drop-in library's surface."""
+    assert not hasattr(ctypes.CDLL(dev.lib_path()), name)
+
+
 def test_gkmopt_layout_matches_reference(dev):
     # x86-64 offsets probed from the reference build (SURVEY.md §8(b))
     offs = [getattr(dev.gkmOpt, f).offset for f, _ in dev.gkmOpt._fields_]

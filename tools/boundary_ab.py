@@ -3,10 +3,9 @@
 process of its own, `--calls` calls (FASTA on disk -> the caller's pageable numpy rows), first call and the warm minimum.
 
     python3 tools/boundary_ab.py [--workload c2|peaks|c3|c5] [--calls 5] [--rounds 2] [--trace]
-        [--settings "default" "GKM_KEEP_DEVICE=0" "GKM_BLOCK_FRACTIONS=0.5,0.25,0.125,0.0625,0.03" "GKM_EQUAL_BLOCKS=1"]
+        [--settings "default" "GKM_KEEP_DEVICE=0"]
 
-GKM_KEEP_DEVICE=0 is round 3's behaviour (context and matrix created and freed per call), GKM_BLOCK_FRACTIONS=0.5,... its
-block schedule (halvings), GKM_EQUAL_BLOCKS=1 round 1's.  Worker mode: --worker (internal).
+GKM_KEEP_DEVICE=0 is round 3's behaviour (context and matrix created and freed per call).  Worker mode: --worker (internal).
 """
 import argparse
 import ctypes
@@ -53,8 +52,7 @@ def main():
     ap.add_argument("--threads", type=int, default=0, help="the call's nthreads (the caller's -@); 0 = the cores of the box")
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--trace", action="store_true", help="GKM_TRACE=1 and verbosity 3: the call's own phase timings on stderr")
-    ap.add_argument("--settings", nargs="*", default=["default", "GKM_KEEP_DEVICE=0", "GKM_BLOCK_FRACTIONS=0.5,0.25,0.125,0.0625,0.03",
-                                                      "GKM_EQUAL_BLOCKS=1"])
+    ap.add_argument("--settings", nargs="*", default=["default", "GKM_KEEP_DEVICE=0"])
     args = ap.parse_args()
     if args.worker:
         return worker(args)
