@@ -174,6 +174,7 @@ extern "C" void gkmhip_destroy(gkmhip_ctx *ctx)
     ctx->len.release(); ctx->lmf.release(); ctx->sb.release(); ctx->colpk.release(); ctx->postab.release();
     for (auto &scr : ctx->scratch) scr.release();
     ctx->sq.release();
+    ctx->ex_rows.release(); ctx->ex_part.release();
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     for (auto &pr : ctx->tl_pairs) {

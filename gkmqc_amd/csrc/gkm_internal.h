@@ -9,6 +9,7 @@
  *                          the general kernel k_gram_direct, gkmhip_gram_rows*
  *   gkm_normalize.hip      k_sqnorm, k_normalize, k_assemble_normalize: square roots of the diagonal, division, RBF
  *   gkm_copyout.hip        device matrix -> the caller's host rows: row blocks, staging pieces, the stream prober
+ *   gkm_explain.hip        per-base importance of a trained model (k_explain, k_explain_reduce), gkmhip_explain_block
  */
 #ifndef GKM_INTERNAL_H
 #define GKM_INTERNAL_H
@@ -138,6 +139,8 @@ struct gkmhip_ctx {
     double sampled_hit_share = -1.0; /* share of sampled l-mer pairs of THESE sequences within d mismatches (set_sequences) */
     double last_comparisons = 0;
     const char *last_kernel = "none";
+    DevBuf<int> ex_rows;      /* gkmhip_explain_block: its row list and the partial rows of its support-vector chunks */
+    DevBuf<double> ex_part;
 };
 
 /* the pair of events the next Gram kernel is bracketed by (gkm_context.hip) */

@@ -115,6 +115,8 @@ def load():
     L.gkmhip_gram_block.argtypes = (vp, vp, i32, i32, i32, vp, i64, vp)
     L.gkmhip_normalize_block.restype = i32
     L.gkmhip_normalize_block.argtypes = (vp, vp, i32, i32, i32, vp, i64, vp, vp)
+    L.gkmhip_explain_block.restype = i32
+    L.gkmhip_explain_block.argtypes = (vp, vp, i32, i32, i32, vp, vp, vp, vp, vp)
     L.gkmhip_self_norms.restype = i32
     L.gkmhip_self_norms.argtypes = (vp, vp, vp)
     L.gkmhip_normalize_rows_full.restype = i32
@@ -368,6 +370,18 @@ class GramContext:
         rows = np.ascontiguousarray(rows, dtype=np.int32)
         self._chk(self.lib.gkmhip_normalize_block(self.handle, rows.ctypes.data, len(rows), int(col_begin), int(col_end),
                                                   G_ptr, ld, sq_ptr, stream), "gkmhip_normalize_block")
+
+    def explain_block(self, rows, col_begin, col_end, share, coef_ptr, xscale_ptr, out_ptr, stream=0):
+        """Per-base importance of the queries [col_begin, col_end) against the support vectors `rows` into out_ptr (the
+        bases of the range back to back): share = d + 1 host doubles, coef_ptr = len(rows) device doubles, xscale_ptr =
+        one device double per query or None (include/gkm_hip.h gkmhip_explain_block)."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        share = np.ascontiguousarray(share, dtype=np.float64)
+        if len(share) != self.d + 1:
+            raise GkmError("explain_block: share needs d + 1 = %d values" % (self.d + 1))
+        self._chk(self.lib.gkmhip_explain_block(self.handle, rows.ctypes.data, len(rows), int(col_begin), int(col_end),
+                                                share.ctypes.data, coef_ptr, xscale_ptr, out_ptr, stream),
+                  "gkmhip_explain_block")
 
     def self_norms(self, sq_ptr, stream=0):
         self._chk(self.lib.gkmhip_self_norms(self.handle, sq_ptr, stream), "gkmhip_self_norms")

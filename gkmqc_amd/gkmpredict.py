@@ -9,10 +9,13 @@ The other half of a gkm-SVM next to the cross-validation of `gkmsvm.py` (the cou
   * `score` uploads [support vectors; a block of queries] into one cached context, takes the self norms of that set,
     computes the S x Qb block of kernel values (gkmhip_gram_block: SVs as rows, queries as columns) and its
     normalisation (gkmhip_normalize_block), and sums the decision values with k_decision (gkmsvm_decision_batch) --
-    scikit-learn's `decision_function` of the trained SVC, bit for bit, for every block size.
+    scikit-learn's `decision_function` of the trained SVC, bit for bit, for every block size;
+  * `explain` splits each query's score over its bases (gkmhip_explain_block): per block the same upload
+    and self norms as `score`, then one launch that credits every matching l-mer pair to the query bases it matched on.
 
     python -m gkmqc_amd.gkmpredict train [-t -L -k -d -M -H -G -C -e -u] pos.fa neg.fa model.txt
     python -m gkmqc_amd.gkmpredict predict query.fa model.txt out.txt
+    python -m gkmqc_amd.gkmpredict explain [--block Qb] query.fa model.txt out.txt
 """
 import argparse
 import logging
@@ -292,6 +295,109 @@ def _score_flat(model, seqs, device, block, kernel, on_block):
     return out
 
 
+# ------------------------------------------------------------------ per-base importance
+EXPLAIN_CHUNKS = 16       # the most partial rows gkmhip_explain_block keeps per base (one per chunk of support vectors)
+
+
+def check_explainable(model):
+    """The models `explain` serves: not the RBF types (exp() breaks completeness) and not k = 0 (d = L is allowed there,
+    and a pair with L mismatches has no matched base to credit)."""
+    if model.kernel_type in (3, 5):
+        raise ModelError("explain: RBF kernels (types 3 and 5) have no per-base decomposition")
+    if model.k == 0:
+        raise ModelError("explain: models with k = 0 have no per-base decomposition (a pair may match on no base)")
+
+
+def explain_shares(model):
+    """share[m] = c_m / (L - m), m = 0..d: what one matched base of a pair with m mismatches is credited."""
+    c = dv.mismatch_weights(model.kernel_type, model.L, model.k)[:model.d + 1]
+    return c / (model.L - np.arange(model.d + 1))
+
+
+def default_explain_block(max_len, budget=BLOCK_BYTES):
+    """Queries per block: the launch's partial rows (up to EXPLAIN_CHUNKS doubles per base) and the output within `budget`
+    bytes of device memory."""
+    return int(max(1, min(1 << 20, budget // (8 * (EXPLAIN_CHUNKS + 1) * max(int(max_len), 64)))))
+
+
+def explain(model, fasta_or_sequences, device=0, block=None, on_block=None):
+    """Per-base importance of `model` for a FASTA file (or a list / FlatSequences of base codes) -> (names, [float64 array
+    of one value per base, per query]):
+
+        E(x)[t] = sum_s dual_coef_s A_s(x)[t] / (sq_s sq_x)
+
+    where A_s(x)[t] credits every l-mer pair of x (forward) and s (forward or reverse complement) with m <= d mismatches
+    with c_m / (L - m) times the pair's positional weights on each of the L - m query bases it matched on.
+    sum_t E(x)[t] = score(x) - model.rho.  For kernel type 0 this is GkmExplain's rule (each shared gapped k-mer split
+    evenly over its k bases); for types 1, 2 and 4 the same rule on this project's c_m.  RBF and k = 0 models are refused.
+    block: queries per device block (default_explain_block).  on_block(dict) (measurements): called after every block
+    with its size, the explain kernel's milliseconds (HIP events), its l-mer comparisons and the block's wall time."""
+    check_explainable(model)
+    seqs, names = _as_queries(fasta_or_sequences)
+    check_queries(model, seqs)
+    return names, _explain_flat(model, seqs, device, block, on_block)
+
+
+def _explain_flat(model, seqs, device, block, on_block=None):
+    import torch
+    S, Q = model.n_sv, len(seqs)
+    lens = np.diff(seqs.off)
+    qb_max = min(Q, int(block) if block else default_explain_block(int(lens.max())))
+    if qb_max < 1:
+        raise ModelError("block must be at least 1")
+    ctx = dv.cached_context(*model.kernel_params(), device=device)
+    share = explain_shares(model)
+    sv_codes = np.concatenate(model.seqs)
+    sv_off = np.zeros(S + 1, dtype=np.int64)
+    np.cumsum([len(s) for s in model.seqs], out=sv_off[1:])
+    rows = np.arange(S, dtype=np.int32)
+    dev = torch.device("cuda", device)
+    out = []
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        sq = torch.empty(S + qb_max, dtype=torch.float64, device=dev)
+        dual = torch.from_numpy(model.dual_coef()).to(dev)
+        most = max(int(seqs.off[min(Q, q0 + qb_max)] - seqs.off[q0]) for q0 in range(0, Q, qb_max))
+        E = torch.empty(most, dtype=torch.float64, device=dev)
+        for q0 in range(0, Q, qb_max):
+            q1 = min(Q, q0 + qb_max)
+            qb = q1 - q0
+            t0 = time.perf_counter()
+            qoff = seqs.off[q0:q1 + 1]
+            union = dv.FlatSequences(np.concatenate((sv_codes, seqs.codes[qoff[0]:qoff[-1]])),
+                                     np.concatenate((sv_off, sv_off[-1] + (qoff[1:] - qoff[0]))))
+            ctx.set_sequences(union, stream)     # (complete on return)
+            ctx.self_norms(sq.data_ptr(), stream)
+            coef = dual / sq[:S]
+            xscale = 1.0 / sq[S:S + qb]
+            ctx.explain_block(rows, S, S + qb, share, coef.data_ptr(), xscale.data_ptr(), E.data_ptr(), stream)
+            host = E[:int(qoff[-1] - qoff[0])].cpu().numpy()
+            out.extend(np.split(host, (qoff[1:-1] - qoff[0]).astype(np.int64)))
+            if on_block is not None:
+                on_block(dict(queries=qb, explain_kernel_ms=ctx.last_kernel_ms(), comparisons=ctx.last_comparisons(),
+                              kernel=ctx.last_kernel_name(), wall_ms=(time.perf_counter() - t0) * 1e3))
+    return out
+
+
+def write_explanation(path, names, values):
+    """The `explain` output: one line per query, name<TAB>v0,v1,... with repr() floats (they read back to the same
+    doubles)."""
+    with open(path, "w") as f:
+        for name, v in zip(names, values):
+            f.write("%s\t%s\n" % (name, ",".join(repr(float(e)) for e in v)))
+
+
+def read_explanation(path):
+    """-> (names, [float64 array per query]) from a file written by write_explanation."""
+    names, values = [], []
+    with open(path) as f:
+        for line in f.read().split("\n")[:-1]:
+            name, vals = line.rsplit("\t", 1)
+            names.append(name)
+            values.append(np.array([float(e) for e in vals.split(",")], dtype=np.float64))
+    return names, values
+
+
 # ------------------------------------------------------------------ command line
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m gkmqc_amd.gkmpredict",
@@ -318,6 +424,12 @@ def build_parser():
     q.add_argument("query_fa")
     q.add_argument("model")
     q.add_argument("output")
+    x = sub.add_parser("explain", help="per-base importance of the sequences of query.fa: name<TAB>v0,v1,... per line")
+    x.add_argument("--device", type=int, default=0, help="GPU (default: 0)")
+    x.add_argument("--block", type=int, default=None, help="queries per device block (default: from device memory)")
+    x.add_argument("query_fa")
+    x.add_argument("model")
+    x.add_argument("output")
     return p
 
 
@@ -355,13 +467,18 @@ def main(argv=None):
             if not os.path.isfile(a.query_fa):
                 raise ModelError("cannot read %s" % a.query_fa)
             m = load(a.model)
+            if a.cmd == "explain":
+                check_explainable(m)
             seqs, names = _as_queries(a.query_fa)
             check_queries(m, seqs)
-            scores = _score_flat(m, seqs, a.device, a.block, dv.KERNEL_AUTO, None)
             tmp = a.output + ".tmp"
-            with open(tmp, "w") as f:
-                for name, s in zip(names, scores):
-                    f.write("%s\t%r\n" % (name, float(s)))
+            if a.cmd == "explain":
+                write_explanation(tmp, names, _explain_flat(m, seqs, a.device, a.block))
+            else:
+                scores = _score_flat(m, seqs, a.device, a.block, dv.KERNEL_AUTO, None)
+                with open(tmp, "w") as f:
+                    for name, s in zip(names, scores):
+                        f.write("%s\t%r\n" % (name, float(s)))
             os.replace(tmp, a.output)
     except (ModelError, dv.GkmError, svmcv.SvmError, OSError) as e:
         print("gkmpredict: error: %s" % e, file=sys.stderr)

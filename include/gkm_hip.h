@@ -104,6 +104,22 @@ int gkmhip_gram_rows_full(gkmhip_ctx *ctx, const int *rows, int nrows, int local
 int gkmhip_gram_block(gkmhip_ctx *ctx, const int *rows, int nrows, int col_begin, int col_end, double *G, int64_t ld,
                       void *stream);
 
+/* Per-base importance: rows are support vectors, the columns [col_begin, col_end) queries.  For query j and
+ * each of its bases t, out[off[j] - off[col_begin] + t] = xscale[j - col_begin] * sum_i coef[i] * A_i(j)[t], the sum over
+ * the rows in list order, where A_i(j)[t] = sum_m share[m] H_m[t] (ascending m) and H_m[t] is the exact integer tally of
+ * w_j[p] w_i[q] over the l-mer pairs (query l-mer p, forward or reverse-complement l-mer q of row i) with m <= d
+ * mismatches whose base t - p is a MATCHED base (off: the offsets given to gkmhip_set_sequences).  With
+ * share[m] = c_m / (L - m), sum_t A_i(j)[t] = G(j, rows[i]).
+ *   share  HOST, d + 1 doubles (tests pass unit vectors to read single tallies);
+ *   coef   DEVICE, nrows doubles (scoring: dual_coef_i / sqnorm_i);
+ *   xscale DEVICE, col_end - col_begin doubles, or NULL for 1 (scoring: 1 / sqnorm_j);
+ *   out    DEVICE, the bases of the range; nothing else is written.
+ * rows: host array, strictly ascending.  Needs d < L.  Bit-identical for a query whatever the range it is in: the rows are
+ * cut into chunks by their number only, each chunk's sum is exact integer tallies folded in a fixed order, and the chunks
+ * are summed in order.  Work is enqueued on `stream`; last_kernel_ms / last_comparisons / last_kernel_name describe it. */
+int gkmhip_explain_block(gkmhip_ctx *ctx, const int *rows, int nrows, int col_begin, int col_end, const double *share,
+                         const double *coef, const double *xscale, double *out, void *stream);
+
 /* sqnorm[i] = sqrt(G(i,i)) for all uploaded sequences (device array of n doubles), computed
  * from the diagonal band only (~1 % of the work of the whole matrix).  Replaces
  * gkmkernel_kernelfunc_sqnorm_single, src/libgkm.c:723-759. */
