@@ -10,6 +10,8 @@
  *   gkm_normalize.hip      k_sqnorm, k_normalize, k_assemble_normalize: square roots of the diagonal, division, RBF
  *   gkm_copyout.hip        device matrix -> the caller's host rows: row blocks, staging pieces, the stream prober
  *   gkm_explain.hip        per-base importance of a trained model (k_explain, k_explain_reduce), gkmhip_explain_block
+ *   gkm_ism.hip            in-silico mutagenesis of a trained model (k_ism, k_ism_reduce, k_ism_self_base, k_ism_self),
+ *                          gkmhip_ism_block, gkmhip_ism_self_profiles
  */
 #ifndef GKM_INTERNAL_H
 #define GKM_INTERNAL_H
@@ -141,6 +143,10 @@ struct gkmhip_ctx {
     const char *last_kernel = "none";
     DevBuf<int> ex_rows;      /* gkmhip_explain_block: its row list and the partial rows of its support-vector chunks */
     DevBuf<double> ex_part;
+    DevBuf<int> ism_rows;     /* gkmhip_ism_block: its row list, the partial rows of its support-vector chunks and their */
+    DevBuf<double> ism_part;  /* per-tile G; gkmhip_ism_self_profiles: the queries' own profiles P_m(x, x) */
+    DevBuf<double> ism_gpart;
+    DevBuf<int64_t> ism_pself;
 };
 
 /* the pair of events the next Gram kernel is bracketed by (gkm_context.hip) */

@@ -117,6 +117,10 @@ def load():
     L.gkmhip_normalize_block.argtypes = (vp, vp, i32, i32, i32, vp, i64, vp, vp)
     L.gkmhip_explain_block.restype = i32
     L.gkmhip_explain_block.argtypes = (vp, vp, i32, i32, i32, vp, vp, vp, vp, vp)
+    L.gkmhip_ism_block.restype = i32
+    L.gkmhip_ism_block.argtypes = (vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp)
+    L.gkmhip_ism_self_profiles.restype = i32
+    L.gkmhip_ism_self_profiles.argtypes = (vp, i32, i32, vp, vp)
     L.gkmhip_self_norms.restype = i32
     L.gkmhip_self_norms.argtypes = (vp, vp, vp)
     L.gkmhip_normalize_rows_full.restype = i32
@@ -382,6 +386,25 @@ class GramContext:
         self._chk(self.lib.gkmhip_explain_block(self.handle, rows.ctypes.data, len(rows), int(col_begin), int(col_end),
                                                 share.ctypes.data, coef_ptr, xscale_ptr, out_ptr, stream),
                   "gkmhip_explain_block")
+
+    def ism_block(self, rows, col_begin, col_end, fold_u, fold_b, gcoef, coef_ptr, out_ptr, base_ptr=None, stream=0):
+        """In-silico mutagenesis, support-vector side, of the queries [col_begin, col_end) against the support vectors
+        `rows` into out_ptr (4 doubles per base of the range, columns A, C, G, T) and base_ptr (one double per query, or
+        None): fold_u, fold_b, gcoef = d + 1 host doubles each, coef_ptr = len(rows) device doubles
+        (include/gkm_hip.h gkmhip_ism_block)."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        fold = [np.ascontiguousarray(v, dtype=np.float64) for v in (fold_u, fold_b, gcoef)]
+        if any(len(v) != self.d + 1 for v in fold):
+            raise GkmError("ism_block: fold_u, fold_b and gcoef need d + 1 = %d values each" % (self.d + 1))
+        self._chk(self.lib.gkmhip_ism_block(self.handle, rows.ctypes.data, len(rows), int(col_begin), int(col_end),
+                                            fold[0].ctypes.data, fold[1].ctypes.data, fold[2].ctypes.data, coef_ptr,
+                                            out_ptr, base_ptr, stream), "gkmhip_ism_block")
+
+    def ism_self_profiles(self, col_begin, col_end, prof_ptr, stream=0):
+        """P_m(y, y) of every single-base mutant y of the queries [col_begin, col_end) into prof_ptr (int64, 4 (d + 1) per
+        base of the range; include/gkm_hip.h gkmhip_ism_self_profiles)."""
+        self._chk(self.lib.gkmhip_ism_self_profiles(self.handle, int(col_begin), int(col_end), prof_ptr, stream),
+                  "gkmhip_ism_self_profiles")
 
     def self_norms(self, sq_ptr, stream=0):
         self._chk(self.lib.gkmhip_self_norms(self.handle, sq_ptr, stream), "gkmhip_self_norms")

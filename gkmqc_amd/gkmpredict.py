@@ -11,11 +11,15 @@ The other half of a gkm-SVM next to the cross-validation of `gkmsvm.py` (the cou
     normalisation (gkmhip_normalize_block), and sums the decision values with k_decision (gkmsvm_decision_batch) --
     scikit-learn's `decision_function` of the trained SVC, bit for bit, for every block size;
   * `explain` splits each query's score over its bases (gkmhip_explain_block): per block the same upload
-    and self norms as `score`, then one launch that credits every matching l-mer pair to the query bases it matched on.
+    and self norms as `score`, then one launch that credits every matching l-mer pair to the query bases it matched on;
+  * `ism` scores every single-base substitution of each query (gkmhip_ism_block and
+    gkmhip_ism_self_profiles): per block the same upload and self norms, one launch that tallies how each l-mer pair's
+    mismatch count moves under a substitution, and one that counts every mutant's profile against itself.
 
     python -m gkmqc_amd.gkmpredict train [-t -L -k -d -M -H -G -C -e -u] pos.fa neg.fa model.txt
     python -m gkmqc_amd.gkmpredict predict query.fa model.txt out.txt
     python -m gkmqc_amd.gkmpredict explain [--block Qb] query.fa model.txt out.txt
+    python -m gkmqc_amd.gkmpredict ism [--block Qb] query.fa model.txt out.txt
 """
 import argparse
 import logging
@@ -398,6 +402,126 @@ def read_explanation(path):
     return names, values
 
 
+# ------------------------------------------------------------------ in-silico mutagenesis
+ISM_CHUNKS = 16           # the most partial rows gkmhip_ism_block keeps per base (3 doubles per chunk of support vectors)
+
+
+def check_ism(model):
+    """The models `ism` serves: every model `score` serves except the RBF types, whose score is not linear in G."""
+    if model.kernel_type in (3, 5):
+        raise ModelError("ism: RBF kernels (types 3 and 5) are not served (their score is not linear in the raw kernel)")
+
+
+def ism_coefficients(model):
+    """(fold_u, fold_b, c), d + 1 doubles each: c[m] = c_m for m = 0..d; with c_{d+1} = 0, fold_u[m] = c_{m+1} - c_m
+    (a matched base of a pair with m mismatches moves it to m + 1) and fold_b[m - 1] = c_{m-1} - c_m for m = 1..d + 1 (a
+    mismatched base set to the support vector's base moves it to m - 1).  c_m beyond d is taken as 0 whatever
+    dv.mismatch_weights returns there."""
+    c = dv.mismatch_weights(model.kernel_type, model.L, model.k)[:model.d + 1].copy()
+    ce = np.append(c, 0.0)
+    return ce[1:] - ce[:-1], ce[:-1] - ce[1:], c
+
+
+def default_ism_block(max_len, d, budget=BLOCK_BYTES):
+    """Queries per block: the launch's partial rows (up to 3 x ISM_CHUNKS doubles per base), the (T, 4) output, the
+    mutants' self profiles (4 (d + 1) int64 per base) and the finishing temporaries within `budget` bytes of device
+    memory."""
+    per_base = 8 * (3 * ISM_CHUNKS + 4 * (int(d) + 1) + 24)
+    return int(max(1, min(1 << 20, budget // (per_base * max(int(max_len), 64)))))
+
+
+def ism(model, fasta_or_sequences, device=0, block=None, on_block=None):
+    """In-silico mutagenesis of `model` for a FASTA file (or a list / FlatSequences of base codes) -> (names, [float64
+    array (T, 4) per query], columns A, C, G, T):
+
+        ism(x)[t, b] = score(y) - score(x),   y = x with base t set to b   (0.0 where b == x[t])
+
+    with score as `score` computes it: sum_s dual_coef_s G(y, s) / (sq_s sqrt(G(y, y))) - rho.  Every
+    model `score` serves except RBF (types 3 and 5), k = 0 included; every query length `score` accepts.
+    block: queries per device block (default_ism_block).  on_block(dict) (measurements): called after every block with
+    its size, k_ism's milliseconds (HIP events), its l-mer comparisons, the self-profile kernels' milliseconds and the
+    block's wall time."""
+    check_ism(model)
+    seqs, names = _as_queries(fasta_or_sequences)
+    check_queries(model, seqs)
+    return names, _ism_flat(model, seqs, device, block, on_block)
+
+
+def _ism_flat(model, seqs, device, block, on_block=None):
+    import torch
+    S, Q, d = model.n_sv, len(seqs), model.d
+    lens = np.diff(seqs.off)
+    qb_max = min(Q, int(block) if block else default_ism_block(int(lens.max()), d))
+    if qb_max < 1:
+        raise ModelError("block must be at least 1")
+    ctx = dv.cached_context(*model.kernel_params(), device=device)
+    fold_u, fold_b, c = ism_coefficients(model)
+    sv_codes = np.concatenate(model.seqs)
+    sv_off = np.zeros(S + 1, dtype=np.int64)
+    np.cumsum([len(s) for s in model.seqs], out=sv_off[1:])
+    rows = np.arange(S, dtype=np.int32)
+    dev = torch.device("cuda", device)
+    out = []
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        sq = torch.empty(S + qb_max, dtype=torch.float64, device=dev)
+        dual = torch.from_numpy(model.dual_coef()).to(dev)
+        most = max(int(seqs.off[min(Q, q0 + qb_max)] - seqs.off[q0]) for q0 in range(0, Q, qb_max))
+        D = torch.empty((most, 4), dtype=torch.float64, device=dev)
+        prof = torch.empty((most, 4, d + 1), dtype=torch.int64, device=dev)
+        base = torch.empty(qb_max, dtype=torch.float64, device=dev)
+        for q0 in range(0, Q, qb_max):
+            q1 = min(Q, q0 + qb_max)
+            qb = q1 - q0
+            t0 = time.perf_counter()
+            qoff = seqs.off[q0:q1 + 1]
+            nb = int(qoff[-1] - qoff[0])
+            union = dv.FlatSequences(np.concatenate((sv_codes, seqs.codes[qoff[0]:qoff[-1]])),
+                                     np.concatenate((sv_off, sv_off[-1] + (qoff[1:] - qoff[0]))))
+            ctx.set_sequences(union, stream)     # (complete on return)
+            ctx.self_norms(sq.data_ptr(), stream)
+            ctx.ism_self_profiles(S, S + qb, prof.data_ptr(), stream)
+            self_ms = ctx.last_kernel_ms() if on_block is not None else None
+            coef = dual / sq[:S]
+            ctx.ism_block(rows, S, S + qb, fold_u, fold_b, c, coef.data_ptr(), D.data_ptr(), base.data_ptr(), stream)
+            # G(y, y) = sum_m c_m P_m(y, y) in ascending m from 0.0, as the oracle forms it; then
+            # score(y) - score(x) = (base + D) / sqrt(G(y, y)) - base / sq_x
+            g = torch.zeros((nb, 4), dtype=torch.float64, device=dev)
+            for m in range(d + 1):
+                g.add_(prof[:nb, :, m].double().mul_(float(c[m])))
+            per = torch.from_numpy(np.diff(qoff)).to(dev)
+            bx = torch.repeat_interleave(base[:qb], per)
+            sx = torch.repeat_interleave(sq[S:S + qb], per)
+            res = (bx[:, None] + D[:nb]).div_(g.sqrt_()).sub_((bx / sx)[:, None])
+            host = res.cpu().numpy()
+            host[np.arange(nb), seqs.codes[qoff[0]:qoff[-1]]] = 0.0
+            out.extend(np.split(host, (qoff[1:-1] - qoff[0]).astype(np.int64)))
+            if on_block is not None:
+                on_block(dict(queries=qb, ism_kernel_ms=ctx.last_kernel_ms(), comparisons=ctx.last_comparisons(),
+                              kernel=ctx.last_kernel_name(), self_kernels_ms=self_ms,
+                              wall_ms=(time.perf_counter() - t0) * 1e3))
+    return out
+
+
+def write_ism(path, names, values):
+    """The `ism` output: one line per query, name<TAB>v(0,A),v(0,C),v(0,G),v(0,T),v(1,A),... (4T values, position-major)
+    with repr() floats (they read back to the same doubles)."""
+    with open(path, "w") as f:
+        for name, v in zip(names, values):
+            f.write("%s\t%s\n" % (name, ",".join(repr(float(e)) for e in np.asarray(v).reshape(-1))))
+
+
+def read_ism(path):
+    """-> (names, [float64 array (T, 4) per query]) from a file written by write_ism."""
+    names, values = [], []
+    with open(path) as f:
+        for line in f.read().split("\n")[:-1]:
+            name, vals = line.rsplit("\t", 1)
+            names.append(name)
+            values.append(np.array([float(e) for e in vals.split(",")], dtype=np.float64).reshape(-1, 4))
+    return names, values
+
+
 # ------------------------------------------------------------------ command line
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m gkmqc_amd.gkmpredict",
@@ -430,6 +554,13 @@ def build_parser():
     x.add_argument("query_fa")
     x.add_argument("model")
     x.add_argument("output")
+    z = sub.add_parser("ism", help="in-silico mutagenesis of the sequences of query.fa: name<TAB>4T values per line, "
+                                   "position-major, columns A, C, G, T")
+    z.add_argument("--device", type=int, default=0, help="GPU (default: 0)")
+    z.add_argument("--block", type=int, default=None, help="queries per device block (default: from device memory)")
+    z.add_argument("query_fa")
+    z.add_argument("model")
+    z.add_argument("output")
     return p
 
 
@@ -469,11 +600,15 @@ def main(argv=None):
             m = load(a.model)
             if a.cmd == "explain":
                 check_explainable(m)
+            elif a.cmd == "ism":
+                check_ism(m)
             seqs, names = _as_queries(a.query_fa)
             check_queries(m, seqs)
             tmp = a.output + ".tmp"
             if a.cmd == "explain":
                 write_explanation(tmp, names, _explain_flat(m, seqs, a.device, a.block))
+            elif a.cmd == "ism":
+                write_ism(tmp, names, _ism_flat(m, seqs, a.device, a.block))
             else:
                 scores = _score_flat(m, seqs, a.device, a.block, dv.KERNEL_AUTO, None)
                 with open(tmp, "w") as f:

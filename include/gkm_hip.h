@@ -120,6 +120,36 @@ int gkmhip_gram_block(gkmhip_ctx *ctx, const int *rows, int nrows, int col_begin
 int gkmhip_explain_block(gkmhip_ctx *ctx, const int *rows, int nrows, int col_begin, int col_end, const double *share,
                          const double *coef, const double *xscale, double *out, void *stream);
 
+/* In-silico mutagenesis, support-vector side: rows are support vectors, the columns [col_begin, col_end)
+ * queries.  For query j, each of its bases t and each base b (0..3 = A, C, G, T) other than x_j[t],
+ *   out[4 (off[j] - off[col_begin] + t) + b] = sum_i coef[i] sum_{m ascending} (fold_u[m] U_m[t] + fold_b[m-1] B_m[t][b]),
+ * the sum over the rows in list order, and 0.0 at b = x_j[t].  U_m[t] is the exact integer tally of w_j[p] w_i[q] over the
+ * l-mer pairs (query l-mer p, forward or reverse-complement l-mer q of row i) with m <= d mismatches whose base t - p is
+ * MATCHED; B_m[t][b] the same over the pairs with 1 <= m <= min(d + 1, L) mismatches whose base t - p is MISMATCHED with
+ * base b on the row's side.  With c_{d+1} = 0, fold_u[m] = c_{m+1} - c_m and fold_b[m-1] = c_{m-1} - c_m, out is
+ * sum_i coef[i] (G(y, rows[i]) - G(x_j, rows[i])) for the mutant y.  If base is not NULL,
+ * base[j - col_begin] = sum_i coef[i] sum_m gcoef[m] P_m(x_j, rows[i]) (= sum_i coef[i] G(x_j, rows[i]) with gcoef = c).
+ *   fold_u, gcoef HOST, d + 1 doubles (m = 0..d); fold_b HOST, d + 1 doubles (m = 1..d + 1; beyond m = L unused)
+ *                 (tests pass unit vectors to read single tallies);
+ *   coef          DEVICE, nrows doubles (scoring: dual_coef_i / sqnorm_i);
+ *   out           DEVICE, 4 doubles per base of the range; base DEVICE, col_end - col_begin doubles, or NULL.
+ * rows: host array, strictly ascending.  Any (L, d), any query length: query positions are tiled when a query's tallies
+ * do not fit in LDS.  Bit-identical for a query whatever the range it is in: the rows are cut into chunks by their number
+ * only and the queries into tiles by (L, d) only, each chunk's sum is exact integer tallies folded in a fixed order, and
+ * the chunks and tiles are summed in order.  Work is enqueued on `stream`; last_kernel_ms / last_comparisons /
+ * last_kernel_name describe k_ism. */
+int gkmhip_ism_block(gkmhip_ctx *ctx, const int *rows, int nrows, int col_begin, int col_end, const double *fold_u,
+                     const double *fold_b, const double *gcoef, const double *coef, double *out, double *base,
+                     void *stream);
+
+/* In-silico mutagenesis, self side: for query j of [col_begin, col_end), each base t and each base b (0..3),
+ *   prof[(4 (off[j] - off[col_begin] + t) + b) (d + 1) + m] = P_m(y, y), m = 0..d,
+ * the exact integer mismatch profile of y = x_j with base t set to b against itself (b = x_j[t]: P_m(x_j, x_j)), as
+ * gkmhip_self_norms counts it: forward l-mers of y against forward and reverse-complement l-mers of y.
+ *   prof DEVICE, 4 (d + 1) int64 per base of the range; nothing else is written.
+ * Work is enqueued on `stream`; last_kernel_ms / last_comparisons / last_kernel_name describe k_ism_self_base + k_ism_self. */
+int gkmhip_ism_self_profiles(gkmhip_ctx *ctx, int col_begin, int col_end, int64_t *prof, void *stream);
+
 /* sqnorm[i] = sqrt(G(i,i)) for all uploaded sequences (device array of n doubles), computed
  * from the diagonal band only (~1 % of the work of the whole matrix).  Replaces
  * gkmkernel_kernelfunc_sqnorm_single, src/libgkm.c:723-759. */
