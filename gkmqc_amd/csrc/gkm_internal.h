@@ -11,7 +11,8 @@
  *   gkm_copyout.hip        device matrix -> the caller's host rows: row blocks, staging pieces, the stream prober
  *   gkm_explain.hip        per-base importance of a trained model (k_explain, k_explain_reduce), gkmhip_explain_block
  *   gkm_ism.hip            in-silico mutagenesis of a trained model (k_ism, k_ism_reduce, k_ism_self_base, k_ism_self),
- *                          gkmhip_ism_block, gkmhip_ism_self_profiles
+ *                          gkmhip_ism_block, gkmhip_ism_self_profiles; hypothetical importance (k_ism_hyp,
+ *                          k_ism_hyp_reduce), gkmhip_hyp_block
  */
 #ifndef GKM_INTERNAL_H
 #define GKM_INTERNAL_H
@@ -144,7 +145,8 @@ struct gkmhip_ctx {
     DevBuf<int> ex_rows;      /* gkmhip_explain_block: its row list and the partial rows of its support-vector chunks */
     DevBuf<double> ex_part;
     DevBuf<int> ism_rows;     /* gkmhip_ism_block: its row list, the partial rows of its support-vector chunks and their */
-    DevBuf<double> ism_part;  /* per-tile G; gkmhip_ism_self_profiles: the queries' own profiles P_m(x, x) */
+    DevBuf<double> ism_part;  /* per-tile G (gkmhip_hyp_block: its row list and partial rows); gkmhip_ism_self_profiles: */
+                              /* the queries' own profiles P_m(x, x) */
     DevBuf<double> ism_gpart;
     DevBuf<int64_t> ism_pself;
 };

@@ -10,6 +10,11 @@
  *   Then dP_m(t, b) = U[m-1][t] - U[m][t] + B[m+1][t][b] - B[m][t][b], and with fold_u[m] = c_{m+1} - c_m and
  *   fold_b[m] = c_{m-1} - c_m (c_{d+1} = 0), dG_s(t, b) = sum_m fold_u[m] U[m][t] + sum_m fold_b[m] B[m][t][b].
  *
+ * Hypothetical importance is a second fold of the same tallies: a pair MISMATCHED at t against the
+ * support vector's base b is, in y = x with base t set to b, a pair with one mismatch fewer that is MATCHED at t, so
+ * explain's tally of y is H_y[m][t] = B[m + 1][t][b], and the raw hypothetical score of (t, b) is
+ * sum_s coef_s sum_{m=1..d+1} share[m-1] B[m][t][b] (b != x[t]) or sum_s coef_s sum_{m=0..d} share[m] U[m][t] (b = x[t]).
+ *
  * Kernels
  *   k_ism            one workgroup per (query, chunk of support vectors, tile of query positions): exact uint32 tallies
  *                    U and B of each support vector in LDS (ds_add_u32: order-free) and an exact uint64 profile of the
@@ -17,6 +22,9 @@
  *                    list order; one partial row per chunk
  *   k_ism_reduce     the partial rows summed in chunk order into the (T, 4) output (0.0 at the query's own base), and
  *                    base(x) = sum_s coef_s G(x, s) summed over tiles and chunks in order
+ *   k_ism<true>      (k_ism is k_ism<false>) the same enumeration, tallies, chunking and tiling with the hypothetical
+ *                    fold: 4 doubles per base, no profile
+ *   k_ism_hyp_reduce k_ism<true>'s partial rows summed in chunk order into the (T, 4) output, the query's own base included
  *   k_ism_self_base  P_m(x, x), exact uint64
  *   k_ism_self       P_m(y, y) of the three mutants at one position: P_m(x, x) plus the exact change of every pair in
  *                    which a changed l-mer takes part (about 4 L T comparisons per mutant)
@@ -65,17 +73,21 @@ struct IsmArgs {
     double gc[GKM_MAXD1];      /* profile m, m = 0..d */
     int L, d, mb, col_begin;
     int tile, stride, ntiles;  /* positions per tile, LDS row length (min(tile, longest query)), tiles of the launch */
-    double *part;              /* [chunk][3 x bases of the range] */
+    double *part;              /* [chunk][3 x bases of the range] (hypothetical mode: 4 x bases) */
     int64_t part_stride;
     double *gpart;             /* [chunk][query][tile] */
 };
 
 /* A pair (query l-mer at tile position pt, i.e. query position t0 + pt; support-vector l-mer v) with m <= mb mismatches
- * (mm: one bit 2j per mismatched base, j = L - 1 - i for base i of the l-mer).  Base i sits at tile position pt + i. */
+ * (mm: one bit 2j per mismatched base, j = L - 1 - i for base i of the l-mer).  Base i sits at tile position pt + i.
+ * HYP: the hypothetical mode, which keeps no profile. */
+template <bool HYP>
 __device__ __forceinline__ void ism_hit(uint32_t *U, uint32_t *B, unsigned long long *P, int stride, int tlen, int d,
                                         int L, int m, int pt, uint32_t mm, uint32_t u, uint32_t v, uint32_t w)
 {
-    if (m <= d && pt >= 0) atomicAdd(P + m, (unsigned long long)w); /* (the l-mers of the tile's own positions only) */
+    if constexpr (!HYP) {
+        if (m <= d && pt >= 0) atomicAdd(P + m, (unsigned long long)w); /* (the l-mers of the tile's own positions only) */
+    }
     const int top = pt + L - 1;
     for (int j = 0; j < L; j++) {
         const int tl = top - j;
@@ -108,6 +120,7 @@ __device__ __forceinline__ int ism_push(uint32_t *Q, int qn, bool hit, uint32_t 
     return qn + __popcll(bal);
 }
 
+template <bool HYP>
 __device__ __forceinline__ void ism_flush(const uint32_t *Q, int qn, int lane, uint32_t *U, uint32_t *B,
                                           unsigned long long *P, int stride, int tlen, int d, int L)
 {
@@ -115,15 +128,19 @@ __device__ __forceinline__ void ism_flush(const uint32_t *Q, int qn, int lane, u
     for (int k = lane; k < qn; k += 64) {
         const uint32_t a = Q[ISM_QWORDS * k], v = Q[ISM_QWORDS * k + 1], c = Q[ISM_QWORDS * k + 2];
         const uint32_t u = a & 0x00FFFFFFu, t = u ^ v;
-        ism_hit(U, B, P, stride, tlen, d, L, (int)(a >> 24), (int)(c & 0xFFFFu) - 16, (t | (t >> 1)) & 0x00555555u, u,
-                v, c >> 16);
+        ism_hit<HYP>(U, B, P, stride, tlen, d, L, (int)(a >> 24), (int)(c & 0xFFFFu) - 16, (t | (t >> 1)) & 0x00555555u,
+                     u, v, c >> 16);
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
 }
 
+/* HYP = false: in-silico mutagenesis; HYP = true: the hypothetical mode, part rows [slot 0, slot 1, slot 2, own] per base
+ * (slot s: the mutant to base (x[t] + 1 + s) mod 4).  The two differ in the fold and what they write only */
+template <bool HYP>
 __global__ __launch_bounds__(ISM_THREADS) void k_ism(const IsmArgs A)
 {
     extern __shared__ unsigned long long lds[];
+    constexpr int W = HYP ? 4 : 3; /* doubles per base of a partial row */
     unsigned long long *P = lds;                     /* [d + 1] */
     uint32_t *U = (uint32_t *)(lds + GKM_MAXD1);     /* [d + 1][stride] */
     uint32_t *B = U + (A.d + 1) * A.stride;          /* [mb][3][stride] */
@@ -155,9 +172,12 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism(const IsmArgs A)
     const int w0 = (tid >> 6) * 64;
     const int rn = __builtin_amdgcn_readfirstlane(min(ISM_R, max(0, (pl1 - pl0 - w0 + ISM_THREADS - 1) / ISM_THREADS)));
 
-    double acc[ISM_OWN][3];
+    double acc[ISM_OWN][W];
 #pragma unroll
-    for (int k = 0; k < ISM_OWN; k++) acc[k][0] = acc[k][1] = acc[k][2] = 0.0;
+    for (int k = 0; k < ISM_OWN; k++) {
+        acc[k][0] = acc[k][1] = acc[k][2] = 0.0;
+        if constexpr (HYP) acc[k][3] = 0.0;
+    }
     double gacc = 0.0;
     for (int e = tid; e < (d + 1 + 3 * mb) * stride; e += ISM_THREADS) U[e] = 0u;
     if (tid <= d) P[tid] = 0ull;
@@ -190,27 +210,50 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism(const IsmArgs A)
                     qn = ism_push(Q, qn, mf <= lim[r], u[r] | ((uint32_t)mf << 24), xf[t] & 0x00FFFFFFu,
                                   ptw | (wu[r] * (xf[t] >> 24)) << 16);
                     if (qn >= 64) {
-                        ism_flush(Q, qn, lane, U, B, P, stride, tlen, d, L);
+                        ism_flush<HYP>(Q, qn, lane, U, B, P, stride, tlen, d, L);
                         qn = 0;
                     }
                     qn = ism_push(Q, qn, mr <= lim[r], u[r] | ((uint32_t)mr << 24), xr[t] & 0x00FFFFFFu,
                                   ptw | (wu[r] * (xr[t] >> 24)) << 16);
                     if (qn >= 64) {
-                        ism_flush(Q, qn, lane, U, B, P, stride, tlen, d, L);
+                        ism_flush<HYP>(Q, qn, lane, U, B, P, stride, tlen, d, L);
                         qn = 0;
                     }
                 }
             }
         }
-        if (qn) ism_flush(Q, qn, lane, U, B, P, stride, tlen, d, L);
+        if (qn) ism_flush<HYP>(Q, qn, lane, U, B, P, stride, tlen, d, L);
         __syncthreads();
         /* fold in ascending m: a(t, b) = sum_m fu[m] U[m][t] + fb[m] B[m][t][b], then acc += coef_s a; each thread clears
-         * what it has read, so the next support vector starts from zero after one barrier */
+         * what it has read, so the next support vector starts from zero after one barrier.  Hypothetical mode (fu[m] =
+         * share[m], fb[m - 1] = share[m - 1]): the own column takes the U rows only, each mutant column its B rows only,
+         * in k_explain's expression shape */
         const double cs = A.coef[i];
 #pragma unroll
         for (int k = 0; k < ISM_OWN; k++) {
             const int tl = k * ISM_THREADS + tid;
-            if (tl < tlen) {
+            if constexpr (HYP) {
+                if (tl < tlen) {
+                    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+                    for (int m = 0; m <= d || m <= mb; m++) {
+                        if (m <= d) {
+                            a3 += A.fu[m] * (double)U[m * stride + tl];
+                            U[m * stride + tl] = 0u;
+                        }
+                        if (m >= 1 && m <= mb) {
+                            uint32_t *b = B + (m - 1) * 3 * stride + tl;
+                            a0 += A.fb[m - 1] * (double)b[0];
+                            a1 += A.fb[m - 1] * (double)b[stride];
+                            a2 += A.fb[m - 1] * (double)b[2 * stride];
+                            b[0] = b[stride] = b[2 * stride] = 0u;
+                        }
+                    }
+                    acc[k][0] += cs * a0;
+                    acc[k][1] += cs * a1;
+                    acc[k][2] += cs * a2;
+                    acc[k][3] += cs * a3;
+                }
+            } else if (tl < tlen) {
                 double a0 = 0.0, a1 = 0.0, a2 = 0.0;
                 for (int m = 0; m <= d || m <= mb; m++) {
                     if (m <= d) {
@@ -233,27 +276,32 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism(const IsmArgs A)
                 acc[k][2] += cs * a2;
             }
         }
-        if (tid == 0) {
-            double g = 0.0;
-            for (int m = 0; m <= d; m++) {
-                g += A.gc[m] * (double)P[m];
-                P[m] = 0ull;
+        if constexpr (!HYP) {
+            if (tid == 0) {
+                double g = 0.0;
+                for (int m = 0; m <= d; m++) {
+                    g += A.gc[m] * (double)P[m];
+                    P[m] = 0ull;
+                }
+                gacc += cs * g;
             }
-            gacc += cs * g;
         }
         __syncthreads();
     }
-    double *row = A.part + (int64_t)c * A.part_stride + 3 * (A.off[j] - A.off[A.col_begin] + t0);
+    double *row = A.part + (int64_t)c * A.part_stride + W * (A.off[j] - A.off[A.col_begin] + t0);
 #pragma unroll
     for (int k = 0; k < ISM_OWN; k++) {
         const int tl = k * ISM_THREADS + tid;
         if (tl < tlen) {
-            row[3 * tl] = acc[k][0];
-            row[3 * tl + 1] = acc[k][1];
-            row[3 * tl + 2] = acc[k][2];
+            row[W * tl] = acc[k][0];
+            row[W * tl + 1] = acc[k][1];
+            row[W * tl + 2] = acc[k][2];
+            if constexpr (HYP) row[W * tl + 3] = acc[k][3];
         }
     }
-    if (tid == 0) A.gpart[((int64_t)c * gridDim.x + jl) * A.ntiles + z] = gacc;
+    if constexpr (!HYP) {
+        if (tid == 0) A.gpart[((int64_t)c * gridDim.x + jl) * A.ntiles + z] = gacc;
+    }
 }
 
 /* out[4 (off[j] - off[col_begin] + t) + b] = the partial rows of (t, b) summed in chunk order, 0.0 at b = x[t];
@@ -285,6 +333,29 @@ __global__ void k_ism_reduce(const double *__restrict__ part, int64_t part_strid
         for (int z = 0; z < nt; z++)
             for (int c = 0; c < nchunks; c++) v += gpart[((int64_t)c * gridDim.x + jl) * ntiles + z];
         base[jl] = v;
+    }
+}
+
+/* out[4 (off[j] - off[col_begin] + t) + b] = k_ism<true>'s partial rows of (t, b) summed in chunk order, the query's own
+ * base included */
+__global__ void k_ism_hyp_reduce(const double *__restrict__ part, int64_t part_stride, int nchunks,
+                                 const int *__restrict__ len, const int64_t *__restrict__ off,
+                                 const uint8_t *__restrict__ codes, int col_begin, double *__restrict__ out)
+{
+    const int jl = blockIdx.x, j = col_begin + jl;
+    const int T = len[j];
+    const int64_t b0 = off[j] - off[col_begin];
+    const uint8_t *x = codes + off[j];
+    for (int t = threadIdx.x; t < T; t += blockDim.x) {
+        const int xb = x[t] & 3;
+        double *o = out + 4 * (b0 + t);
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+            const int64_t e = 4 * (b0 + t) + s;
+            double v = part[e];
+            for (int c = 1; c < nchunks; c++) v += part[(int64_t)c * part_stride + e];
+            o[(xb + 1 + s) & 3] = v; /* (s = 3: the own base) */
+        }
     }
 }
 
@@ -453,11 +524,11 @@ extern "C" int gkmhip_ism_block(gkmhip_ctx *ctx, const int *rows, int nrows, int
     A.part = ctx->ism_part.p; A.part_stride = 3 * bases; A.gpart = ctx->ism_gpart.p;
     /* at most 6 248 + 4 x (13 + 3 x 12) x 804 = 163 832 bytes (L = 12, d = 12); 44 648 at gkmQC's shape */
     const size_t lds = ISM_LDS_FIXED + (size_t)(d + 1 + 3 * mb) * (size_t)stride * sizeof(uint32_t);
-    HIPCHK(hipFuncSetAttribute((const void *)k_ism, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(hipFuncSetAttribute((const void *)k_ism<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipEvent_t e0, e1;
     if (gkm_launch_events(ctx, &e0, &e1)) return 4;
     HIPCHK(hipEventRecord(e0, stream));
-    hipLaunchKernelGGL(k_ism, dim3((unsigned)ncols, (unsigned)nchunks, (unsigned)ntiles), dim3(ISM_THREADS), lds, stream, A);
+    hipLaunchKernelGGL(k_ism<false>, dim3((unsigned)ncols, (unsigned)nchunks, (unsigned)ntiles), dim3(ISM_THREADS), lds, stream, A);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e1, stream));
     hipLaunchKernelGGL(k_ism_reduce, dim3((unsigned)ncols), dim3(256), 0, stream, (const double *)ctx->ism_part.p,
@@ -472,6 +543,76 @@ extern "C" int gkmhip_ism_block(gkmhip_ctx *ctx, const int *rows, int nrows, int
         fprintf(stderr, "gkmhip: ism %d rows x columns [%d, %d) -> k_ism (%d chunks of %d rows, %d tiles of %d positions, "
                         "%zu bytes of LDS, %.3g comparisons)\n", nrows, col_begin, col_end, nchunks, chunk, ntiles, tile,
                 lds, comparisons);
+    return 0;
+}
+
+extern "C" int gkmhip_hyp_block(gkmhip_ctx *ctx, const int *rows, int nrows, int col_begin, int col_end,
+                                const double *share, const double *coef, double *out, void *stream_)
+{
+    if (!ctx || !rows || nrows <= 0 || !share || !coef || !out) return set_err_msg("gkmhip_hyp_block: bad arguments", 2);
+    if (int rc = check_range(ctx, col_begin, col_end, "gkmhip_hyp_block")) return rc;
+    const int L = ctx->L, d = ctx->d, n = ctx->n, mb = ism_mb(L, d);
+    if (d >= L) return set_err_msg("gkmhip_hyp_block: needs d < L (a pair with m = L has no matched base to credit)", 2);
+    const int tile = ism_tile(L, d);
+    double row_lmers = 0;
+    for (int i = 0; i < nrows; i++) {
+        if (rows[i] < 0 || rows[i] >= n || (i > 0 && rows[i] <= rows[i - 1]))
+            return set_err_msg("rows must be strictly ascending sequence indices", 2);
+        row_lmers += (double)(ctx->h_len[(size_t)rows[i]] - L + 1);
+    }
+    int tmax = 0;
+    int64_t bases = 0;
+    double tile_lmers = 0; /* as gkmhip_ism_block */
+    for (int j = col_begin; j < col_end; j++) {
+        const int T = ctx->h_len[(size_t)j], nx = T - L + 1;
+        tmax = std::max(tmax, T);
+        bases += T;
+        for (int t0 = 0; t0 < T; t0 += tile) tile_lmers += std::min(nx, t0 + tile) - std::max(0, t0 - L + 1);
+    }
+    const double comparisons = 2.0 * row_lmers * tile_lmers;
+    const int ntiles = (tmax + tile - 1) / tile, stride = std::min(tile, tmax);
+    const int ncols = col_end - col_begin;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIPCHK(hipSetDevice(ctx->device));
+    (void)hipGetLastError(); /* the launch checks below must see this call's errors only */
+    if (ensure_lmers(ctx, stream, true)) return 4;
+    const int chunk = ism_chunk(nrows), nchunks = (nrows + chunk - 1) / chunk;
+    if (ctx->ism_rows.ensure((size_t)nrows) || ctx->ism_part.ensure((size_t)nchunks * 4 * (size_t)bases, true)) return 4;
+    HIPCHK(hipMemcpyAsync(ctx->ism_rows.p, rows, (size_t)nrows * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream)); /* `rows` is the caller's: see gkmhip_set_sequences */
+    IsmArgs A;
+    A.rows = ctx->ism_rows.p; A.nrows = nrows; A.chunk = chunk;
+    A.len = ctx->len.p; A.off = ctx->off.p; A.lmoff = ctx->lmoff.p;
+    A.lmf = ctx->lmf.p; A.lmr = ctx->lmf.p + ctx->lm_stride;
+    A.coef = coef;
+    for (int m = 0; m < GKM_MAXD1; m++) {
+        A.fu[m] = m <= d ? share[m] : 0.0;      /* U row m: share[m] */
+        A.fb[m] = m < mb ? share[m] : 0.0;      /* B row m + 1: share[m] */
+        A.gc[m] = 0.0;
+    }
+    A.L = L; A.d = d; A.mb = mb; A.col_begin = col_begin;
+    A.tile = tile; A.stride = stride; A.ntiles = ntiles;
+    A.part = ctx->ism_part.p; A.part_stride = 4 * bases; A.gpart = nullptr;
+    const size_t lds = ISM_LDS_FIXED + (size_t)(d + 1 + 3 * mb) * (size_t)stride * sizeof(uint32_t); /* as k_ism's */
+    HIPCHK(hipFuncSetAttribute((const void *)k_ism<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipEvent_t e0, e1;
+    if (gkm_launch_events(ctx, &e0, &e1)) return 4;
+    HIPCHK(hipEventRecord(e0, stream));
+    hipLaunchKernelGGL(k_ism<true>, dim3((unsigned)ncols, (unsigned)nchunks, (unsigned)ntiles), dim3(ISM_THREADS), lds, stream,
+                       A);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e1, stream));
+    hipLaunchKernelGGL(k_ism_hyp_reduce, dim3((unsigned)ncols), dim3(256), 0, stream, (const double *)ctx->ism_part.p,
+                       (int64_t)4 * bases, nchunks, (const int *)ctx->len.p, (const int64_t *)ctx->off.p,
+                       (const uint8_t *)ctx->codes.p, col_begin, out);
+    HIPCHK(hipGetLastError());
+    ctx->ev_valid = true;
+    ctx->last_comparisons = comparisons;
+    ctx->last_kernel = "k_ism<true>";
+    if (getenv("GKM_TRACE"))
+        fprintf(stderr, "gkmhip: hypothetical %d rows x columns [%d, %d) -> k_ism<true> (%d chunks of %d rows, %d tiles of %d "
+                        "positions, %zu bytes of LDS, %.3g comparisons)\n", nrows, col_begin, col_end, nchunks, chunk,
+                ntiles, tile, lds, comparisons);
     return 0;
 }
 

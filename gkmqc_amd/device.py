@@ -119,6 +119,8 @@ def load():
     L.gkmhip_explain_block.argtypes = (vp, vp, i32, i32, i32, vp, vp, vp, vp, vp)
     L.gkmhip_ism_block.restype = i32
     L.gkmhip_ism_block.argtypes = (vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp)
+    L.gkmhip_hyp_block.restype = i32
+    L.gkmhip_hyp_block.argtypes = (vp, vp, i32, i32, i32, vp, vp, vp, vp)
     L.gkmhip_ism_self_profiles.restype = i32
     L.gkmhip_ism_self_profiles.argtypes = (vp, i32, i32, vp, vp)
     L.gkmhip_self_norms.restype = i32
@@ -399,6 +401,17 @@ class GramContext:
         self._chk(self.lib.gkmhip_ism_block(self.handle, rows.ctypes.data, len(rows), int(col_begin), int(col_end),
                                             fold[0].ctypes.data, fold[1].ctypes.data, fold[2].ctypes.data, coef_ptr,
                                             out_ptr, base_ptr, stream), "gkmhip_ism_block")
+
+    def hyp_block(self, rows, col_begin, col_end, share, coef_ptr, out_ptr, stream=0):
+        """Raw hypothetical importance of the queries [col_begin, col_end) against the support vectors `rows` into
+        out_ptr (4 doubles per base of the range, columns A, C, G, T): share = d + 1 host doubles, coef_ptr = len(rows)
+        device doubles (include/gkm_hip.h gkmhip_hyp_block)."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        share = np.ascontiguousarray(share, dtype=np.float64)
+        if len(share) != self.d + 1:
+            raise GkmError("hyp_block: share needs d + 1 = %d values" % (self.d + 1))
+        self._chk(self.lib.gkmhip_hyp_block(self.handle, rows.ctypes.data, len(rows), int(col_begin), int(col_end),
+                                            share.ctypes.data, coef_ptr, out_ptr, stream), "gkmhip_hyp_block")
 
     def ism_self_profiles(self, col_begin, col_end, prof_ptr, stream=0):
         """P_m(y, y) of every single-base mutant y of the queries [col_begin, col_end) into prof_ptr (int64, 4 (d + 1) per

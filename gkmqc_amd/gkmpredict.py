@@ -14,12 +14,16 @@ The other half of a gkm-SVM next to the cross-validation of `gkmsvm.py` (the cou
     and self norms as `score`, then one launch that credits every matching l-mer pair to the query bases it matched on;
   * `ism` scores every single-base substitution of each query (gkmhip_ism_block and
     gkmhip_ism_self_profiles): per block the same upload and self norms, one launch that tallies how each l-mer pair's
-    mismatch count moves under a substitution, and one that counts every mutant's profile against itself.
+    mismatch count moves under a substitution, and one that counts every mutant's profile against itself;
+  * `hypothetical` gives, for every position and each of the four bases, the importance that base would get there
+    (gkmhip_hyp_block): ism's upload, self norms, mutant self profiles and tallies, folded the way
+    `explain` folds its own.
 
     python -m gkmqc_amd.gkmpredict train [-t -L -k -d -M -H -G -C -e -u] pos.fa neg.fa model.txt
     python -m gkmqc_amd.gkmpredict predict query.fa model.txt out.txt
     python -m gkmqc_amd.gkmpredict explain [--block Qb] query.fa model.txt out.txt
     python -m gkmqc_amd.gkmpredict ism [--block Qb] query.fa model.txt out.txt
+    python -m gkmqc_amd.gkmpredict hypothetical [--block Qb] query.fa model.txt out.txt
 """
 import argparse
 import logging
@@ -303,13 +307,13 @@ def _score_flat(model, seqs, device, block, kernel, on_block):
 EXPLAIN_CHUNKS = 16       # the most partial rows gkmhip_explain_block keeps per base (one per chunk of support vectors)
 
 
-def check_explainable(model):
-    """The models `explain` serves: not the RBF types (exp() breaks completeness) and not k = 0 (d = L is allowed there,
-    and a pair with L mismatches has no matched base to credit)."""
+def check_explainable(model, what="explain"):
+    """The models `explain` (and `hypothetical`) serves: not the RBF types (exp() breaks completeness) and not k = 0
+    (d = L is allowed there, and a pair with L mismatches has no matched base to credit).  what: the error's prefix."""
     if model.kernel_type in (3, 5):
-        raise ModelError("explain: RBF kernels (types 3 and 5) have no per-base decomposition")
+        raise ModelError("%s: RBF kernels (types 3 and 5) have no per-base decomposition" % what)
     if model.k == 0:
-        raise ModelError("explain: models with k = 0 have no per-base decomposition (a pair may match on no base)")
+        raise ModelError("%s: models with k = 0 have no per-base decomposition (a pair may match on no base)" % what)
 
 
 def explain_shares(model):
@@ -504,8 +508,8 @@ def _ism_flat(model, seqs, device, block, on_block=None):
 
 
 def write_ism(path, names, values):
-    """The `ism` output: one line per query, name<TAB>v(0,A),v(0,C),v(0,G),v(0,T),v(1,A),... (4T values, position-major)
-    with repr() floats (they read back to the same doubles)."""
+    """The `ism` (and `hypothetical`) output: one line per query, name<TAB>v(0,A),v(0,C),v(0,G),v(0,T),v(1,A),... (4T
+    values, position-major) with repr() floats (they read back to the same doubles)."""
     with open(path, "w") as f:
         for name, v in zip(names, values):
             f.write("%s\t%s\n" % (name, ",".join(repr(float(e)) for e in np.asarray(v).reshape(-1))))
@@ -520,6 +524,88 @@ def read_ism(path):
             names.append(name)
             values.append(np.array([float(e) for e in vals.split(",")], dtype=np.float64).reshape(-1, 4))
     return names, values
+
+
+# ------------------------------------------------------------------ hypothetical importance
+def default_hyp_block(max_len, d, budget=BLOCK_BYTES):
+    """Queries per block: the launch's partial rows (up to 4 x ISM_CHUNKS doubles per base), the raw (T, 4) values, the
+    mutants' self profiles (4 (d + 1) int64 per base) and the finishing temporaries within `budget` bytes of device
+    memory."""
+    per_base = 8 * (4 * ISM_CHUNKS + 4 * (int(d) + 1) + 28)
+    return int(max(1, min(1 << 20, budget // (per_base * max(int(max_len), 64)))))
+
+
+def hypothetical(model, fasta_or_sequences, device=0, block=None, on_block=None):
+    """Hypothetical importance of `model` for a FASTA file (or a list / FlatSequences of base codes) -> (names, [float64
+    array (T, 4) per query], columns A, C, G, T):
+
+        hyp(x)[t, b] = E(y)[t],   y = x with base t set to b   (so hyp(x)[t, x[t]] = E(x)[t])
+
+    with E the per-base importance `explain` computes, y's own norm sqrt(G(y, y)) included.  Times the
+    one-hot of x it is explain(x), bit for bit; each mutant column is explain of that mutant at t, bit for bit.  The
+    models `explain` serves (no RBF, no k = 0); every query length `score` accepts.  block: queries per device block
+    (default_hyp_block).  on_block(dict) (measurements): called after every block with its size, k_ism<true>'s
+    milliseconds (HIP events), its l-mer comparisons, the self-profile kernels' milliseconds and the block's wall time."""
+    check_explainable(model, "hypothetical")
+    seqs, names = _as_queries(fasta_or_sequences)
+    check_queries(model, seqs)
+    return names, _hyp_flat(model, seqs, device, block, on_block)
+
+
+def _hyp_flat(model, seqs, device, block, on_block=None):
+    import torch
+    S, Q, d = model.n_sv, len(seqs), model.d
+    lens = np.diff(seqs.off)
+    qb_max = min(Q, int(block) if block else default_hyp_block(int(lens.max()), d))
+    if qb_max < 1:
+        raise ModelError("block must be at least 1")
+    ctx = dv.cached_context(*model.kernel_params(), device=device)
+    share = explain_shares(model)
+    c = dv.mismatch_weights(model.kernel_type, model.L, model.k)[:d + 1]
+    sv_codes = np.concatenate(model.seqs)
+    sv_off = np.zeros(S + 1, dtype=np.int64)
+    np.cumsum([len(s) for s in model.seqs], out=sv_off[1:])
+    rows = np.arange(S, dtype=np.int32)
+    dev = torch.device("cuda", device)
+    out = []
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        sq = torch.empty(S + qb_max, dtype=torch.float64, device=dev)
+        dual = torch.from_numpy(model.dual_coef()).to(dev)
+        most = max(int(seqs.off[min(Q, q0 + qb_max)] - seqs.off[q0]) for q0 in range(0, Q, qb_max))
+        R = torch.empty((most, 4), dtype=torch.float64, device=dev)
+        prof = torch.empty((most, 4, d + 1), dtype=torch.int64, device=dev)
+        for q0 in range(0, Q, qb_max):
+            q1 = min(Q, q0 + qb_max)
+            qb = q1 - q0
+            t0 = time.perf_counter()
+            qoff = seqs.off[q0:q1 + 1]
+            nb = int(qoff[-1] - qoff[0])
+            union = dv.FlatSequences(np.concatenate((sv_codes, seqs.codes[qoff[0]:qoff[-1]])),
+                                     np.concatenate((sv_off, sv_off[-1] + (qoff[1:] - qoff[0]))))
+            ctx.set_sequences(union, stream)     # (complete on return)
+            ctx.self_norms(sq.data_ptr(), stream)
+            ctx.ism_self_profiles(S, S + qb, prof.data_ptr(), stream)
+            self_ms = ctx.last_kernel_ms() if on_block is not None else None
+            coef = dual / sq[:S]
+            xscale = 1.0 / sq[S:S + qb]
+            ctx.hyp_block(rows, S, S + qb, share, coef.data_ptr(), R.data_ptr(), stream)
+            # the mutant columns times 1 / sqrt(G(y, y)), G(y, y) = sum_m c_m P_m(y, y) in ascending m from 0.0 as _ism_flat
+            # forms it; the own column times explain's xscale
+            g = torch.zeros((nb, 4), dtype=torch.float64, device=dev)
+            for m in range(d + 1):
+                g.add_(prof[:nb, :, m].double().mul_(float(c[m])))
+            scale = 1.0 / g.sqrt_()
+            own = torch.from_numpy(seqs.codes[qoff[0]:qoff[-1]].astype(np.int64)).to(dev)
+            per = torch.from_numpy(np.diff(qoff)).to(dev)
+            scale.scatter_(1, own[:, None], torch.repeat_interleave(xscale, per)[:, None])
+            host = (R[:nb] * scale).cpu().numpy()
+            out.extend(np.split(host, (qoff[1:-1] - qoff[0]).astype(np.int64)))
+            if on_block is not None:
+                on_block(dict(queries=qb, hyp_kernel_ms=ctx.last_kernel_ms(), comparisons=ctx.last_comparisons(),
+                              kernel=ctx.last_kernel_name(), self_kernels_ms=self_ms,
+                              wall_ms=(time.perf_counter() - t0) * 1e3))
+    return out
 
 
 # ------------------------------------------------------------------ command line
@@ -561,6 +647,13 @@ def build_parser():
     z.add_argument("query_fa")
     z.add_argument("model")
     z.add_argument("output")
+    h = sub.add_parser("hypothetical", help="hypothetical importance of the sequences of query.fa: name<TAB>4T values per "
+                                            "line, position-major, columns A, C, G, T (the ism format)")
+    h.add_argument("--device", type=int, default=0, help="GPU (default: 0)")
+    h.add_argument("--block", type=int, default=None, help="queries per device block (default: from device memory)")
+    h.add_argument("query_fa")
+    h.add_argument("model")
+    h.add_argument("output")
     return p
 
 
@@ -602,6 +695,8 @@ def main(argv=None):
                 check_explainable(m)
             elif a.cmd == "ism":
                 check_ism(m)
+            elif a.cmd == "hypothetical":
+                check_explainable(m, "hypothetical")
             seqs, names = _as_queries(a.query_fa)
             check_queries(m, seqs)
             tmp = a.output + ".tmp"
@@ -609,6 +704,8 @@ def main(argv=None):
                 write_explanation(tmp, names, _explain_flat(m, seqs, a.device, a.block))
             elif a.cmd == "ism":
                 write_ism(tmp, names, _ism_flat(m, seqs, a.device, a.block))
+            elif a.cmd == "hypothetical":
+                write_ism(tmp, names, _hyp_flat(m, seqs, a.device, a.block))
             else:
                 scores = _score_flat(m, seqs, a.device, a.block, dv.KERNEL_AUTO, None)
                 with open(tmp, "w") as f:

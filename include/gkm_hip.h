@@ -142,6 +142,21 @@ int gkmhip_ism_block(gkmhip_ctx *ctx, const int *rows, int nrows, int col_begin,
                      const double *fold_b, const double *gcoef, const double *coef, double *out, double *base,
                      void *stream);
 
+/* Hypothetical importance, raw: rows are support vectors, the columns [col_begin, col_end) queries.  For
+ * query j, each of its bases t and each base b (0..3 = A, C, G, T),
+ *   out[4 (off[j] - off[col_begin] + t) + b] = sum_i coef[i] sum_{m=1..d+1} share[m-1] B_m[t][b]   (b != x_j[t])
+ *                                            = sum_i coef[i] sum_{m=0..d}   share[m]   U_m[t]      (b == x_j[t])
+ * the sums over the rows in list order and over m in ascending order from 0.0, with U and B the tallies of
+ * gkmhip_ism_block.  B_{m+1}[t][b] is gkmhip_explain_block's tally H_m[t] of the mutant y = x_j with base t set to b, so
+ * with share[m] = c_m / (L - m) the value at b times 1 / sqrt(G(y, y)) is explain's value of y at t, bit for bit.
+ *   share HOST, d + 1 doubles (tests pass unit vectors to read single tallies);
+ *   coef  DEVICE, nrows doubles (scoring: dual_coef_i / sqnorm_i);
+ *   out   DEVICE, 4 doubles per base of the range; nothing else is written.
+ * rows: host array, strictly ascending.  Needs d < L.  Chunking, tiling and bit-identity as gkmhip_ism_block.  Work is
+ * enqueued on `stream`; last_kernel_ms / last_comparisons / last_kernel_name describe k_ism_hyp. */
+int gkmhip_hyp_block(gkmhip_ctx *ctx, const int *rows, int nrows, int col_begin, int col_end, const double *share,
+                     const double *coef, double *out, void *stream);
+
 /* In-silico mutagenesis, self side: for query j of [col_begin, col_end), each base t and each base b (0..3),
  *   prof[(4 (off[j] - off[col_begin] + t) + b) (d + 1) + m] = P_m(y, y), m = 0..d,
  * the exact integer mismatch profile of y = x_j with base t set to b against itself (b = x_j[t]: P_m(x_j, x_j)), as
