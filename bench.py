@@ -6,22 +6,31 @@ already resident in HBM: build the per-call row tables, run the Gram kernel for 
 all-gather the row slabs over RCCL (N > 1), normalise the assembled matrix (division by the self
 norms, unit diagonal) on every rank.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload c2|peaks|c3|c5] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--workload c2|peaks|c3|c5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-N > 1 (`--assembly auto`, the default) measures BOTH multi-GPU drivers, each in fresh processes with a timeout:
+A plain run does only what its headline figure needs: set up, warm up, time the steps, write --dump-outputs, print
+the line.  On one GPU the line's `roofline` is read off the timed steps' own launches and costs no run of its own.
+--full adds everything else the benchmark measures or checks, after the timed steps: the parity gate, the roofline
+of N > 1 (extra kernel launches, one probed step), the side workloads (`also`: peaks, c5), `end_to_end`, the
+reference's CPU path (`cpu_baseline`, `vs_baseline`) and, for N > 1, the torch.distributed cross-check.
+--no-also, --no-end-to-end and --no-cpu-baseline leave single parts of it out.
+
+N > 1 (`--assembly auto`, the default) measures the multi-GPU drivers, each in fresh processes with a timeout:
   primary      the product's own entry behind the C ABI, gkmhip_gram_allgather (ONE process, one host thread per
                device, RCCL all-gather of the packed row slabs) -- run as a child `--assembly cabi` of rank 0 before
                any rank has touched a GPU;
   cross-check  one process per GPU, torch.distributed (backend nccl = RCCL) all_gather_into_tensor: the ranks the
-               launcher started (or, without a launcher, N ranks this script starts itself) -> `also.torch_dist`.
+               launcher started (or, with --full and without a launcher, N ranks this script starts itself)
+               -> `also.torch_dist`.
 If the primary fails, times out or fails its parity check the line says so (`cabi_error`) and carries the torch
-numbers instead.  `--assembly torch|cabi` runs one of them alone.
+numbers instead (without a launcher the torch ranks are then started in a plain run too).  `--assembly torch|cabi`
+runs one of them alone.
 
-PARITY GATE: after the timed region the matrix the last timed step produced is copied to the host and the SHA-256 of
-its strict lower triangle (the cells the reference writes, src/gkmkern_pylib.c:83,218-221) is compared with the digest
-of the reference's own matrix (tests/golden/<workload>_full_digest.npz) -- on every rank's / device's copy for N > 1.
-A mismatch sets `value` aside (`parity_failed`, exit code 3).
+PARITY GATE (--full): after the timed region the matrix the last timed step produced is copied to the host and the
+SHA-256 of its strict lower triangle (the cells the reference writes, src/gkmkern_pylib.c:83,218-221) is compared with
+the digest of the reference's own matrix (tests/golden/<workload>_full_digest.npz) -- on every rank's / device's copy
+for N > 1.  A mismatch sets `value` aside (`parity_failed`, exit code 3).
 
 --dump-outputs DIR: after the timed steps, rank 0 writes a fixed, seeded sample of that same matrix (values and their
 coordinates, about 32 MiB) to DIR/*.npy (dump_outputs()), so that two builds can be compared output for output.
@@ -489,10 +498,14 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-sample", type=int, default=None,
                     help="pos (=neg) sequences of the CPU baseline sample; default: the WHOLE workload for the headline "
                          "(c2: 5 000 + 5 000, ~90 s on 16 cores), 2 000 + 2 000 otherwise")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline figure does not need: the "
+                         "parity gate, the N > 1 roofline, the side workloads, end_to_end, the CPU baseline and, for "
+                         "N > 1 without a launcher, the torch.distributed cross-check")
     ap.add_argument("--no-also", action="store_true",
-                    help="skip the short side measurements of gkmQC's own shape (peaks) and config 5 in the headline line")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true")
+                    help="--full: skip the short side measurements of gkmQC's own shape (peaks) and config 5 in the headline line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-end-to-end", action="store_true", help="--full: skip the end_to_end walls")
     ap.add_argument("--check", action="store_true", help="compare the assembled matrix with a 1-GPU run (debug)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write a fixed sample of the matrix the last one produced to DIR/*.npy")
@@ -720,13 +733,18 @@ def merge_assemblies(cabi_line, cabi_err, torch_line, torch_err, torch_rc=0):
 
 def run_auto(args, argv):
     """N > 1, --assembly auto: the product's one-process entry first (child of rank 0, while no rank has touched a
-    GPU), then the torch.distributed ranks; one merged line."""
+    GPU), then the torch.distributed ranks; one merged line.  Without a launcher a plain run starts those ranks only
+    when the child gave no line to print; under a launcher they were started for it and run either way."""
     torch_argv = _strip_flag(argv, "--assembly") + ["--assembly", "torch"]
     targs = parse_args(torch_argv)
     if "WORLD_SIZE" not in os.environ:
         # no launcher: this process orchestrates and never touches a GPU
         cabi_line, cabi_err = run_cabi_child(args, argv)
         if _cabi_counts(cabi_line, cabi_err):     # --dump-outputs: the child wrote the line's matrix
+            if not args.full:                     # a plain run: the cross-check is part of --full
+                cabi_line["assembly"] = "cabi: gkmhip_gram_allgather (one process, one host thread per device)"
+                print(json.dumps(cabi_line), flush=True)
+                return 0
             torch_argv = _strip_flag(torch_argv, "--dump-outputs")
         captured = []
         rc = launch_ranks(targs, torch_argv, capture=captured)
@@ -1012,23 +1030,30 @@ def run_rank(args, emit=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # PARITY GATE: the matrix the last timed step left behind -- every device's copy (cabi), this rank's copy (torch)
-    if cabi:
-        parity_mine = [parity_of_device_matrix(args, K) for K in Ks]
-    else:
-        parity_mine = [parity_of_device_matrix(args, full)]
-    if dist_on:
-        gathered_par = [None] * world
-        dist.all_gather_object(gathered_par, parity_mine[0])
-        parity_mine = gathered_par
-    parity = merge_parity(parity_mine)
+    # PARITY GATE (--full): the matrix the last timed step left behind -- every device's copy (cabi), this rank's copy
+    # (torch)
+    parity = None
+    if args.full:
+        if cabi:
+            parity_mine = [parity_of_device_matrix(args, K) for K in Ks]
+        else:
+            parity_mine = [parity_of_device_matrix(args, full)]
+        if dist_on:
+            gathered_par = [None] * world
+            dist.all_gather_object(gathered_par, parity_mine[0])
+            parity_mine = gathered_par
+        parity = merge_parity(parity_mine)
     dumped = dump_outputs(full, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
-    # dominant kernel: extra launches bracketed by HIP events on the launch stream (recorded inside
-    # gkmhip_gram_rows), outside the wall-clock region
+    # dominant kernel: on one GPU the timed steps' own launches; otherwise (--full) extra launches bracketed by HIP
+    # events on the launch stream (recorded inside gkmhip_gram_rows), outside the wall-clock region
+    kernel_figures = args.full or timed_kernel_ms is not None
     durs, comparisons = [], 0.0
     per_rank = None     # N > 1: what every rank measured on its own stream (kernel, collective, assembly)
-    if cabi:
+    if timed_kernel_ms is not None:
+        durs.append(timed_kernel_ms)
+        comparisons = ctx.last_comparisons()    # 2 n_a n_j summed over the (a, j<=a) pairs: one launch per step
+    elif cabi and args.full:
         st = device.allgather_stats()   # HIP events of the last timed step, per host thread / device
         if st:
             per_rank = [{"kernel_ms": st["kernel_ms"][g], "comparisons": st["comparisons"][g],
@@ -1041,10 +1066,7 @@ def run_rank(args, emit=None):
             durs.append(ctx.last_kernel_ms())
             comparisons = ctx.last_comparisons()
         del buf
-    elif timed_kernel_ms is not None:
-        durs.append(timed_kernel_ms)
-        comparisons = ctx.last_comparisons()    # 2 n_a n_j summed over the (a, j<=a) pairs: one launch per step
-    else:
+    elif args.full:
         for _ in range(max(3, min(args.steps, 5))):
             ms, comparisons = 0.0, 0.0
             for c in range(chunks):
@@ -1055,9 +1077,9 @@ def run_rank(args, emit=None):
                 ms += ctx.last_kernel_ms()
                 comparisons += ctx.last_comparisons()   # 2 n_a n_j summed over this rank's (a, j<=a) pairs
             durs.append(ms)
-    kern_ms = float(np.mean(durs))
+    kern_ms = float(np.mean(durs)) if durs else None
     kname = ctx.last_kernel_name()
-    if dist_on and not cabi:
+    if kernel_figures and dist_on and not cabi:
         # one more, untimed, step with events around every collective and around the assembly
         barrier()
         probe = {}
@@ -1120,8 +1142,9 @@ def run_rank(args, emit=None):
                    "chunks": chunks,
                    "env": {k: v for k, v in sorted(os.environ.items()) if k.startswith("GKM_")}},
     }
-    # the parity gate: a matrix that is not the reference's, on any copy, sets the number aside
-    out["parity"] = parity
+    # the parity gate (--full): a matrix that is not the reference's, on any copy, sets the number aside
+    if args.full:
+        out["parity"] = parity
     if dumped is not None:
         out["dump_outputs"] = dumped
     parity_failed = parity is not None and parity.get("ok") is False
@@ -1129,7 +1152,7 @@ def run_rank(args, emit=None):
         out["parity_failed"] = True
         out["value_set_aside"] = out["value"]
         out["value"] = None
-    if rank == 0:
+    if rank == 0 and kernel_figures:
         kern_s = kern_ms * 1e-3
         algorithmic = comparisons * OPS_PER_COMPARISON / kern_s / 1e9
         pmc, pmc_src = (None, "custom problem or forced kernel: no PMC summary applies")
@@ -1194,8 +1217,9 @@ def run_rank(args, emit=None):
                            "slabs, row a = a + 1 doubles)." % chunks)
             if cabi:
                 rf["allgather_hipmalloc_calls_in_timed_region"] = allocs_timed
+    if rank == 0:
         # the side measurements must never cost the line itself: a failure is reported in their place
-        if n_gpus == 1 and args.workload == "c2" and not args.custom and not args.no_also:
+        if args.full and n_gpus == 1 and args.workload == "c2" and not args.custom and not args.no_also:
             # gkmQC's own shape (bin/gkmqc.py:150-154,181-185: 600 bp, wgkm L=10 k=6 d=3) and config 5 (ragged,
             # L=12 d=4), three steps each, so that their numbers are timed by whoever runs the headline line
             try:
@@ -1205,7 +1229,7 @@ def run_rank(args, emit=None):
                 out["also"] = {name: side_workload(name, dev) for name in ("peaks", "c5")}
             except Exception as e:   # noqa: BLE001
                 out["also"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if n_gpus == 1 and not args.no_end_to_end:
+        if args.full and n_gpus == 1 and not args.no_end_to_end:
             ctx.close()
             full = None
             torch.cuda.empty_cache()
@@ -1213,7 +1237,7 @@ def run_rank(args, emit=None):
                 out["end_to_end"] = end_to_end(args, dev)
             except Exception as e:   # noqa: BLE001
                 out["end_to_end"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args)
                 cb = out["cpu_baseline"]

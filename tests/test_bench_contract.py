@@ -32,7 +32,7 @@ def _one_line(r):
 @pytest.mark.parametrize("forced_dist", [False, True])
 def test_one_json_line_with_roofline_end_to_end_and_cpu_baseline(built, forced_dist):
     env = {"GKM_BENCH_FORCE_DIST": "1"} if forced_dist else {}   # the sharded path through real RCCL, one rank
-    d = _one_line(_run(SMALL, env))
+    d = _one_line(_run(SMALL + ["--full"], env))
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "end_to_end"):
         assert key in d, key
@@ -63,13 +63,43 @@ def test_one_json_line_with_roofline_end_to_end_and_cpu_baseline(built, forced_d
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("how", ["one_gpu", "gpus_2", "gpus_2_fallback"])
+def test_plain_run_measures_only_the_headline(built, how):
+    """Without --full the line carries the headline figure and nothing that takes a run or a check of its own: no parity
+    gate, no side workloads, no end_to_end, no CPU baseline and, for N > 1 without a launcher, no torch.distributed
+    cross-check unless the C-ABI child fails.  On one GPU the roofline is read off the timed steps' own launches."""
+    env = {} if how == "one_gpu" else {"GKM_BENCH_SHARE_GPU": "1", "GKM_BENCH_BACKEND": "gloo"}
+    if how == "gpus_2_fallback":
+        env["GKM_BENCH_CABI_FAIL"] = "1"
+    d = _one_line(_run((["--gpus", "2"] if how != "one_gpu" else []) + SMALL, env))
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype",
+                "config"):
+        assert key in d, key
+    assert d["unit"] == "pairs/s" and d["value"] > 0 and d["higher_is_better"] is True and d["dtype"] == "u32"
+    assert d["value"] == pytest.approx((800 * 799 / 2) / (d["ms_per_step"] * 1e-3))
+    for key in ("parity", "parity_failed", "also", "end_to_end", "cpu_baseline"):
+        assert key not in d, key
+    assert d["vs_baseline"] is None
+    if how == "one_gpu":
+        rf = d["roofline"]
+        assert "timed steps" in rf["kernel_ms_source"] and rf["kernel_ms"] > 0
+        assert rf["step_span_ms"] <= d["ms_per_step"] * 1.001
+    else:
+        assert d["n_gpus"] == 2 and "roofline" not in d
+        if how == "gpus_2":
+            assert d["assembly"].startswith("cabi") and d["config"]["transport"] == "p2p"
+        else:
+            assert "FALLBACK" in d["assembly"] and "injected" in d["cabi_error"] and d["config"]["transport"] == "gloo"
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("assembly", ["torch", "cabi"])
 def test_plain_gpus_2_launches_its_own_ranks(built, assembly):
     """No launcher, no WORLD_SIZE: `python bench.py --gpus 2` (two ranks sharing the box's one GPU; the
     torch path then moves the slabs through gloo, the one-process C-ABI path by peer copies) prints one
     line with n_gpus 2, and --check holds the assembled matrix to the single-GPU one bit for bit."""
     env = {"GKM_BENCH_SHARE_GPU": "1", "GKM_BENCH_BACKEND": "gloo"}
-    d = _one_line(_run(["--gpus", "2", "--assembly", assembly, "--check", "--no-cpu-baseline"] + SMALL, env))
+    d = _one_line(_run(["--gpus", "2", "--assembly", assembly, "--check", "--full", "--no-cpu-baseline"] + SMALL, env))
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["roofline"]["frac"] is None   # custom size: no PMC summary applies
     assert "end_to_end" not in d and "cpu_baseline" not in d
     # what an N > 1 line says about itself: ranks, transport, every rank's own kernel, the collective, the assembly
@@ -99,7 +129,7 @@ def test_gpus_2_measures_the_c_abi_entry_and_falls_back_to_torch(built, how):
         env["GKM_BENCH_CABI_FAIL"] = "1"
     if how == "kill":
         env["GKM_BENCH_CABI_TIMEOUT"] = "0.5"
-    d = _one_line(_run(["--gpus", "2", "--no-cpu-baseline"] + SMALL, env))
+    d = _one_line(_run(["--gpus", "2", "--full", "--no-cpu-baseline"] + SMALL, env))
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["config"]["ranks"] == 2
     if how == "ok":
         assert d["config"]["transport"] == "p2p" and d["assembly"].startswith("cabi") and "cabi_error" not in d
@@ -125,7 +155,7 @@ def test_gpus_2_under_the_launcher_prints_its_line_on_stdout(built):
             port = sk.getsockname()[1]
         r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                             "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                            "--gpus", "2", "--no-cpu-baseline"] + SMALL, cwd=ROOT, env=env, stdout=subprocess.PIPE,
+                            "--gpus", "2", "--full", "--no-cpu-baseline"] + SMALL, cwd=ROOT, env=env, stdout=subprocess.PIPE,
                            stderr=subprocess.PIPE, timeout=900)
         # (someone else may take the port between the probe and the launcher's own bind: the launcher then ends before
         # any rank exists -- probe again; anything else is the test's business)
@@ -152,8 +182,8 @@ def test_dump_outputs_holds_the_timed_matrix(built, tmp_path):
     the last of exactly --steps timed steps produced, against the reference's matrix; the unit diagonal included."""
     import numpy as np
     from tests import helpers
-    d = _one_line(_run(["--workload", "c1", "--steps", "3", "--warmup", "0", "--no-end-to-end", "--no-cpu-baseline",
-                        "--dump-outputs", str(tmp_path / "out")]))
+    d = _one_line(_run(["--workload", "c1", "--steps", "3", "--warmup", "0", "--full", "--no-end-to-end",
+                        "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "out")]))
     assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["parity"]["ok"] is True
     assert "timed steps" in d["roofline"]["kernel_ms_source"]    # one Gram launch per timed step, 3 of them
     n = 400
@@ -274,6 +304,13 @@ def test_launcher_stops_the_other_ranks_when_one_fails():
     assert bench.launch_ranks(args, [], cmd=[sys.executable, "-c", "import time; time.sleep(120)"], timeout=1.0) != 0
     assert time.time() - t0 < 20
     assert bench.launch_ranks(args, [], cmd=[sys.executable, "-c", "print('{}')"]) == 0
+
+
+def test_full_is_off_by_default():
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args([]).full is False
+    assert bench.parse_args(["--full"]).full is True
 
 
 def test_default_cpu_baseline_is_the_headline_workload():

@@ -5,7 +5,7 @@ O=gpurun_out/colchunk; mkdir -p $O
 for wl in c2 peaks c5; do
   for ch in 0 default 1024 2048 4096; do
     if [ "$ch" = default ]; then unset GKM_COL_CHUNK; else export GKM_COL_CHUNK=$ch; fi
-    echo "$wl chunk $ch: $(python3 bench.py --workload $wl --steps 3 --warmup 1 --no-cpu-baseline --no-end-to-end --no-also 2>/dev/null | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print("%.2f ms parity %s" % (d["roofline"]["kernel_ms"], d["parity"]["ok"]))')"
+    echo "$wl chunk $ch: $(python3 bench.py --workload $wl --steps 3 --warmup 1 --full --no-cpu-baseline --no-end-to-end --no-also 2>/dev/null | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print("%.2f ms parity %s" % (d["roofline"]["kernel_ms"], d["parity"]["ok"]))')"
   done
 done
 unset GKM_COL_CHUNK

@@ -3,7 +3,7 @@ O=gpurun_out/colchunk2; mkdir -p $O
 for wl in peaks c5 c2; do
   for ch in 0 2560 3072 3584 4096 5120; do
     export GKM_COL_CHUNK=$ch
-    t=$(python3 bench.py --workload $wl --steps 3 --warmup 1 --no-cpu-baseline --no-end-to-end --no-also 2>/dev/null | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print("%.2f ms parity %s" % (d["roofline"]["kernel_ms"], d["parity"]["ok"]))')
+    t=$(python3 bench.py --workload $wl --steps 3 --warmup 1 --full --no-cpu-baseline --no-end-to-end --no-also 2>/dev/null | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print("%.2f ms parity %s" % (d["roofline"]["kernel_ms"], d["parity"]["ok"]))')
     rocprofv3 --pmc FETCH_SIZE -d $O/f_${wl}_$ch --output-format csv -- python3 bench.py --workload $wl --steps 1 --warmup 0 --no-cpu-baseline --no-end-to-end --no-also > /dev/null 2> $O/f_${wl}_$ch.err
     f=$(python3 - "$O/f_${wl}_$ch" <<'PY'
 import csv, glob, sys

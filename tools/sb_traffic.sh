@@ -16,7 +16,7 @@ echo "# tools/sb_traffic.sh $R $WL: contexts sharing ONE MI355X; hot kernel per-
 rocprofv3 -L 2>/dev/null | grep -i -E "mall|dram|hbm|TCC_EA0_RDREQ|TCC_HIT|TCC_MISS|TCC_REQ" | head -40 > "$OUT/counters_avail.txt"
 for G in 1 2 4; do
   if [ "$G" = 1 ]; then ARGS="bench.py --workload $WL --steps 2 --warmup 1 --no-cpu-baseline --no-end-to-end --no-also";
-  else ARGS="bench.py --workload $WL --gpus $G --assembly cabi --steps 2 --warmup 1 --no-cpu-baseline --no-end-to-end"; fi
+  else ARGS="bench.py --workload $WL --gpus $G --assembly cabi --steps 2 --warmup 1 --full --no-cpu-baseline --no-end-to-end"; fi
   GKM_BENCH_SHARE_GPU=1 rocprofv3 --kernel-trace --stats -d "$OUT/stats_$G" --output-format csv -- python3 $ARGS > "$OUT/bench_$G.json" 2> "$OUT/bench_$G.err" || exit 1
   GKM_BENCH_SHARE_GPU=1 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch_$G" --output-format csv -- python3 $ARGS > /dev/null 2> "$OUT/fetch_$G.err" || exit 1
   GKM_BENCH_SHARE_GPU=1 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum -d "$OUT/tcc_$G" --output-format csv -- python3 $ARGS > /dev/null 2> "$OUT/tcc_$G.err" || echo "(no TCC_* pass for $G contexts)" >> "$TXT"
