@@ -13,6 +13,8 @@
  *   gkm_ism.hip            in-silico mutagenesis of a trained model (k_ism, k_ism_reduce, k_ism_self_base, k_ism_self),
  *                          gkmhip_ism_block, gkmhip_ism_self_profiles; hypothetical importance (k_ism_hyp,
  *                          k_ism_hyp_reduce), gkmhip_hyp_block
+ *   gkm_lmer.hip           l-mer weight tables of a trained model and scores from them (k_lmer_weights, k_lmer_score),
+ *                          gkmhip_lmer_weights, gkmhip_lmer_score
  */
 #ifndef GKM_INTERNAL_H
 #define GKM_INTERNAL_H

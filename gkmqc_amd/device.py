@@ -121,6 +121,10 @@ def load():
     L.gkmhip_ism_block.argtypes = (vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp)
     L.gkmhip_hyp_block.restype = i32
     L.gkmhip_hyp_block.argtypes = (vp, vp, i32, i32, i32, vp, vp, vp, vp)
+    L.gkmhip_lmer_weights.restype = i32
+    L.gkmhip_lmer_weights.argtypes = (vp, vp, vp, vp, i32, ctypes.c_uint32, ctypes.c_uint32, vp, vp)
+    L.gkmhip_lmer_score.restype = i32
+    L.gkmhip_lmer_score.argtypes = (vp, i32, i32, vp, vp, vp)
     L.gkmhip_ism_self_profiles.restype = i32
     L.gkmhip_ism_self_profiles.argtypes = (vp, i32, i32, vp, vp)
     L.gkmhip_self_norms.restype = i32
@@ -418,6 +422,25 @@ class GramContext:
         base of the range; include/gkm_hip.h gkmhip_ism_self_profiles)."""
         self._chk(self.lib.gkmhip_ism_self_profiles(self.handle, int(col_begin), int(col_end), prof_ptr, stream),
                   "gkmhip_ism_self_profiles")
+
+    def lmer_weights(self, c, v_ptr, cv_ptr, nv, u_begin, u_end, W_ptr, stream=0):
+        """L-mer weights W[u - u_begin] for the codes [u_begin, u_end) from nv canonical classes (v_ptr: device uint32
+        codes, cv_ptr: device doubles) into W_ptr: c = d + 1 host doubles (include/gkm_hip.h gkmhip_lmer_weights)."""
+        c = np.ascontiguousarray(c, dtype=np.float64)
+        if len(c) != self.d + 1:
+            raise GkmError("lmer_weights: c needs d + 1 = %d values" % (self.d + 1))
+        if not 0 <= int(u_begin) < int(u_end) <= 4 ** self.L:
+            raise GkmError("lmer_weights: the code range must satisfy 0 <= u_begin < u_end <= 4^L")
+        if int(nv) < 0:
+            raise GkmError("lmer_weights: nv must not be negative")
+        self._chk(self.lib.gkmhip_lmer_weights(self.handle, c.ctypes.data, v_ptr, cv_ptr, int(nv), int(u_begin), int(u_end),
+                                               W_ptr, stream), "gkmhip_lmer_weights")
+
+    def lmer_score(self, col_begin, col_end, W_ptr, out_ptr, stream=0):
+        """sum_p w_j[p] W[code(u_p)] of the uploaded sequences [col_begin, col_end) into out_ptr: W_ptr = 4^L device
+        doubles indexed by code (include/gkm_hip.h gkmhip_lmer_score)."""
+        self._chk(self.lib.gkmhip_lmer_score(self.handle, int(col_begin), int(col_end), W_ptr, out_ptr, stream),
+                  "gkmhip_lmer_score")
 
     def self_norms(self, sq_ptr, stream=0):
         self._chk(self.lib.gkmhip_self_norms(self.handle, sq_ptr, stream), "gkmhip_self_norms")

@@ -17,13 +17,18 @@ The other half of a gkm-SVM next to the cross-validation of `gkmsvm.py` (the cou
     mismatch count moves under a substitution, and one that counts every mutant's profile against itself;
   * `hypothetical` gives, for every position and each of the four bases, the importance that base would get there
     (gkmhip_hyp_block): ism's upload, self norms, mutant self profiles and tallies, folded the way
-    `explain` folds its own.
+    `explain` folds its own;
+  * `weights` folds a model (not RBF) into one weight per l-mer (gkmhip_lmer_weights) and writes that
+    table; `predict-table` scores from it with only the queries uploaded: their self norms, then one gather per l-mer
+    (gkmhip_lmer_score) -- `predict`'s values up to rounding, for a fraction of the work.
 
     python -m gkmqc_amd.gkmpredict train [-t -L -k -d -M -H -G -C -e -u] pos.fa neg.fa model.txt
     python -m gkmqc_amd.gkmpredict predict query.fa model.txt out.txt
     python -m gkmqc_amd.gkmpredict explain [--block Qb] query.fa model.txt out.txt
     python -m gkmqc_amd.gkmpredict ism [--block Qb] query.fa model.txt out.txt
     python -m gkmqc_amd.gkmpredict hypothetical [--block Qb] query.fa model.txt out.txt
+    python -m gkmqc_amd.gkmpredict weights model.txt weights.txt
+    python -m gkmqc_amd.gkmpredict predict-table [--block Qb] query.fa weights.txt out.txt
 """
 import argparse
 import logging
@@ -608,6 +613,261 @@ def _hyp_flat(model, seqs, device, block, on_block=None):
     return out
 
 
+# ------------------------------------------------------------------ l-mer weight tables
+TABLE_FORMAT = "gkmqc-lmer-weights-1"
+_TABLE_KEYS = ("format", "kernel_type", "L", "k", "d", "M", "H", "rho")
+TABLE_PIECE = 1 << 20     # codes per k_lmer_weights launch
+
+
+def check_table_model(model, what="weights"):
+    """The models an l-mer table serves: every model `score` serves except the RBF types, whose score is not linear in
+    the query's l-mers."""
+    if model.kernel_type in (3, 5):
+        raise ModelError("%s: RBF kernels (types 3 and 5) have no l-mer weight table (their score is not linear in the "
+                         "query's l-mers)" % what)
+
+
+def pack_lmers(codes, L):
+    """Codes of the l-mers of a base-code array, first base in the highest pair (as the device tables pack them)."""
+    codes = np.asarray(codes, dtype=np.uint32)
+    n = len(codes) - L + 1
+    v = np.zeros(max(n, 0), dtype=np.uint32)
+    for i in range(L):
+        v = (v << np.uint32(2)) | codes[i:i + n]
+    return v
+
+
+def lmer_rc(u, L):
+    """Reverse complements of l-mer codes."""
+    u = np.asarray(u, dtype=np.uint32)
+    r = np.zeros_like(u)
+    for i in range(L):
+        r = (r << np.uint32(2)) | (np.uint32(3) - ((u >> np.uint32(2 * i)) & np.uint32(3)))
+    return r
+
+
+def lmer_classes(model, sq):
+    """(v, cv): the canonical classes min(f, rc(f)) of the support vectors' forward l-mers f, ascending, and for each the
+    sum of dual_coef_s / sq_s * w_s[q] over its occurrences (s, q) in support-vector order, then position order.  sq: the
+    support vectors' self norms."""
+    L = model.L
+    coef = model.dual_coef() / np.asarray(sq, dtype=np.float64)
+    lens = np.array([len(s) for s in model.seqs], dtype=np.int64)
+    n = lens - L + 1
+    codes = np.concatenate(model.seqs)
+    starts = np.concatenate(([0], np.cumsum(lens)[:-1]))
+    owner = np.repeat(np.arange(model.n_sv), n)
+    pos = np.arange(int(n.sum()), dtype=np.int64) - np.repeat(np.cumsum(n) - n, n)
+    f = pack_lmers(codes, L)[np.repeat(starts, n) + pos]
+    if model.kernel_type in (4, 5):
+        wd = dv.distance_weights(model.kernel_type, int(n.max()), model.M, model.H).astype(np.float64)
+        w = wd[np.abs(np.repeat(n // 2, n) - pos)]
+    else:
+        w = np.ones(len(f))
+    v, inv = np.unique(np.minimum(f, lmer_rc(f, L)), return_inverse=True)
+    cv = np.bincount(inv.reshape(-1), weights=coef[owner] * w, minlength=len(v))
+    return v.astype(np.uint32), cv
+
+
+class LmerTable:
+    """A trained model folded into one weight per l-mer: W (float64, 4^L, indexed by code, W[u] ==
+    W[rc(u)]) plus what scoring needs -- the kernel parameters and rho; no support vectors."""
+
+    def __init__(self, W, kernel_type, L, k, d, M, H, rho):
+        self.kernel_type, self.L, self.k, self.d, self.M = int(kernel_type), int(L), int(k), int(d), int(M)
+        self.H, self.rho = float(H), float(rho)
+        self.W = np.ascontiguousarray(W, dtype=np.float64)
+        bad = dv.check_parameters(self.kernel_type, self.L, self.k, self.d)
+        if bad:
+            raise ModelError("kernel parameters rejected: %s" % bad)
+        check_table_model(self, "table")
+        if not 0 <= self.M <= 255 or not (np.isfinite(self.H) and np.isfinite(self.rho)):
+            raise ModelError("M must lie in 0..255, H and rho must be finite")
+        if self.W.shape != (4 ** self.L,):
+            raise ModelError("a table for L = %d needs 4^L = %d weights" % (self.L, 4 ** self.L))
+
+    def kernel_params(self):
+        return (self.kernel_type, self.L, self.k, self.d, self.M, self.H, 1.0)
+
+    def save(self, path):
+        """Write the weights file (format: INTEGRATION.md §5b): `# key value` header lines, then LMER<TAB>weight for
+        every canonical l-mer in lexicographic ACGT order, with repr() floats."""
+        u = canonical_codes(self.L)
+        head = [("format", TABLE_FORMAT), ("kernel_type", self.kernel_type), ("L", self.L), ("k", self.k), ("d", self.d),
+                ("M", self.M), ("H", repr(self.H)), ("rho", repr(self.rho))]
+        tmp = path + ".tmp"
+        with open(tmp, "w") as f:
+            for key, val in head:
+                f.write("# %s %s\n" % (key, val))
+            text, weights = lmer_text(u, self.L), self.W[u].tolist()
+            for i in range(0, len(u), 1 << 16):
+                f.write("".join("%s\t%r\n" % tw for tw in zip(text[i:i + (1 << 16)], weights[i:i + (1 << 16)])))
+        os.replace(tmp, path)
+
+
+def canonical_codes(L):
+    """The canonical l-mer codes (u <= rc(u)) in ascending order = lexicographic ACGT order:
+    (4^L + 4^(L/2) [L even]) / 2 of them."""
+    u = np.arange(4 ** L, dtype=np.uint32)
+    return u[u <= lmer_rc(u, L)]
+
+
+def lmer_text(u, L):
+    """l-mer codes -> their ACGT strings"""
+    u = np.asarray(u, dtype=np.uint32)
+    digits = np.stack([(u >> np.uint32(2 * (L - 1 - i))) & np.uint32(3) for i in range(L)], axis=1).astype(np.uint8)
+    return _ACGT[digits].view("S%d" % L).reshape(-1).astype(str).tolist() if len(u) else []
+
+
+def load_lmer_table(path):
+    """Read a weights file written by LmerTable.save; anything malformed raises ModelError with the reason."""
+    with open(path) as f:
+        lines = f.read().split("\n")
+    if lines and lines[-1] == "":
+        lines.pop()
+    head, i = {}, 0
+    while i < len(lines) and lines[i].startswith("#"):
+        parts = lines[i].split(" ")
+        if len(parts) != 3 or parts[0] != "#" or parts[1] not in _TABLE_KEYS:
+            raise ModelError("%s:%d: not a `# key value` line of the header: %r" % (path, i + 1, lines[i]))
+        if parts[1] in head:
+            raise ModelError("%s:%d: key %s given twice" % (path, i + 1, parts[1]))
+        head[parts[1]] = parts[2]
+        i += 1
+    missing = [key for key in _TABLE_KEYS if key not in head]
+    if missing:
+        raise ModelError("%s: missing key(s): %s" % (path, ", ".join(missing)))
+    if head["format"] != TABLE_FORMAT:
+        raise ModelError("%s: format %r, expected %r" % (path, head["format"], TABLE_FORMAT))
+    try:
+        val = {key: int(head[key]) for key in ("kernel_type", "L", "k", "d", "M")}
+        val.update({key: float(head[key]) for key in ("H", "rho")})
+    except ValueError as e:
+        raise ModelError("%s: %s" % (path, e))
+    L = val["L"]
+    bad = dv.check_parameters(val["kernel_type"], L, val["k"], val["d"])
+    if bad:
+        raise ModelError("%s: kernel parameters rejected: %s" % (path, bad))
+    body = lines[i:]
+    want = len(canonical_codes(L))
+    if len(body) != want:
+        raise ModelError("%s: %d l-mer lines, expected %d for L = %d" % (path, len(body), want, L))
+    pairs = [line.split("\t") for line in body]
+    for j, p in enumerate(pairs):
+        if len(p) != 2 or len(p[0]) != L:
+            raise ModelError("%s:%d: expected an l-mer of %d bases<TAB>weight" % (path, i + 1 + j, L))
+    raw = np.frombuffer("".join(p[0] for p in pairs).encode("latin-1", "replace"), dtype=np.uint8).reshape(-1, L)
+    lut = np.full(256, 255, dtype=np.uint8)
+    lut[_ACGT] = np.arange(4, dtype=np.uint8)
+    digits = lut[raw]
+    if (digits == 255).any():
+        j = int(np.nonzero((digits == 255).any(axis=1))[0][0])
+        raise ModelError("%s:%d: an l-mer holds a character other than A, C, G, T" % (path, i + 1 + j))
+    u = np.zeros(len(body), dtype=np.uint32)
+    for b in range(L):
+        u = (u << np.uint32(2)) | digits[:, b].astype(np.uint32)
+    rc = lmer_rc(u, L)
+    if (u > rc).any():
+        j = int(np.nonzero(u > rc)[0][0])
+        raise ModelError("%s:%d: %s is not canonical (its reverse complement comes first)" % (path, i + 1 + j, pairs[j][0]))
+    order = np.argsort(u, kind="stable")
+    rep = np.nonzero(u[order][1:] == u[order][:-1])[0]
+    if len(rep):
+        j = int(order[rep[0] + 1])
+        raise ModelError("%s:%d: l-mer %s given twice" % (path, i + 1 + j, pairs[j][0]))
+    try:
+        w = np.array([float(p[1]) for p in pairs], dtype=np.float64)
+    except ValueError as e:
+        raise ModelError("%s: %s" % (path, e))
+    W = np.empty(4 ** L, dtype=np.float64)
+    W[u] = w
+    W[rc] = w
+    return LmerTable(W, val["kernel_type"], L, val["k"], val["d"], val["M"], val["H"], val["rho"])
+
+
+def lmer_weights(model, device=0, on_piece=None):
+    """The l-mer weight table of `model` -> LmerTable:
+
+        W(u) = sum_s (dual_coef_s / sq_s) sum_q w_s[q] (c[m(u, f_q)] + c[m(u, rc(f_q))])      (c[m] = 0 for m > d)
+
+    so that score(x) = sum_p w_x[p] W(u_p) / sq_x + rho.  Every model `score` serves except RBF (types 3 and 5), k = 0
+    included.  The support vectors' self norms come from one gkmhip_self_norms launch, the classes (v, cv) from the host
+    (lmer_classes), W from k_lmer_weights over all 4^L codes in pieces of TABLE_PIECE.  on_piece(dict) (measurements):
+    called after every piece with its codes, kernel milliseconds (HIP events) and l-mer comparisons."""
+    check_table_model(model)
+    import torch
+    S, L, d = model.n_sv, model.L, model.d
+    ctx = dv.cached_context(*model.kernel_params(), device=device)
+    sv_off = np.zeros(S + 1, dtype=np.int64)
+    np.cumsum([len(s) for s in model.seqs], out=sv_off[1:])
+    dev = torch.device("cuda", device)
+    c = dv.mismatch_weights(model.kernel_type, L, model.k)[:d + 1]
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        ctx.set_sequences(dv.FlatSequences(np.concatenate(model.seqs), sv_off), stream)
+        sq = torch.empty(S, dtype=torch.float64, device=dev)
+        ctx.self_norms(sq.data_ptr(), stream)
+        v, cv = lmer_classes(model, sq.cpu().numpy())
+        d_v = torch.from_numpy(v.view(np.int32)).to(dev)
+        d_cv = torch.from_numpy(cv).to(dev)
+        W = torch.empty(4 ** L, dtype=torch.float64, device=dev)
+        for u0 in range(0, 4 ** L, TABLE_PIECE):
+            u1 = min(4 ** L, u0 + TABLE_PIECE)
+            ctx.lmer_weights(c, d_v.data_ptr(), d_cv.data_ptr(), len(v), u0, u1, W.data_ptr() + 8 * u0, stream)
+            if on_piece is not None:
+                on_piece(dict(codes=u1 - u0, classes=len(v), kernel_ms=ctx.last_kernel_ms(),
+                              comparisons=ctx.last_comparisons(), kernel=ctx.last_kernel_name()))
+        Wh = W.cpu().numpy()
+    return LmerTable(Wh, model.kernel_type, L, model.k, d, model.M, model.H, model.rho)
+
+
+def default_table_block(max_len, budget=BLOCK_BYTES):
+    """Queries per block: the upload's per-sequence device tables (sized by the longest query, a few words per base)
+    within `budget` bytes, and at most 32 768 (about `score`'s blocks of support vectors and queries together)."""
+    return int(max(1, min(1 << 15, budget // (32 * max(int(max_len), 64)))))
+
+
+def score_with_table(table, fasta_or_sequences, device=0, block=None, on_block=None):
+    """Decision values from an l-mer weight table for a FASTA file (or a list / FlatSequences of base codes) -> (names,
+    scores): sum_p w_x[p] W(u_p) / sq_x + rho, `score`'s value up to rounding.  Only the queries are uploaded: per block
+    the self norms (gkmhip_self_norms) and one gather per l-mer (k_lmer_score); bit-identical for every block size.
+    on_block(dict) (measurements): called after every block with its size, k_lmer_score's milliseconds and the block's
+    wall time."""
+    seqs, names = _as_queries(fasta_or_sequences)
+    check_queries(table, seqs)
+    return names, _table_flat(table, seqs, device, block, on_block)
+
+
+def _table_flat(table, seqs, device, block, on_block=None):
+    import torch
+    Q = len(seqs)
+    lens = np.diff(seqs.off)
+    qb_max = min(Q, int(block) if block else default_table_block(int(lens.max())))
+    if qb_max < 1:
+        raise ModelError("block must be at least 1")
+    ctx = dv.cached_context(*table.kernel_params(), device=device)
+    dev = torch.device("cuda", device)
+    out = np.empty(Q)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        W = torch.from_numpy(table.W).to(dev)
+        sq = torch.empty(qb_max, dtype=torch.float64, device=dev)
+        T = torch.empty(qb_max, dtype=torch.float64, device=dev)
+        for q0 in range(0, Q, qb_max):
+            q1 = min(Q, q0 + qb_max)
+            qb = q1 - q0
+            t0 = time.perf_counter()
+            qoff = seqs.off[q0:q1 + 1]
+            ctx.set_sequences(dv.FlatSequences(seqs.codes[qoff[0]:qoff[-1]], qoff - qoff[0]), stream)
+            ctx.self_norms(sq.data_ptr(), stream)
+            ctx.lmer_score(0, qb, W.data_ptr(), T.data_ptr(), stream)
+            out[q0:q1] = (T[:qb] / sq[:qb] + table.rho).cpu().numpy()
+            if on_block is not None:
+                on_block(dict(queries=qb, score_kernel_ms=ctx.last_kernel_ms(), lmers=ctx.last_comparisons(),
+                              kernel=ctx.last_kernel_name(), wall_ms=(time.perf_counter() - t0) * 1e3))
+    return out
+
+
 # ------------------------------------------------------------------ command line
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m gkmqc_amd.gkmpredict",
@@ -654,6 +914,18 @@ def build_parser():
     h.add_argument("query_fa")
     h.add_argument("model")
     h.add_argument("output")
+    w = sub.add_parser("weights", help="fold a model into its l-mer weight table: a `# key value` header, then "
+                                       "LMER<TAB>weight per canonical l-mer")
+    w.add_argument("--device", type=int, default=0, help="GPU (default: 0)")
+    w.add_argument("model")
+    w.add_argument("output")
+    r = sub.add_parser("predict-table", help="score the sequences of query.fa from an l-mer weight table: name<TAB>score "
+                                             "per line, in file order (the predict format)")
+    r.add_argument("--device", type=int, default=0, help="GPU (default: 0)")
+    r.add_argument("--block", type=int, default=None, help="queries per device block (default: from device memory)")
+    r.add_argument("query_fa")
+    r.add_argument("weights")
+    r.add_argument("output")
     return p
 
 
@@ -685,12 +957,16 @@ def main(argv=None):
             m.save(a.model)
             print("%d support vectors (%d negative, %d positive), rho %r -> %s"
                   % (m.n_sv, m.n0, m.n_sv - m.n0, m.rho, a.model), file=sys.stderr)
+        elif a.cmd == "weights":
+            m = load(a.model)
+            check_table_model(m)
+            lmer_weights(m, a.device).save(a.output)
         else:
             if a.block is not None and a.block < 1:
                 raise ModelError("--block must be at least 1")
             if not os.path.isfile(a.query_fa):
                 raise ModelError("cannot read %s" % a.query_fa)
-            m = load(a.model)
+            m = load_lmer_table(a.weights) if a.cmd == "predict-table" else load(a.model)
             if a.cmd == "explain":
                 check_explainable(m)
             elif a.cmd == "ism":
@@ -707,7 +983,10 @@ def main(argv=None):
             elif a.cmd == "hypothetical":
                 write_ism(tmp, names, _hyp_flat(m, seqs, a.device, a.block))
             else:
-                scores = _score_flat(m, seqs, a.device, a.block, dv.KERNEL_AUTO, None)
+                if a.cmd == "predict-table":
+                    scores = _table_flat(m, seqs, a.device, a.block)
+                else:
+                    scores = _score_flat(m, seqs, a.device, a.block, dv.KERNEL_AUTO, None)
                 with open(tmp, "w") as f:
                     for name, s in zip(names, scores):
                         f.write("%s\t%r\n" % (name, float(s)))

@@ -165,6 +165,34 @@ int gkmhip_hyp_block(gkmhip_ctx *ctx, const int *rows, int nrows, int col_begin,
  * Work is enqueued on `stream`; last_kernel_ms / last_comparisons / last_kernel_name describe k_ism_self_base + k_ism_self. */
 int gkmhip_ism_self_profiles(gkmhip_ctx *ctx, int col_begin, int col_end, int64_t *prof, void *stream);
 
+/* L-mer weight table: for every code u of [u_begin, u_end) (an l-mer packed as gkm_bitslice.h's
+ * lmer_entry packs it, first base in the highest pair, no weight byte),
+ *   W[u - u_begin] = sum_{i ascending} cv[i] * (cf + cr),   cf = c[m(u, v[i])] if that mismatch count is <= d, else 0.0,
+ *                                                           cr the same for rc(v[i]),
+ * the sum from 0.0 in that order whatever the range, the launch or the run (no atomics), so W[u] and W[rc(u)] are
+ * bit-identical.  With v the canonical classes (min(code, rc(code))) of a model's support-vector l-mers and cv[i] the sum
+ * of dual_coef_s / sq_s w_s[q] over the class, W is the model's weight per l-mer and score(x) = sum_p w_x[p] W(u_p) / sq_x
+ * + rho.  L and d are the context's; no sequences need be uploaded.
+ *   c  HOST, d + 1 doubles (tests pass unit vectors to count single mismatch classes);
+ *   v  DEVICE, nv l-mer codes (distinct, ascending and canonical for a model's table; the sum is defined for any);
+ *   cv DEVICE, nv doubles;
+ *   W  DEVICE, u_end - u_begin doubles; nothing else is written.
+ * 0 <= u_begin < u_end <= 4^L.  Work is enqueued on `stream`; last_kernel_ms / last_comparisons (2 nv (u_end - u_begin))
+ * / last_kernel_name describe k_lmer_weights. */
+int gkmhip_lmer_weights(gkmhip_ctx *ctx, const double *c, const uint32_t *v, const double *cv, int nv, uint32_t u_begin,
+                        uint32_t u_end, double *W, void *stream);
+
+/* Scores from an l-mer weight table: for every uploaded sequence j of [col_begin, col_end),
+ *   out[j - col_begin] = sum_p w_j[p] W[code(u_p)]
+ * over its forward l-mers u_p with their positional weights (the context's l-mer table).  One wave per sequence with a
+ * fixed assignment of positions to lanes and a fixed reduction, so the value is bit-identical whatever range or
+ * neighbours the sequence has.
+ *   W   DEVICE, 4^L doubles, indexed by code;
+ *   out DEVICE, col_end - col_begin doubles.
+ * Work is enqueued on `stream`; last_kernel_ms / last_comparisons (the l-mers looked up) / last_kernel_name describe
+ * k_lmer_score. */
+int gkmhip_lmer_score(gkmhip_ctx *ctx, int col_begin, int col_end, const double *W, double *out, void *stream);
+
 /* sqnorm[i] = sqrt(G(i,i)) for all uploaded sequences (device array of n doubles), computed
  * from the diagonal band only (~1 % of the work of the whole matrix).  Replaces
  * gkmkernel_kernelfunc_sqnorm_single, src/libgkm.c:723-759. */
