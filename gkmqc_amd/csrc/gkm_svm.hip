@@ -16,6 +16,9 @@
  * iterations each): 0.10 s for the whole cross-validation, ~22 k cycles per iteration, bound by
  * the instruction issue of the one CU a fold runs on (scikit-learn, 5 processes: 0.95 s).
  * -DSVM_PROF prints the per-phase cycle counts.
+ * epsilon-SVR (gkmsvm_train_svr_batch*) runs the same kernels on LIBSVM's 2l-variable problem with a
+ * per-position linear term (template flag LIN; the C-SVC instantiations are unchanged), and predicts with
+ * k_decision<true>, the signed sum.
  */
 #include <hip/hip_runtime.h>
 
@@ -24,6 +27,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gkm_svm.h"
@@ -124,6 +128,11 @@ struct SvmProb {
     int l, n0;
     double *alpha, *grad, *rho;
     int *iters;
+};
+/* epsilon-SVR (LIBSVM solve_epsilon_svr): the same solver on 2l positions with a linear term p per position instead of
+ * C-SVC's constant -1 (template flag LIN of k_smo / k_smo_general; the C-SVC instantiations never see this field) */
+struct SvmProbLin : SvmProb {
+    const double *lin;
 };
 
 /* A candidate of the working-set selection together with everything the other threads need to
@@ -255,15 +264,16 @@ __global__ void k_diag(const double *__restrict__ K, int64_t ld, int n, double *
  * its payload in LDS, every thread then picks the block winner from the T/64 records and does
  * the (scalar) two-variable update redundantly, so no third exchange is needed.
  */
-template <int T, int SVM_R, int TABM>
+template <int T, int SVM_R, int TABM, bool LIN>
 __global__ __launch_bounds__(T) void k_smo(const double *__restrict__ K, int64_t ld, const double *__restrict__ diag,
-                                           const SvmProb *probs, double C, double eps, int max_iter)
+                                           const std::conditional_t<LIN, SvmProbLin, SvmProb> *probs, double C,
+                                           double eps, int max_iter)
 {
     constexpr int NW = T / 64;
     __shared__ Cand candA[NW], candB[NW];
     __shared__ double g2s[NW];
     __shared__ double chunk[T];
-    const SvmProb p = probs[blockIdx.x];
+    const auto p = probs[blockIdx.x];
     const auto *const idx_g = as_global(p.idx);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l = p.l, n0 = p.n0;
 
@@ -296,8 +306,13 @@ __global__ __launch_bounds__(T) void k_smo(const double *__restrict__ K, int64_t
             qd[QDG ? 0 : r] = dg;
         }
         if (ALS) al_s[k] = 0.0;
-        else al[ALS ? 0 : r] = 0.0;  /* LIBSVM: alpha = 0, G = p = -1; stored as S = y G (see below) */
-        G[r] = k < n0 ? -1.0 : 1.0;
+        else al[ALS ? 0 : r] = 0.0;  /* LIBSVM: alpha = 0, G = p (C-SVC: -1); stored as S = y G (see below) */
+        if constexpr (LIN) {
+            const double pk = k < l ? as_global(p.lin)[k] : 0.0;
+            G[r] = k < n0 ? pk : -pk;
+        } else {
+            G[r] = k < n0 ? -1.0 : 1.0;
+        }
     }
     if (TAB || ALS) __syncthreads();
     /* The gradient is kept as S_k = y_k G_k and kernel values without LIBSVM's y_i y_k factor: every
@@ -619,6 +634,9 @@ struct GenProb {
     int *fg, *fy;                       /* their matrix index and label */
     float *Qi, *Qj;
 };
+struct GenProbLin : GenProb {
+    const double *lin; /* epsilon-SVR's p, by ORIGINAL position: p at position k is lin[aset[k]] (LIBSVM swaps p) */
+};
 
 /* threads per fold: template parameter GEN_T of k_smo_general -- 1024, or 512 for folds of at most 8 192 samples */
 constexpr int GEN_U = 8; /* positions of a thread whose loads are in flight together */
@@ -696,10 +714,11 @@ __device__ __forceinline__ void block_select_min_and_max(double &v, int &k, doub
     mx = row_max(mslots[lane & (GEN_NW - 1)]);
 }
 
-template <int GEN_T, bool LDS_STATE>
+template <int GEN_T, bool LDS_STATE, bool LIN>
 __global__ __launch_bounds__(GEN_T) void k_smo_general(const double *__restrict__ K, int64_t ld,
-                                                       const double *__restrict__ diag, const GenProb *probs, double C,
-                                                       double eps, int max_iter, int shrinking, int cap)
+                                                       const double *__restrict__ diag,
+                                                       const std::conditional_t<LIN, GenProbLin, GenProb> *probs,
+                                                       double C, double eps, int max_iter, int shrinking, int cap)
 {
     constexpr int GEN_NW = GEN_T / 64;
     constexpr int GEN_U = LDS_STATE ? GEN_U_LDS : GEN_T == 1024 ? GEN_U_1024 : ::GEN_U;
@@ -712,7 +731,7 @@ __global__ __launch_bounds__(GEN_T) void k_smo_general(const double *__restrict_
      * positions; with LDS_STATE then cap state bytes, cap doubles G, cap floats Q_i, cap ints matrix index */
     extern __shared__ __attribute__((aligned(16))) unsigned char flag_s[];
     unsigned char *const st_s = flag_s + cap;
-    const GenProb p = probs[blockIdx.x];
+    const auto p = probs[blockIdx.x];
     const int tid = threadIdx.x, l = p.l;
     auto *const gidx = pick<LDS_STATE>((int *)(flag_s + (size_t)14 * cap), as_global(p.gidx));
     auto *const ys = as_global(p.ys), *const aset = as_global(p.aset);
@@ -736,7 +755,8 @@ __global__ __launch_bounds__(GEN_T) void k_smo_general(const double *__restrict_
         ys[k] = k < p.n0 ? 1 : -1;
         aset[k] = k;
         alpha[k] = 0.0;
-        G[k] = -1.0; /* p = -1 */
+        if constexpr (LIN) G[k] = as_global(p.lin)[k]; /* G = p */
+        else G[k] = -1.0; /* p = -1 */
         Gbar[k] = 0.0;
         QD[k] = diag[g];
         if constexpr (LDS_STATE) st_s[k] = (unsigned char)encode(0.0, k < p.n0 ? 1 : -1);
@@ -801,7 +821,9 @@ __global__ __launch_bounds__(GEN_T) void k_smo_general(const double *__restrict_
         __syncthreads();
         const int nf = misc[0];
         for (int j = active + tid; j < l; j += GEN_T) {
-            double g = Gbar[j] + (-1.0);
+            double g;
+            if constexpr (LIN) g = Gbar[j] + as_global(p.lin)[aset[j]]; /* p of the position: p swaps with it */
+            else g = Gbar[j] + (-1.0);
             const int gj = gidx[j], yj = ys[j];
             for (int f0 = 0; f0 < nf; f0 += 8) { /* 8 kernel values in flight, the additions in order */
                 double kv[8];
@@ -1196,8 +1218,11 @@ struct DecProb {
  * training samples are in flight together (the index -> matrix row chain would otherwise cost one
  * memory round trip per sample: the call took 5.6 ms instead of 3.5 ms for 5 folds of the headline
  * matrix, host overhead included); the
- * additions stay sequential, in LIBSVM's order. */
+ * additions stay sequential, in LIBSVM's order.
+ * SIGNED (epsilon-SVR): `alpha` holds the signed coefficients and every nonzero one is added as it is
+ * (LIBSVM's regression sum over its support vectors); n0 is not read. */
 constexpr int DEC_U = 16;
+template <bool SIGNED>
 __global__ void k_decision(const double *__restrict__ K, int64_t ld, const DecProb *probs)
 {
     const DecProb p = probs[blockIdx.y];
@@ -1216,42 +1241,52 @@ __global__ void k_decision(const double *__restrict__ K, int64_t ld, const DecPr
             kv[u] = K[(int64_t)idx_g[k] * ld + col];
         }
 #pragma unroll
-        for (int u = 0; u < DEC_U; u++)
-            if (a[u] > 0) sum += (k0 + u < p.n0 ? a[u] : -a[u]) * kv[u];
+        for (int u = 0; u < DEC_U; u++) {
+            if constexpr (SIGNED) {
+                if (a[u] != 0) sum += a[u] * kv[u];
+            } else {
+                if (a[u] > 0) sum += (k0 + u < p.n0 ? a[u] : -a[u]) * kv[u];
+            }
+        }
     }
     p.dec[t] = sum - *p.rho;
 }
 
-extern "C" int gkmsvm_train_batch(int device, const double *K, int64_t ld, int n, int nprob, const int *idx,
-                                  const int64_t *off, const int *n0, double C, double eps, double *alpha, double *grad,
-                                  double *rho, int *iters, void *stream_)
+/* k_smo for C-SVC (LIN = false, lin unused) or on an epsilon-SVR problem already laid out as LIBSVM's 2l positions */
+template <bool LIN>
+static int train_batch(const char *name, int device, const double *K, int64_t ld, int n, int nprob, const int *idx,
+                       const int64_t *off, const int *n0, const double *lin, double C, double eps, double *alpha,
+                       double *grad, double *rho, int *iters, void *stream_)
 {
-    if (!K || n <= 0 || ld < n || nprob <= 0 || !idx || !off || !n0 || !alpha || !grad || !rho || !iters) {
-        g_svm_err = "gkmsvm_train_batch: bad arguments";
+    using Prob = std::conditional_t<LIN, SvmProbLin, SvmProb>;
+    if (!K || n <= 0 || ld < n || nprob <= 0 || !idx || !off || !n0 || !alpha || !grad || !rho || !iters || (LIN && !lin)) {
+        g_svm_err = std::string(name) + ": bad arguments";
         return 2;
     }
     hipStream_t stream = (hipStream_t)stream_;
     SVMCHK(hipSetDevice(device));
-    std::vector<SvmProb> h((size_t)nprob);
+    std::vector<Prob> h((size_t)nprob);
     int64_t maxl = 0;
     for (int p = 0; p < nprob; p++) {
         const int64_t l = off[p + 1] - off[p];
         if (l > maxl) maxl = l;
         if (l <= 0 || l > (int64_t)SVM_MAX_L || n0[p] < 0 || n0[p] > l) {
-            g_svm_err = "gkmsvm_train_batch: a problem has no samples or more than 16384";
+            g_svm_err = std::string(name) + ": a problem has no samples or more than 16384";
             return 3;
         }
-        h[(size_t)p] = {idx + off[p], (int)l, n0[p], alpha + off[p], grad + off[p], rho + p, iters + p};
+        SvmProb &b = h[(size_t)p];
+        b = {idx + off[p], (int)l, n0[p], alpha + off[p], grad + off[p], rho + p, iters + p};
+        if constexpr (LIN) h[(size_t)p].lin = lin + off[p];
     }
-    const size_t probs_bytes = align256(sizeof(SvmProb) * (size_t)nprob);
+    const size_t probs_bytes = align256(sizeof(Prob) * (size_t)nprob);
     SvmScratch *const scr = scratch_acquire(device, probs_bytes + sizeof(double) * (size_t)n);
-    if (!scr) { g_svm_err = "gkmsvm_train_batch: device scratch"; return 4; }
+    if (!scr) { g_svm_err = std::string(name) + ": device scratch"; return 4; }
     /* (error returns included: whatever this call enqueued may still be writing the buffer -- k_diag below -- and another
      * solver on another stream of the device may take it from the pool next) */
     struct Release { SvmScratch *b; hipStream_t s; ~Release() { (void)hipStreamSynchronize(s); scratch_release(b); } } release{scr, stream};
-    SvmProb *const dprobs = (SvmProb *)scr->p;
+    Prob *const dprobs = (Prob *)scr->p;
     double *const diag = (double *)(scr->p + probs_bytes);
-    SVMCHK(hipMemcpyAsync(dprobs, h.data(), sizeof(SvmProb) * (size_t)nprob, hipMemcpyHostToDevice, stream));
+    SVMCHK(hipMemcpyAsync(dprobs, h.data(), sizeof(Prob) * (size_t)nprob, hipMemcpyHostToDevice, stream));
     SVMCHK(hipStreamSynchronize(stream)); /* h is a host temporary */
     hipLaunchKernelGGL(k_diag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, K, ld, n, diag);
     /* fewest threads and registers that hold the largest problem: narrower reductions, fewer waves
@@ -1280,14 +1315,14 @@ extern "C" int gkmsvm_train_batch(int device, const double *K, int64_t ld, int n
 #define SMO_LAUNCH(TT, RR, TB)                                                                                  \
     if (T == TT && R == RR) {                                                                                   \
         const size_t dyn = TB == 1 ? (size_t)TT * RR * 12 : TB == 2 ? (size_t)TT * RR * 8 : 0;                  \
-        if (dyn > 0 && hipFuncSetAttribute((const void *)k_smo<TT, RR, TB>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                           (int)dyn) != hipSuccess) {                                           \
+        if (dyn > 0 && hipFuncSetAttribute((const void *)k_smo<TT, RR, TB, LIN>,                               \
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) { \
             (void)hipGetLastError();                                                                            \
             g_svm_err = "k_smo: the device refuses this launch shape (dynamic LDS)";                            \
             return GKMSVM_RC_SHAPE_REFUSED;                                                                     \
         }                                                                                                       \
-        hipLaunchKernelGGL((k_smo<TT, RR, TB>), dim3((unsigned)nprob), dim3(TT), dyn, stream, K, ld, diag, dprobs, C, \
-                           eps, max_iter);                                                                      \
+        hipLaunchKernelGGL((k_smo<TT, RR, TB, LIN>), dim3((unsigned)nprob), dim3(TT), dyn, stream, K, ld, diag,  \
+                           dprobs, C, eps, max_iter);                                                           \
     } else
     SMO_LAUNCH(256, 4, 1)
     SMO_LAUNCH(512, 4, 1)
@@ -1310,14 +1345,24 @@ extern "C" int gkmsvm_train_batch(int device, const double *K, int64_t ld, int n
     return 0;
 }
 
+extern "C" int gkmsvm_train_batch(int device, const double *K, int64_t ld, int n, int nprob, const int *idx,
+                                  const int64_t *off, const int *n0, double C, double eps, double *alpha, double *grad,
+                                  double *rho, int *iters, void *stream_)
+{
+    return train_batch<false>("gkmsvm_train_batch", device, K, ld, n, nprob, idx, off, n0, nullptr, C, eps, alpha, grad,
+                              rho, iters, stream_);
+}
+
 constexpr int GEN_MAX_L = 60000; /* one byte of LDS per sample for the shrinking flags */
 
-extern "C" int gkmsvm_train_batch_general(int device, const double *K, int64_t ld, int n, int nprob, const int *idx,
-                                          const int64_t *off, const int *n0, double C, double eps, int shrinking,
-                                          double *alpha, double *grad, double *rho, int *iters, void *stream_)
+template <bool LIN>
+static int train_batch_general(const char *name, int device, const double *K, int64_t ld, int n, int nprob,
+                               const int *idx, const int64_t *off, const int *n0, const double *lin, double C, double eps,
+                               int shrinking, double *alpha, double *grad, double *rho, int *iters, void *stream_)
 {
-    if (!K || n <= 0 || ld < n || nprob <= 0 || !idx || !off || !n0 || !alpha || !grad || !rho || !iters) {
-        g_svm_err = "gkmsvm_train_batch_general: bad arguments";
+    using Prob = std::conditional_t<LIN, GenProbLin, GenProb>;
+    if (!K || n <= 0 || ld < n || nprob <= 0 || !idx || !off || !n0 || !alpha || !grad || !rho || !iters || (LIN && !lin)) {
+        g_svm_err = std::string(name) + ": bad arguments";
         return 2;
     }
     hipStream_t stream = (hipStream_t)stream_;
@@ -1328,15 +1373,15 @@ extern "C" int gkmsvm_train_batch_general(int device, const double *K, int64_t l
         const int64_t l = off[p + 1] - off[p];
         if (l > maxl) maxl = l;
         if (l <= 0 || l > (int64_t)GEN_MAX_L || n0[p] < 0 || n0[p] > l) {
-            g_svm_err = "gkmsvm_train_batch_general: a problem has no samples or more than 60000";
+            g_svm_err = std::string(name) + ": a problem has no samples or more than 60000";
             return 3;
         }
     }
     /* scratch: 6 int, 5 double, 2 float arrays of `total` entries */
     const size_t per = 6 * sizeof(int) + 5 * sizeof(double) + 2 * sizeof(float);
-    const size_t state_bytes = align256(per * (size_t)total + 64), probs_bytes = align256(sizeof(GenProb) * (size_t)nprob);
+    const size_t state_bytes = align256(per * (size_t)total + 64), probs_bytes = align256(sizeof(Prob) * (size_t)nprob);
     SvmScratch *const scr = scratch_acquire(device, state_bytes + probs_bytes + sizeof(double) * (size_t)n);
-    if (!scr) { g_svm_err = "gkmsvm_train_batch_general: device scratch"; return 4; }
+    if (!scr) { g_svm_err = std::string(name) + ": device scratch"; return 4; }
     /* (error returns included: whatever this call enqueued may still be writing the buffer -- k_diag below -- and another
      * solver on another stream of the device may take it from the pool next) */
     struct Release { SvmScratch *b; hipStream_t s; ~Release() { (void)hipStreamSynchronize(s); scratch_release(b); } } release{scr, stream};
@@ -1344,7 +1389,7 @@ extern "C" int gkmsvm_train_batch_general(int device, const double *K, int64_t l
     double *d0 = (double *)scratch;
     int *i0 = (int *)(d0 + 5 * total);
     float *f0 = (float *)(i0 + 6 * total);
-    std::vector<GenProb> h((size_t)nprob);
+    std::vector<Prob> h((size_t)nprob);
     for (int p = 0; p < nprob; p++) {
         const int64_t o = off[p];
         GenProb &g = h[(size_t)p];
@@ -1354,10 +1399,11 @@ extern "C" int gkmsvm_train_batch_general(int device, const double *K, int64_t l
         g.gidx = i0 + o; g.ys = i0 + total + o; g.aset = i0 + 2 * total + o; g.swaps = i0 + 3 * total + o;
         g.fg = i0 + 4 * total + o; g.fy = i0 + 5 * total + o;
         g.Qi = f0 + o; g.Qj = f0 + total + o;
+        if constexpr (LIN) h[(size_t)p].lin = lin + o;
     }
-    GenProb *const dprobs = (GenProb *)(scratch + state_bytes);
+    Prob *const dprobs = (Prob *)(scratch + state_bytes);
     double *const diag = (double *)(scratch + state_bytes + probs_bytes);
-    hipError_t e = hipMemcpyAsync(dprobs, h.data(), sizeof(GenProb) * (size_t)nprob, hipMemcpyHostToDevice, stream);
+    hipError_t e = hipMemcpyAsync(dprobs, h.data(), sizeof(Prob) * (size_t)nprob, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream); /* h is a host temporary */
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_diag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, K, ld, n, diag);
@@ -1372,26 +1418,26 @@ extern "C" int gkmsvm_train_batch_general(int device, const double *K, int64_t l
         bool lds_state = gt == 512 && maxl <= GEN_LDS_L;
         if (const char *g = getenv("GKM_SVM_GEN_LDS")) lds_state = lds_state && atoi(g) != 0;
         size_t dyn = lds_state ? (size_t)18 * cap : (size_t)cap;
-        const void *fn = lds_state ? (const void *)k_smo_general<512, true>
-                         : gt == 512 ? (const void *)k_smo_general<512, false> : (const void *)k_smo_general<1024, false>;
+        const void *fn = lds_state ? (const void *)k_smo_general<512, true, LIN>
+                         : gt == 512 ? (const void *)k_smo_general<512, false, LIN> : (const void *)k_smo_general<1024, false, LIN>;
         e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
         if (e != hipSuccess && lds_state) { /* a device that refuses 147 KB of LDS: the state stays in global memory */
             (void)hipGetLastError();
             lds_state = false;
             dyn = (size_t)cap;
-            fn = (const void *)k_smo_general<512, false>;
+            fn = (const void *)k_smo_general<512, false, LIN>;
             e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
         }
         if (e == hipSuccess) {
             if (lds_state)
-                hipLaunchKernelGGL((k_smo_general<512, true>), dim3((unsigned)nprob), dim3(512), dyn, stream, K, ld, diag, dprobs, C,
-                                   eps, max_iter, shrinking ? 1 : 0, cap);
+                hipLaunchKernelGGL((k_smo_general<512, true, LIN>), dim3((unsigned)nprob), dim3(512), dyn, stream, K, ld, diag,
+                                   dprobs, C, eps, max_iter, shrinking ? 1 : 0, cap);
             else if (gt == 512)
-                hipLaunchKernelGGL((k_smo_general<512, false>), dim3((unsigned)nprob), dim3(512), dyn, stream, K, ld, diag, dprobs, C,
-                                   eps, max_iter, shrinking ? 1 : 0, cap);
+                hipLaunchKernelGGL((k_smo_general<512, false, LIN>), dim3((unsigned)nprob), dim3(512), dyn, stream, K, ld, diag,
+                                   dprobs, C, eps, max_iter, shrinking ? 1 : 0, cap);
             else
-                hipLaunchKernelGGL((k_smo_general<1024, false>), dim3((unsigned)nprob), dim3(1024), dyn, stream, K, ld, diag, dprobs,
-                                   C, eps, max_iter, shrinking ? 1 : 0, cap);
+                hipLaunchKernelGGL((k_smo_general<1024, false, LIN>), dim3((unsigned)nprob), dim3(1024), dyn, stream, K, ld,
+                                   diag, dprobs, C, eps, max_iter, shrinking ? 1 : 0, cap);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
@@ -1400,12 +1446,120 @@ extern "C" int gkmsvm_train_batch_general(int device, const double *K, int64_t l
     return 0;
 }
 
-extern "C" int gkmsvm_decision_batch(int device, const double *K, int64_t ld, int nprob, const int *idx,
-                                     const int64_t *off, const int *n0, const double *alpha, const double *rho,
-                                     const int *test_idx, const int64_t *test_off, double *dec, void *stream_)
+extern "C" int gkmsvm_train_batch_general(int device, const double *K, int64_t ld, int n, int nprob, const int *idx,
+                                          const int64_t *off, const int *n0, double C, double eps, int shrinking,
+                                          double *alpha, double *grad, double *rho, int *iters, void *stream_)
 {
-    if (!K || nprob <= 0 || !idx || !off || !n0 || !alpha || !rho || !test_idx || !test_off || !dec) {
-        g_svm_err = "gkmsvm_decision_batch: bad arguments";
+    return train_batch_general<false>("gkmsvm_train_batch_general", device, K, ld, n, nprob, idx, off, n0, nullptr, C,
+                                      eps, shrinking, alpha, grad, rho, iters, stream_);
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * epsilon-SVR (LIBSVM solve_epsilon_svr): problem p of l samples becomes 2l solver positions, all in the caller's order,
+ *   position k < l:  sample k, y = +1, p_k = epsilon - z_k
+ *   position l + k:  sample k, y = -1, p_{l+k} = epsilon + z_k
+ * (n0 = l; alpha = 0, G = p, box C everywhere), solved by k_smo / k_smo_general with LIN = true; then
+ * coef_k = alpha_k - alpha_{l+k}.  rho is the solver's, LIBSVM's own. */
+__global__ void k_svr_setup(const int64_t *__restrict__ off, const int *__restrict__ idx, const double *__restrict__ z,
+                            double epsilon, int *__restrict__ idx2, double *__restrict__ lin)
+{
+    const int64_t o = off[blockIdx.y], l = off[blockIdx.y + 1] - o;
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= l) return;
+    const int g = idx[o + k];
+    const double zk = z[o + k];
+    idx2[2 * o + k] = g;
+    idx2[2 * o + l + k] = g;
+    lin[2 * o + k] = epsilon - zk;
+    lin[2 * o + l + k] = epsilon + zk;
+}
+
+__global__ void k_svr_coef(const int64_t *__restrict__ off, const double *__restrict__ alpha2, double *__restrict__ coef)
+{
+    const int64_t o = off[blockIdx.y], l = off[blockIdx.y + 1] - o;
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= l) return;
+    coef[o + k] = alpha2[2 * o + k] - alpha2[2 * o + l + k];
+}
+
+template <bool GENERAL>
+static int train_svr(const char *name, int device, const double *K, int64_t ld, int n, int nprob, const int *idx,
+                     const int64_t *off, const double *z, double C, double epsilon, double tol, int shrinking,
+                     double *coef, double *rho, int *iters, void *stream_)
+{
+    if (!K || n <= 0 || ld < n || nprob <= 0 || nprob > 65535 || !idx || !off || !z || !coef || !rho || !iters) {
+        g_svm_err = std::string(name) + ": bad arguments";
+        return 2;
+    }
+    const int64_t lim = (GENERAL ? GEN_MAX_L : SVM_MAX_L) / 2;
+    std::vector<int64_t> off2((size_t)nprob + 1);
+    std::vector<int> n0((size_t)nprob);
+    int64_t maxl = 0;
+    for (int p = 0; p < nprob; p++) {
+        const int64_t l = off[p + 1] - off[p];
+        if (l <= 0 || l > lim) {
+            g_svm_err = std::string(name) + ": a problem has no samples or more than " + std::to_string(lim) +
+                        " (2l solver positions)";
+            return 3;
+        }
+        if (l > maxl) maxl = l;
+        off2[(size_t)p] = 2 * off[p];
+        n0[(size_t)p] = (int)l;
+    }
+    off2[(size_t)nprob] = 2 * off[nprob];
+    const int64_t total = off[nprob];
+    hipStream_t stream = (hipStream_t)stream_;
+    SVMCHK(hipSetDevice(device));
+    /* scratch: the problem offsets, the 2l index list, p, alpha and the gradient of every problem */
+    const size_t off_b = align256(sizeof(int64_t) * ((size_t)nprob + 1)), idx_b = align256(sizeof(int) * 2 * (size_t)total);
+    const size_t dbl_b = align256(sizeof(double) * 2 * (size_t)total);
+    SvmScratch *const scr = scratch_acquire(device, off_b + idx_b + 3 * dbl_b);
+    if (!scr) { g_svm_err = std::string(name) + ": device scratch"; return 4; }
+    struct Release { SvmScratch *b; hipStream_t s; ~Release() { (void)hipStreamSynchronize(s); scratch_release(b); } } release{scr, stream};
+    int64_t *const d_off = (int64_t *)scr->p;
+    int *const idx2 = (int *)(scr->p + off_b);
+    double *const lin = (double *)(scr->p + off_b + idx_b);
+    double *const alpha2 = (double *)(scr->p + off_b + idx_b + dbl_b);
+    double *const grad2 = (double *)(scr->p + off_b + idx_b + 2 * dbl_b);
+    SVMCHK(hipMemcpyAsync(d_off, off, sizeof(int64_t) * ((size_t)nprob + 1), hipMemcpyHostToDevice, stream));
+    const dim3 grid((unsigned)((maxl + 255) / 256), (unsigned)nprob);
+    hipLaunchKernelGGL(k_svr_setup, grid, dim3(256), 0, stream, d_off, idx, z, epsilon, idx2, lin);
+    SVMCHK(hipGetLastError());
+    const int rc = GENERAL ? train_batch_general<true>(name, device, K, ld, n, nprob, idx2, off2.data(), n0.data(), lin, C,
+                                                       tol, shrinking, alpha2, grad2, rho, iters, stream_)
+                           : train_batch<true>(name, device, K, ld, n, nprob, idx2, off2.data(), n0.data(), lin, C, tol,
+                                               alpha2, grad2, rho, iters, stream_);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_svr_coef, grid, dim3(256), 0, stream, d_off, alpha2, coef);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return svm_fail("k_svr_coef", e);
+    return 0;
+}
+
+extern "C" int gkmsvm_train_svr_batch(int device, const double *K, int64_t ld, int n, int nprob, const int *idx,
+                                      const int64_t *off, const double *z, double C, double epsilon, double tol,
+                                      double *coef, double *rho, int *iters, void *stream_)
+{
+    return train_svr<false>("gkmsvm_train_svr_batch", device, K, ld, n, nprob, idx, off, z, C, epsilon, tol, 0, coef, rho,
+                            iters, stream_);
+}
+
+extern "C" int gkmsvm_train_svr_batch_general(int device, const double *K, int64_t ld, int n, int nprob, const int *idx,
+                                              const int64_t *off, const double *z, double C, double epsilon, double tol,
+                                              int shrinking, double *coef, double *rho, int *iters, void *stream_)
+{
+    return train_svr<true>("gkmsvm_train_svr_batch_general", device, K, ld, n, nprob, idx, off, z, C, epsilon, tol,
+                           shrinking, coef, rho, iters, stream_);
+}
+
+template <bool SIGNED>
+static int decision_batch(const char *name, int device, const double *K, int64_t ld, int nprob, const int *idx,
+                          const int64_t *off, const int *n0, const double *alpha, const double *rho, const int *test_idx,
+                          const int64_t *test_off, double *dec, void *stream_)
+{
+    if (!K || nprob <= 0 || !idx || !off || (!SIGNED && !n0) || !alpha || !rho || !test_idx || !test_off || !dec) {
+        g_svm_err = std::string(name) + ": bad arguments";
         return 2;
     }
     hipStream_t stream = (hipStream_t)stream_;
@@ -1414,22 +1568,38 @@ extern "C" int gkmsvm_decision_batch(int device, const double *K, int64_t ld, in
     int maxtest = 0;
     for (int p = 0; p < nprob; p++) {
         const int nt = (int)(test_off[p + 1] - test_off[p]);
-        h[(size_t)p] = {idx + off[p], (int)(off[p + 1] - off[p]), n0[p], alpha + off[p], rho + p,
+        h[(size_t)p] = {idx + off[p], (int)(off[p + 1] - off[p]), SIGNED ? 0 : n0[p], alpha + off[p], rho + p,
                         test_idx + test_off[p], nt, dec + test_off[p]};
         if (nt > maxtest) maxtest = nt;
     }
     if (maxtest == 0) return 0;
     SvmScratch *const scr = scratch_acquire(device, sizeof(DecProb) * (size_t)nprob);
-    if (!scr) { g_svm_err = "gkmsvm_decision_batch: device scratch"; return 4; }
+    if (!scr) { g_svm_err = std::string(name) + ": device scratch"; return 4; }
     /* (error returns included: whatever this call enqueued may still be writing the buffer -- k_diag below -- and another
      * solver on another stream of the device may take it from the pool next) */
     struct Release { SvmScratch *b; hipStream_t s; ~Release() { (void)hipStreamSynchronize(s); scratch_release(b); } } release{scr, stream};
     DecProb *const dprobs = (DecProb *)scr->p;
     SVMCHK(hipMemcpyAsync(dprobs, h.data(), sizeof(DecProb) * (size_t)nprob, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(k_decision, dim3((unsigned)((maxtest + 127) / 128), (unsigned)nprob), dim3(128), 0, stream, K, ld,
-                       dprobs);
+    hipLaunchKernelGGL(k_decision<SIGNED>, dim3((unsigned)((maxtest + 127) / 128), (unsigned)nprob), dim3(128), 0, stream,
+                       K, ld, dprobs);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) return svm_fail("k_decision", e);
     return 0;
+}
+
+extern "C" int gkmsvm_decision_batch(int device, const double *K, int64_t ld, int nprob, const int *idx,
+                                     const int64_t *off, const int *n0, const double *alpha, const double *rho,
+                                     const int *test_idx, const int64_t *test_off, double *dec, void *stream_)
+{
+    return decision_batch<false>("gkmsvm_decision_batch", device, K, ld, nprob, idx, off, n0, alpha, rho, test_idx,
+                                 test_off, dec, stream_);
+}
+
+extern "C" int gkmsvm_decision_signed_batch(int device, const double *K, int64_t ld, int nprob, const int *idx,
+                                            const int64_t *off, const double *coef, const double *rho,
+                                            const int *test_idx, const int64_t *test_off, double *dec, void *stream_)
+{
+    return decision_batch<true>("gkmsvm_decision_signed_batch", device, K, ld, nprob, idx, off, nullptr, coef, rho,
+                                test_idx, test_off, dec, stream_);
 }

@@ -20,9 +20,14 @@ The other half of a gkm-SVM next to the cross-validation of `gkmsvm.py` (the cou
     `explain` folds its own;
   * `weights` folds a model (not RBF) into one weight per l-mer (gkmhip_lmer_weights) and writes that
     table; `predict-table` scores from it with only the queries uploaded: their self norms, then one gather per l-mer
-    (gkmhip_lmer_score) -- `predict`'s values up to rounding, for a fraction of the work.
+    (gkmhip_lmer_score) -- `predict`'s values up to rounding, for a fraction of the work;
+  * `train_svr` fits an epsilon-SVR to one real target per sequence: the same Gram matrix, LIBSVM's
+    2l-variable problem solved by the GPU solver with a linear term per position (svmcv.train_svr_folds); its model
+    scores through the signed decision (gkmsvm_decision_signed_batch) -- scikit-learn's `SVR.predict`, bit for bit --
+    and serves `explain`, `ism`, `hypothetical` and `weights` like a C-SVC model.
 
     python -m gkmqc_amd.gkmpredict train [-t -L -k -d -M -H -G -C -e -u] pos.fa neg.fa model.txt
+    python -m gkmqc_amd.gkmpredict train-svr [-t -L -k -d -M -H -G -C -p -e -u] seqs.fa targets.txt model.txt
     python -m gkmqc_amd.gkmpredict predict query.fa model.txt out.txt
     python -m gkmqc_amd.gkmpredict explain [--block Qb] query.fa model.txt out.txt
     python -m gkmqc_amd.gkmpredict ism [--block Qb] query.fa model.txt out.txt
@@ -42,9 +47,13 @@ from . import device as dv
 from . import svmcv
 
 FORMAT = "gkmqc-model-1"
+SVR_FORMAT = "gkmqc-svr-1"
+C_SVC, EPSILON_SVR = "c_svc", "epsilon_svr"
 _INT_KEYS = ("kernel_type", "L", "k", "d", "M", "shrinking", "n0", "n_sv")
-_FLOAT_KEYS = ("H", "gamma", "C", "tol", "rho")
+_FLOAT_KEYS = ("H", "gamma", "C", "tol", "rho", "epsilon")
 _KEYS = ("format", "kernel_type", "L", "k", "d", "M", "H", "gamma", "C", "tol", "shrinking", "rho", "n0", "n_sv")
+_SVR_KEYS = ("format", "kernel_type", "L", "k", "d", "M", "H", "gamma", "C", "tol", "shrinking", "epsilon", "rho", "n_sv")
+MAX_SVR_SAMPLES = svmcv.MAX_FOLD_SAMPLES // 2   # LIBSVM's epsilon-SVR solves 2l variables
 BLOCK_BYTES = 2 << 30     # device memory one block of queries may take: S x Qb kernel values + the kernel's own output
 _ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
 
@@ -68,10 +77,15 @@ def text_to_codes(text):
 
 
 class Model:
-    """A trained gkm-SVM: kernel and SVM parameters, rho, and the support vectors in LIBSVM's internal order (class 0 --
-    the negatives -- first, n0 of them), each with its alpha (> 0), FASTA name and base codes."""
+    """A trained gkm-SVM: kernel and SVM parameters, rho, and the support vectors, each with its FASTA name and base codes.
 
-    def __init__(self, kernel_type, L, k, d, M, H, gamma, C, tol, shrinking, rho, n0, alpha, names, seqs):
+    C-SVC (svm_type C_SVC): the support vectors in LIBSVM's internal order (class 0 -- the negatives -- first, n0 of
+    them), `alpha` their dual variables (> 0).  epsilon-SVR (svm_type EPSILON_SVR, `epsilon` set, n0 = 0): the support
+    vectors in training order, `alpha` their signed coefficients alpha_k - alpha*_k (nonzero).  For both,
+    score = sum dual_coef() K + rho: rho is scikit-learn's intercept_ (for SVR that is LIBSVM's rho negated)."""
+
+    def __init__(self, kernel_type, L, k, d, M, H, gamma, C, tol, shrinking, rho, n0, alpha, names, seqs, svm_type=C_SVC,
+                 epsilon=None):
         self.kernel_type, self.L, self.k, self.d, self.M = int(kernel_type), int(L), int(k), int(d), int(M)
         self.H, self.gamma, self.C, self.tol = float(H), float(gamma), float(C), float(tol)
         self.shrinking = bool(shrinking)
@@ -79,7 +93,13 @@ class Model:
         self.alpha = np.ascontiguousarray(alpha, dtype=np.float64)
         self.names = list(names)
         self.seqs = [np.ascontiguousarray(s, dtype=np.uint8) for s in seqs]
+        self.svm_type = svm_type
+        self.epsilon = None if epsilon is None else float(epsilon)
         _validate(self)
+
+    @property
+    def is_svr(self):
+        return self.svm_type == EPSILON_SVR
 
     @property
     def n_sv(self):
@@ -89,15 +109,21 @@ class Model:
         return (self.kernel_type, self.L, self.k, self.d, self.M, self.H, self.gamma)
 
     def dual_coef(self):
-        """scikit-learn's `dual_coef_[0]` (labels 0 / 1: class 0 first with a negative sign)."""
+        """scikit-learn's `dual_coef_[0]` (C-SVC, labels 0 / 1: class 0 first with a negative sign; SVR: the signed
+        coefficients as stored)."""
+        if self.is_svr:
+            return self.alpha.copy()
         return np.where(np.arange(self.n_sv) < self.n0, -self.alpha, self.alpha)
 
     def save(self, path):
         """Write the model file (format: INTEGRATION.md).  Floats as repr(), which reads back to the same double."""
-        head = [("format", FORMAT), ("kernel_type", self.kernel_type), ("L", self.L), ("k", self.k), ("d", self.d),
-                ("M", self.M), ("H", repr(self.H)), ("gamma", repr(self.gamma)), ("C", repr(self.C)),
-                ("tol", repr(self.tol)), ("shrinking", int(self.shrinking)), ("rho", repr(self.rho)), ("n0", self.n0),
-                ("n_sv", self.n_sv)]
+        head = [("format", SVR_FORMAT if self.is_svr else FORMAT), ("kernel_type", self.kernel_type), ("L", self.L),
+                ("k", self.k), ("d", self.d), ("M", self.M), ("H", repr(self.H)), ("gamma", repr(self.gamma)),
+                ("C", repr(self.C)), ("tol", repr(self.tol)), ("shrinking", int(self.shrinking))]
+        if self.is_svr:
+            head += [("epsilon", repr(self.epsilon)), ("rho", repr(self.rho)), ("n_sv", self.n_sv)]
+        else:
+            head += [("rho", repr(self.rho)), ("n0", self.n0), ("n_sv", self.n_sv)]
         tmp = path + ".tmp"
         with open(tmp, "w") as f:
             for key, val in head:
@@ -118,10 +144,22 @@ def _validate(m):
         raise ModelError("H, gamma and rho must be finite, C and tol positive")
     if not (len(m.alpha) == len(m.names) == len(m.seqs)) or len(m.alpha) == 0:
         raise ModelError("a model needs at least one support vector, each with alpha, name and sequence")
-    if not 0 <= m.n0 <= len(m.alpha):
-        raise ModelError("n0 must lie in 0..n_sv")
-    if not (np.isfinite(m.alpha).all() and (m.alpha > 0).all()):
-        raise ModelError("every alpha must be positive and finite")
+    if m.svm_type == EPSILON_SVR:
+        if m.epsilon is None or not (np.isfinite(m.epsilon) and m.epsilon >= 0):
+            raise ModelError("an SVR model needs a finite epsilon >= 0")
+        if m.n0 != 0:
+            raise ModelError("an SVR model has no classes (n0 = 0)")
+        if not (np.isfinite(m.alpha).all() and (m.alpha != 0).all()):
+            raise ModelError("every SVR coefficient must be nonzero and finite")
+    elif m.svm_type == C_SVC:
+        if m.epsilon is not None:
+            raise ModelError("a C-SVC model has no epsilon")
+        if not 0 <= m.n0 <= len(m.alpha):
+            raise ModelError("n0 must lie in 0..n_sv")
+        if not (np.isfinite(m.alpha).all() and (m.alpha > 0).all()):
+            raise ModelError("every alpha must be positive and finite")
+    else:
+        raise ModelError("unknown SVM type %r" % (m.svm_type,))
     if any(len(s) < m.L for s in m.seqs):
         raise ModelError("a stored sequence is shorter than L")
     if any("\n" in nm or "\r" in nm for nm in m.names):
@@ -129,7 +167,8 @@ def _validate(m):
 
 
 def load(path):
-    """Read a model file written by Model.save; anything malformed raises ModelError with the reason."""
+    """Read a model file written by Model.save (either format tag); anything malformed raises ModelError with the
+    reason."""
     with open(path) as f:
         lines = f.read().split("\n")
     if lines and lines[-1] == "":
@@ -137,7 +176,7 @@ def load(path):
     head, i = {}, 0
     while i < len(lines) and lines[i] != "SV":
         parts = lines[i].split(" ", 1)
-        if len(parts) != 2 or parts[0] not in _KEYS:
+        if len(parts) != 2 or parts[0] not in _KEYS + _SVR_KEYS:
             raise ModelError("%s:%d: not a `key value` line of the header: %r" % (path, i + 1, lines[i]))
         if parts[0] in head:
             raise ModelError("%s:%d: key %s given twice" % (path, i + 1, parts[0]))
@@ -145,14 +184,19 @@ def load(path):
         i += 1
     if i == len(lines):
         raise ModelError("%s: no SV line" % path)
-    missing = [key for key in _KEYS if key not in head]
+    svr = head.get("format") == SVR_FORMAT
+    keys = _SVR_KEYS if svr else _KEYS
+    missing = [key for key in keys if key not in head]
     if missing:
         raise ModelError("%s: missing key(s): %s" % (path, ", ".join(missing)))
-    if head["format"] != FORMAT:
-        raise ModelError("%s: format %r, expected %r" % (path, head["format"], FORMAT))
+    if head["format"] not in (FORMAT, SVR_FORMAT):
+        raise ModelError("%s: format %r, expected %r or %r" % (path, head["format"], FORMAT, SVR_FORMAT))
+    extra = [key for key in head if key not in keys]
+    if extra:
+        raise ModelError("%s: key(s) %s do not belong to format %s" % (path, ", ".join(extra), head["format"]))
     try:
-        val = {key: int(head[key]) for key in _INT_KEYS}
-        val.update({key: float(head[key]) for key in _FLOAT_KEYS})
+        val = {key: int(head[key]) for key in _INT_KEYS if key in keys}
+        val.update({key: float(head[key]) for key in _FLOAT_KEYS if key in keys})
     except ValueError as e:
         raise ModelError("%s: %s" % (path, e))
     body = lines[i + 1:]
@@ -163,13 +207,16 @@ def load(path):
         parts = line.split("\t", 1)
         rest = parts[1].rsplit("\t", 1) if len(parts) == 2 else []
         if len(rest) != 2:
-            raise ModelError("%s:%d: expected alpha<TAB>name<TAB>sequence" % (path, i + 2 + j))
+            raise ModelError("%s:%d: expected %s<TAB>name<TAB>sequence" % (path, i + 2 + j, "coef" if svr else "alpha"))
         try:
             alpha[j] = float(parts[0])
             seqs.append(text_to_codes(rest[1]))
         except ValueError as e:
             raise ModelError("%s:%d: %s" % (path, i + 2 + j, e))
         names.append(rest[0])
+    if svr:
+        return Model(val["kernel_type"], val["L"], val["k"], val["d"], val["M"], val["H"], val["gamma"], val["C"],
+                     val["tol"], val["shrinking"], val["rho"], 0, alpha, names, seqs, EPSILON_SVR, val["epsilon"])
     return Model(val["kernel_type"], val["L"], val["k"], val["d"], val["M"], val["H"], val["gamma"], val["C"], val["tol"],
                  val["shrinking"], val["rho"], val["n0"], alpha, names, seqs)
 
@@ -208,6 +255,79 @@ def train(pos_fa, neg_fa, kernel_type=4, L=10, k=6, d=3, M=50, H=50, gamma=1.0, 
     torch.cuda.empty_cache()
     return Model(kernel_type, L, k, d, M, H, gamma, C, tol, shrinking, rho, int((y[idx] == 0).sum()), alpha,
                  [names[i] for i in idx], [seqs[i] for i in idx])
+
+
+def read_targets(path, names):
+    """The targets file of `train_svr`: one name<TAB>value line per FASTA record, in FASTA order (split at the LAST tab:
+    names may hold tabs).  names: the headers the FASTA reader returned.  -> float64 array; a count or name mismatch, a
+    value that is not a finite float, raises ModelError with the line number."""
+    with open(path) as f:
+        lines = f.read().split("\n")
+    if lines and lines[-1] == "":
+        lines.pop()
+    z = np.empty(len(names))
+    for j, line in enumerate(lines):
+        if j >= len(names):
+            raise ModelError("%s:%d: more target lines than FASTA records (%d)" % (path, j + 1, len(names)))
+        parts = line.rsplit("\t", 1)
+        if len(parts) != 2:
+            raise ModelError("%s:%d: expected name<TAB>value" % (path, j + 1))
+        if parts[0] != names[j]:
+            raise ModelError("%s:%d: name %r, but FASTA record %d is %r" % (path, j + 1, parts[0], j + 1, names[j]))
+        try:
+            z[j] = float(parts[1])
+        except ValueError:
+            raise ModelError("%s:%d: %r is not a number" % (path, j + 1, parts[1]))
+        if not np.isfinite(z[j]):
+            raise ModelError("%s:%d: the value must be finite, not %r" % (path, j + 1, parts[1]))
+    if len(lines) < len(names):
+        raise ModelError("%s:%d: no target for FASTA record %d (%r): %d lines for %d records"
+                         % (path, len(lines) + 1, len(lines) + 1, names[len(lines)], len(lines), len(names)))
+    return z
+
+
+def train_svr(fasta, targets, kernel_type=4, L=10, k=6, d=3, M=50, H=50, gamma=1.0, C=1.0, epsilon=0.1, tol=1e-3,
+              shrinking=False, device=0, kernel=dv.KERNEL_AUTO):
+    """One epsilon-SVR on every sequence of `fasta` with `targets` (a targets file, see read_targets, or a sequence of
+    floats in FASTA order) -> Model (svm_type EPSILON_SVR): scikit-learn's SVR(kernel="precomputed") on the same matrix,
+    bit for bit (the GPU solver; scikit-learn if it stops at its iteration cap).  At most MAX_SVR_SAMPLES sequences.
+    The model's `n_iter` holds the solver's iteration count (not stored in the file)."""
+    import torch
+    bad = dv.check_parameters(kernel_type, L, k, d)
+    if bad:
+        raise ModelError("kernel parameters rejected: %s" % bad)
+    if not (np.isfinite(epsilon) and epsilon >= 0):
+        raise ModelError("epsilon must be finite and at least 0")
+    if not (C > 0 and tol > 0):
+        raise ModelError("C and tol must be positive")
+    seqs, names, _, _ = dv.read_fasta(fasta)
+    n = len(seqs)
+    if n == 0:
+        raise ModelError("training needs at least one sequence")
+    if n > MAX_SVR_SAMPLES:
+        raise ModelError("epsilon-SVR takes at most %d sequences (2l solver variables), not %d" % (MAX_SVR_SAMPLES, n))
+    if isinstance(targets, (str, bytes, os.PathLike)):
+        z = read_targets(targets, names)
+    else:
+        z = np.asarray(targets, dtype=np.float64).reshape(-1)
+        if len(z) != n:
+            raise ModelError("%d targets for %d sequences" % (len(z), n))
+        if not np.isfinite(z).all():
+            raise ModelError("every target must be finite")
+    res = dv.gram_matrix(seqs, kernel_type, L, k, d, M, H, gamma, device, kernel=kernel, symmetric=True,
+                         keep_context=True)
+    K = res["K"]
+    sol = svmcv.train_svr_folds(K, [np.arange(n)], z, C, epsilon, tol, shrinking)
+    del K, res
+    torch.cuda.empty_cache()
+    sv = sol.support[0]
+    if len(sv) == 0:
+        raise ModelError("no support vectors: every target lies within epsilon = %r of the intercept %r; use a smaller "
+                         "epsilon (-p)" % (float(epsilon), float(sol.intercept[0])))
+    m = Model(kernel_type, L, k, d, M, H, gamma, C, tol, shrinking, sol.intercept[0], 0, sol.dual_coef[0],
+              [names[i] for i in sv], [seqs[i] for i in sv], EPSILON_SVR, epsilon)
+    m.n_iter = int(sol.iters[0])
+    return m
 
 
 # ------------------------------------------------------------------ scoring
@@ -269,7 +389,8 @@ def _score_flat(model, seqs, device, block, kernel, on_block):
         sq = torch.empty(S + qb_max, dtype=torch.float64, device=dev)
         d_idx = torch.from_numpy(rows).to(dev)
         d_alpha = torch.from_numpy(model.alpha).to(dev)
-        d_rho = torch.tensor([model.rho], dtype=torch.float64, device=dev)
+        # (SVR: LIBSVM's rho, which scikit-learn's predict takes as -intercept_)
+        d_rho = torch.tensor([-model.rho if model.is_svr else model.rho], dtype=torch.float64, device=dev)
         d_test = torch.arange(qb_max, dtype=torch.int32, device=dev)
         d_dec = torch.empty(qb_max, dtype=torch.float64, device=dev)
         off_sv = np.array([0, S], dtype=np.int64)
@@ -293,13 +414,22 @@ def _score_flat(model, seqs, device, block, kernel, on_block):
             if on_block is not None:
                 torch.cuda.current_stream().synchronize()
             t3 = time.perf_counter()
-            rc = lib.gkmsvm_decision_batch(device, G.data_ptr(), qb_max, 1, d_idx.data_ptr(), off_sv.ctypes.data,
-                                           n0.ctypes.data, d_alpha.data_ptr(), d_rho.data_ptr(), d_test.data_ptr(),
-                                           np.array([0, qb], dtype=np.int64).ctypes.data, d_dec.data_ptr(), stream)
-            if rc:
-                raise svmcv.SvmError("gkmsvm_decision_batch: %s" % lib.gkmsvm_last_error().decode())
-            # LIBSVM's decision value for labels (0, 1) has the opposite sign of scikit-learn's
-            out[q0:q1] = -d_dec[:qb].cpu().numpy()
+            if model.is_svr:   # scikit-learn's SVR.predict: the signed sum in support-vector order, minus rho
+                rc = lib.gkmsvm_decision_signed_batch(device, G.data_ptr(), qb_max, 1, d_idx.data_ptr(),
+                                                      off_sv.ctypes.data, d_alpha.data_ptr(), d_rho.data_ptr(),
+                                                      d_test.data_ptr(), np.array([0, qb], dtype=np.int64).ctypes.data,
+                                                      d_dec.data_ptr(), stream)
+                if rc:
+                    raise svmcv.SvmError("gkmsvm_decision_signed_batch: %s" % lib.gkmsvm_last_error().decode())
+                out[q0:q1] = d_dec[:qb].cpu().numpy()
+            else:
+                rc = lib.gkmsvm_decision_batch(device, G.data_ptr(), qb_max, 1, d_idx.data_ptr(), off_sv.ctypes.data,
+                                               n0.ctypes.data, d_alpha.data_ptr(), d_rho.data_ptr(), d_test.data_ptr(),
+                                               np.array([0, qb], dtype=np.int64).ctypes.data, d_dec.data_ptr(), stream)
+                if rc:
+                    raise svmcv.SvmError("gkmsvm_decision_batch: %s" % lib.gkmsvm_last_error().decode())
+                # LIBSVM's decision value for labels (0, 1) has the opposite sign of scikit-learn's
+                out[q0:q1] = -d_dec[:qb].cpu().numpy()
             t4 = time.perf_counter()
             if on_block is not None:
                 on_block(dict(queries=qb, upload_ms=(t1 - t0) * 1e3, norms_gram_ms=(t2 - t1) * 1e3, gram_kernel_ms=gram_ms,
@@ -888,6 +1018,23 @@ def build_parser():
     t.add_argument("pos_fa")
     t.add_argument("neg_fa")
     t.add_argument("model")
+    v = sub.add_parser("train-svr", help="fit an epsilon-SVR to seqs.fa and targets.txt (name<TAB>value per record) "
+                                         "and write a model file")
+    v.add_argument("-t", "--kernel-type", type=int, default=4, help="kernel type 0..5 (default: 4)")
+    v.add_argument("-L", "--full-word-length", type=int, default=10, help="full word length (default: 10)")
+    v.add_argument("-k", "--non-gap-length", type=int, default=6, help="non-gap positions (default: 6)")
+    v.add_argument("-d", "--max-num-gaps", type=int, default=3, help="max gaps (default: 3)")
+    v.add_argument("-M", "--init-decay", type=int, default=50, help="initial value of the decay, -t 4/5 (default: 50)")
+    v.add_argument("-H", "--half-life-decay", type=float, default=50, help="half life of the decay, -t 4/5 (default: 50)")
+    v.add_argument("-G", "--rbf-gamma", type=float, default=1.0, help="gamma for RBF kernels, -t 3/5 (default: 1.0)")
+    v.add_argument("-C", "--regularization", type=float, default=1.0, help="regularization parameter C (default: 1.0)")
+    v.add_argument("-p", "--epsilon", type=float, default=0.1, help="epsilon of the insensitive loss (default: 0.1)")
+    v.add_argument("-e", "--precision", type=float, default=0.001, help="precision parameter epsilon (default: 0.001)")
+    v.add_argument("-u", "--shrinking", type=int, choices=(0, 1), default=0, help="shrinking heuristics (default: 0)")
+    v.add_argument("--device", type=int, default=0, help="GPU (default: 0)")
+    v.add_argument("seqs_fa")
+    v.add_argument("targets")
+    v.add_argument("model")
     q = sub.add_parser("predict", help="score the sequences of query.fa: name<TAB>score per line, in file order")
     q.add_argument("--device", type=int, default=0, help="GPU (default: 0)")
     q.add_argument("--block", type=int, default=None, help="queries per device block (default: from device memory)")
@@ -938,6 +1085,8 @@ def check_train_args(a):
         return "-M must lie in 0..255"
     if not (a.regularization > 0 and a.precision > 0):
         return "-C and -e must be positive"
+    if a.cmd == "train-svr" and not (np.isfinite(a.epsilon) and a.epsilon >= 0):
+        return "-p must be finite and at least 0"
     return None
 
 
@@ -957,6 +1106,19 @@ def main(argv=None):
             m.save(a.model)
             print("%d support vectors (%d negative, %d positive), rho %r -> %s"
                   % (m.n_sv, m.n0, m.n_sv - m.n0, m.rho, a.model), file=sys.stderr)
+        elif a.cmd == "train-svr":
+            bad = check_train_args(a)
+            if bad:
+                raise ModelError(bad)
+            for path in (a.seqs_fa, a.targets):
+                if not os.path.isfile(path):
+                    raise ModelError("cannot read %s" % path)
+            m = train_svr(a.seqs_fa, a.targets, a.kernel_type, a.full_word_length, a.non_gap_length, a.max_num_gaps,
+                          a.init_decay, a.half_life_decay, a.rbf_gamma, a.regularization, a.epsilon, a.precision,
+                          bool(a.shrinking), a.device)
+            m.save(a.model)
+            print("%d support vectors, rho %r (LIBSVM's: %r), %d iterations -> %s"
+                  % (m.n_sv, m.rho, -m.rho, m.n_iter, a.model), file=sys.stderr)
         elif a.cmd == "weights":
             m = load(a.model)
             check_table_model(m)

@@ -38,6 +38,12 @@ def _lib():
         L.gkmsvm_train_batch_general.argtypes = (i32, vp, i64, i32, i32, vp, vp, vp, dbl, dbl, i32, vp, vp, vp, vp, vp)
         L.gkmsvm_decision_batch.restype = i32
         L.gkmsvm_decision_batch.argtypes = (i32, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp)
+        L.gkmsvm_train_svr_batch.restype = i32
+        L.gkmsvm_train_svr_batch.argtypes = (i32, vp, i64, i32, i32, vp, vp, vp, dbl, dbl, dbl, vp, vp, vp, vp)
+        L.gkmsvm_train_svr_batch_general.restype = i32
+        L.gkmsvm_train_svr_batch_general.argtypes = (i32, vp, i64, i32, i32, vp, vp, vp, dbl, dbl, dbl, i32, vp, vp, vp, vp)
+        L.gkmsvm_decision_signed_batch.restype = i32
+        L.gkmsvm_decision_signed_batch.argtypes = (i32, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp)
         L.gkmsvm_last_error.restype = ctypes.c_char_p
         L.gkmsvm_release_cache.restype = None
         L._svm_bound = True
@@ -152,6 +158,118 @@ def decision_values(K, handles, tests):
         dec = d_dec.cpu().numpy()
     # sklearn flips the sign of LIBSVM's decision value for a two-class problem
     return [-dec[toff[f]:toff[f + 1]] for f in range(len(tests))]
+
+
+class SvrSolutions:
+    """Result of `train_svr_folds`, per problem: scikit-learn's `support_` (positions in the problem's `train`, ascending),
+    `dual_coef_[0]` (alpha_k - alpha_{l+k}, nonzero), `intercept_[0]` (LIBSVM's rho negated) and the iteration count
+    (negative: the GPU solver stopped at its cap and scikit-learn re-solved the problem)."""
+
+    def __init__(self, trains, support, dual_coef, intercept, iters):
+        self.trains, self.support, self.dual_coef = trains, support, dual_coef
+        self.intercept, self.iters = intercept, iters
+
+
+def _intercept(rho):
+    """scikit-learn's intercept_ from LIBSVM's rho (its copy_intercept: -rho, and +0.0 for a zero rho)"""
+    return -rho if rho != 0 else 0.0
+
+
+def train_svr_folds(K, trains, z, C=1.0, epsilon=0.1, tol=1e-3, shrinking=False):
+    """Solve one epsilon-SVR per entry of `trains` (index arrays into the symmetric torch CUDA fp64 matrix K) with
+    targets z (indexed like the rows of K) concurrently -> SvrSolutions.  LIBSVM's solve_epsilon_svr: 2l solver
+    positions per problem, so the solver choice counts 2l -- k_smo up to FAST_FOLD_SAMPLES without shrinking, the
+    general solver (k_smo_general) up to MAX_FOLD_SAMPLES.  A problem that stops at the iteration cap is re-solved with
+    scikit-learn's SVR."""
+    import torch
+    if not (K.is_cuda and K.dtype == torch.float64 and K.dim() == 2 and K.shape[0] == K.shape[1]
+            and K.stride(1) == 1):
+        raise SvmError("K must be a square fp64 CUDA tensor with unit column stride")
+    trains = [np.asarray(t, dtype=np.int64) for t in trains]
+    z = np.asarray(z, dtype=np.float64)
+    if not trains or min(len(t) for t in trains) == 0:
+        raise SvmError("a problem needs at least one sample")
+    if max(2 * len(t) for t in trains) > MAX_FOLD_SAMPLES:
+        raise SvmError("a problem has more than %d samples (2l solver positions > %d)"
+                       % (MAX_FOLD_SAMPLES // 2, MAX_FOLD_SAMPLES))
+    if not np.isfinite(z[np.concatenate(trains)]).all():
+        raise SvmError("targets must be finite")
+    L = _lib()
+    dev = K.device
+    off = np.zeros(len(trains) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(t) for t in trains])
+    idx = np.concatenate(trains).astype(np.int32)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        d_idx = torch.from_numpy(idx).to(dev)
+        d_z = torch.from_numpy(np.ascontiguousarray(z[idx])).to(dev)
+        d_coef = torch.empty(int(off[-1]), dtype=torch.float64, device=dev)
+        d_rho = torch.empty(len(trains), dtype=torch.float64, device=dev)
+        d_it = torch.empty(len(trains), dtype=torch.int32, device=dev)
+        args = (dev.index or 0, K.data_ptr(), K.stride(0), K.shape[0], len(trains), d_idx.data_ptr(), off.ctypes.data,
+                d_z.data_ptr(), float(C), float(epsilon), float(tol))
+        outs = (d_coef.data_ptr(), d_rho.data_ptr(), d_it.data_ptr(), stream)
+        if shrinking or 2 * max(len(t) for t in trains) > FAST_FOLD_SAMPLES:
+            rc = L.gkmsvm_train_svr_batch_general(*args, 1 if shrinking else 0, *outs)
+        else:
+            rc = L.gkmsvm_train_svr_batch(*args, *outs)
+            if rc == SHAPE_REFUSED:   # as train_folds: only a launch shape the device refuses is retried
+                first = L.gkmsvm_last_error().decode()
+                logging.warning("k_smo: %s: solving with the general GPU solver", first)
+                rc = L.gkmsvm_train_svr_batch_general(*args, 0, *outs)
+                if rc:
+                    raise SvmError("gkmsvm_train_svr_batch: %s; then gkmsvm_train_svr_batch_general: %s"
+                                   % (first, L.gkmsvm_last_error().decode()))
+        if rc:
+            raise SvmError("gkmsvm_train_svr_batch: %s" % L.gkmsvm_last_error().decode())
+        coef = d_coef.cpu().numpy()
+        rho = d_rho.cpu().numpy()
+        iters = d_it.cpu().numpy()
+    support, dual, intercept = [], [], np.zeros(len(trains))
+    for f in range(len(trains)):
+        c = coef[off[f]:off[f + 1]]
+        sv = np.nonzero(c != 0)[0]       # LIBSVM: fabs(alpha) > 0
+        support.append(sv)
+        dual.append(c[sv])
+        intercept[f] = _intercept(float(rho[f]))
+    capped = [f for f in range(len(trains)) if iters[f] < 0]
+    if capped:   # scikit-learn (max_iter=-1) would have kept iterating: re-solve these problems with it
+        from sklearn.svm import SVR
+        logging.warning("%d SVR problem(s) re-solved with scikit-learn (iteration cap of the GPU solver)", len(capped))
+        for f in capped:
+            tr = trains[f]
+            m = SVR(kernel="precomputed", C=C, epsilon=epsilon, tol=tol, shrinking=bool(shrinking))
+            m.fit(device_block(K, tr, tr).cpu().numpy(), z[tr])
+            support[f], dual[f], intercept[f] = m.support_.astype(np.int64), m.dual_coef_[0].copy(), m.intercept_[0]
+    return SvrSolutions(trains, support, dual, intercept, iters)
+
+
+def svr_predict(K, sol, tests):
+    """scikit-learn's `SVR.predict` of every problem of `sol` (SvrSolutions) on its test samples (index arrays into K):
+    the signed decision k_decision<true>, sum_k dual_coef_k K(t, sv_k) in support-vector order minus rho."""
+    import torch
+    L = _lib()
+    dev = K.device
+    off = np.zeros(len(tests) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(s) for s in sol.support])
+    toff = np.zeros(len(tests) + 1, dtype=np.int64)
+    toff[1:] = np.cumsum([len(t) for t in tests])
+    # (one padding entry past the last problem: the arrays are never empty, even when no problem has a support vector)
+    rows = np.concatenate([sol.trains[f][sol.support[f]] for f in range(len(tests))] + [[0]]).astype(np.int32)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        d_idx = torch.from_numpy(rows).to(dev)
+        d_coef = torch.from_numpy(np.concatenate(list(sol.dual_coef) + [[0.0]]).astype(np.float64)).to(dev)
+        d_rho = torch.from_numpy(-np.asarray(sol.intercept, dtype=np.float64)).to(dev)    # scikit-learn's rho = -intercept_
+        d_test = torch.from_numpy(np.concatenate(tests).astype(np.int32)).to(dev)
+        d_dec = torch.empty(int(toff[-1]), dtype=torch.float64, device=dev)
+        rc = L.gkmsvm_decision_signed_batch(dev.index or 0, K.data_ptr(), K.stride(0), len(tests), d_idx.data_ptr(),
+                                            off.ctypes.data, d_coef.data_ptr(), d_rho.data_ptr(), d_test.data_ptr(),
+                                            toff.ctypes.data, d_dec.data_ptr(), stream)
+        if rc:
+            raise SvmError("gkmsvm_decision_signed_batch: %s" % L.gkmsvm_last_error().decode())
+        dec = d_dec.cpu().numpy()
+    return [dec[toff[f]:toff[f + 1]] for f in range(len(tests))]
 
 
 def device_block(K, rows, cols):

@@ -72,6 +72,38 @@ int gkmsvm_decision_batch(int device, const double *K, int64_t ld, int nprob, co
                           const int *n0, const double *alpha, const double *rho, const int *test_idx,
                           const int64_t *test_off, double *dec, void *stream);
 
+/*
+ * epsilon-SVR (LIBSVM solve_epsilon_svr; scikit-learn SVR(kernel="precomputed")) on the same solvers: each problem of l
+ * samples is solved as LIBSVM's 2l-variable problem -- position k < l is sample k with y = +1 and linear term
+ * p_k = epsilon - z_k, position l + k the same sample with y = -1 and p_{l+k} = epsilon + z_k (p in fp64 exactly so), alpha
+ * starting at 0, box C everywhere.  The entries build that problem themselves (device scratch from the pool).
+ *   idx          concatenated training indices (into K) of all problems, each in the caller's order (no reordering)
+ *   off[nprob+1] HOST array: offsets of the problems into idx / z / coef
+ *   z            device, same layout as idx: the targets
+ *   C, epsilon, tol   box constraint, tube half-width, stopping tolerance (scikit-learn `C`, `epsilon`, `tol`)
+ *   coef         out, device, same layout as idx: alpha_k - alpha_{l+k} (scikit-learn's dual_coef_ where nonzero)
+ *   rho          out, device, nprob doubles: LIBSVM's rho (scikit-learn's intercept_ is -rho)
+ *   iters        out, device: as for gkmsvm_train_batch (negative at the iteration cap)
+ * gkmsvm_train_svr_batch runs k_smo (2l <= 16 384, no shrinking; GKMSVM_RC_SHAPE_REFUSED as gkmsvm_train_batch),
+ * gkmsvm_train_svr_batch_general runs k_smo_general (2l <= 60 000, with or without shrinking).  The environment knobs of
+ * the C-SVC entries apply.
+ */
+int gkmsvm_train_svr_batch(int device, const double *K, int64_t ld, int n, int nprob, const int *idx, const int64_t *off,
+                           const double *z, double C, double epsilon, double tol, double *coef, double *rho, int *iters,
+                           void *stream);
+int gkmsvm_train_svr_batch_general(int device, const double *K, int64_t ld, int n, int nprob, const int *idx,
+                                   const int64_t *off, const double *z, double C, double epsilon, double tol,
+                                   int shrinking, double *coef, double *rho, int *iters, void *stream);
+
+/*
+ * The signed decision of an SVR: dec[t] = sum_{k in order, coef_k != 0} coef_k K(test_t, sv_k) - rho, the additions
+ * sequential from +0.0 (scikit-learn's SVR.predict, bit for bit, with rho = -intercept_).  Arguments as for
+ * gkmsvm_decision_batch, with the signed coefficients in place of alpha and no n0.
+ */
+int gkmsvm_decision_signed_batch(int device, const double *K, int64_t ld, int nprob, const int *idx, const int64_t *off,
+                                 const double *coef, const double *rho, const int *test_idx, const int64_t *test_off,
+                                 double *dec, void *stream);
+
 const char *gkmsvm_last_error(void);
 
 /* The calls above keep their device scratch (problem descriptors, the matrix diagonal, the general solver's state) in a
