@@ -174,8 +174,7 @@ extern "C" void gkmhip_destroy(gkmhip_ctx *ctx)
     ctx->len.release(); ctx->lmf.release(); ctx->sb.release(); ctx->colpk.release(); ctx->postab.release();
     for (auto &scr : ctx->scratch) scr.release();
     ctx->sq.release();
-    ctx->ex_rows.release(); ctx->ex_part.release();
-    ctx->ism_rows.release(); ctx->ism_part.release(); ctx->ism_gpart.release(); ctx->ism_pself.release();
+    ctx->blk_rows.release(); ctx->blk_part.release(); ctx->ism_gpart.release(); ctx->ism_pself.release();
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     for (auto &pr : ctx->tl_pairs) {
@@ -412,6 +411,45 @@ int ensure_lmers(gkmhip_ctx *ctx, hipStream_t stream, bool wait)
     HIPCHK(hipGetLastError());
     if (wait) HIPCHK(hipStreamSynchronize(stream)); /* complete before any OTHER stream may read the table */
     ctx->have_lmers = true;
+    return 0;
+}
+
+/* ------------------------------------------ the prologue of a launch over (row list) x (column range) */
+int check_range(const gkmhip_ctx *ctx, int col_begin, int col_end, const char *what)
+{
+    if (ctx->n <= 0) return set_err_msg(std::string(what) + ": no sequences uploaded", 2);
+    if (col_begin < 0 || col_end > ctx->n || col_begin >= col_end)
+        return set_err_msg(std::string(what) + ": the column range must satisfy 0 <= col_begin < col_end <= n", 2);
+    return 0;
+}
+
+int check_rows(const gkmhip_ctx *ctx, const int *rows, int nrows, double *row_lmers)
+{
+    double lmers = 0;
+    for (int i = 0; i < nrows; i++) {
+        if (rows[i] < 0 || rows[i] >= ctx->n || (i > 0 && rows[i] <= rows[i - 1]))
+            return set_err_msg("rows must be strictly ascending sequence indices", 2);
+        lmers += (double)(ctx->h_len[(size_t)rows[i]] - ctx->L + 1);
+    }
+    *row_lmers = lmers;
+    return 0;
+}
+
+void scan_range(const gkmhip_ctx *ctx, int col_begin, int col_end, int *tmax, int64_t *bases)
+{
+    *tmax = 0;
+    *bases = 0;
+    for (int j = col_begin; j < col_end; j++) {
+        *tmax = std::max(*tmax, ctx->h_len[(size_t)j]);
+        *bases += ctx->h_len[(size_t)j];
+    }
+}
+
+int upload_rows(gkmhip_ctx *ctx, const int *rows, int nrows, hipStream_t stream)
+{
+    if (ctx->blk_rows.ensure((size_t)nrows)) return 4;
+    HIPCHK(hipMemcpyAsync(ctx->blk_rows.p, rows, (size_t)nrows * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream)); /* `rows` is the caller's: see gkmhip_set_sequences */
     return 0;
 }
 

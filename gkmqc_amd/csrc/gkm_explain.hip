@@ -165,40 +165,30 @@ extern "C" int gkmhip_explain_block(gkmhip_ctx *ctx, const int *rows, int nrows,
                                     void *stream_)
 {
     if (!ctx || !rows || nrows <= 0 || !share || !coef || !out) return set_err_msg("gkmhip_explain_block: bad arguments", 2);
-    if (ctx->n <= 0) return set_err_msg("gkmhip_explain_block: no sequences uploaded", 2);
-    if (col_begin < 0 || col_end > ctx->n || col_begin >= col_end)
-        return set_err_msg("gkmhip_explain_block: the column range must satisfy 0 <= col_begin < col_end <= n", 2);
-    const int L = ctx->L, d = ctx->d, n = ctx->n;
+    if (int rc = check_range(ctx, col_begin, col_end, "gkmhip_explain_block")) return rc;
+    const int L = ctx->L, d = ctx->d;
     if (d >= L) return set_err_msg("gkmhip_explain_block: needs d < L (a pair with m = L has no matched base to credit)", 2);
-    double comparisons = 0, row_lmers = 0;
-    for (int i = 0; i < nrows; i++) {
-        if (rows[i] < 0 || rows[i] >= n || (i > 0 && rows[i] <= rows[i - 1]))
-            return set_err_msg("rows must be strictly ascending sequence indices", 2);
-        row_lmers += (double)(ctx->h_len[(size_t)rows[i]] - L + 1);
-    }
+    double row_lmers = 0;
+    if (int rc = check_rows(ctx, rows, nrows, &row_lmers)) return rc;
     int tmax = 0;
     int64_t bases = 0;
-    for (int j = col_begin; j < col_end; j++) {
-        tmax = std::max(tmax, ctx->h_len[(size_t)j]);
-        bases += ctx->h_len[(size_t)j];
-    }
-    comparisons = 2.0 * row_lmers * (ctx->h_cum_n[(size_t)col_end] - ctx->h_cum_n[(size_t)col_begin]);
+    scan_range(ctx, col_begin, col_end, &tmax, &bases);
+    const double comparisons = 2.0 * row_lmers * (ctx->h_cum_n[(size_t)col_end] - ctx->h_cum_n[(size_t)col_begin]);
     hipStream_t stream = (hipStream_t)stream_;
     HIPCHK(hipSetDevice(ctx->device));
     (void)hipGetLastError(); /* the launch checks below must see this call's errors only */
     if (ensure_lmers(ctx, stream, true)) return 4;
     const int chunk = explain_chunk(nrows), nchunks = (nrows + chunk - 1) / chunk;
-    if (ctx->ex_rows.ensure((size_t)nrows) || ctx->ex_part.ensure((size_t)nchunks * (size_t)bases, true)) return 4;
-    HIPCHK(hipMemcpyAsync(ctx->ex_rows.p, rows, (size_t)nrows * sizeof(int), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipStreamSynchronize(stream)); /* `rows` is the caller's: see gkmhip_set_sequences */
+    if (ctx->blk_part.ensure((size_t)nchunks * (size_t)bases, true)) return 4;
+    if (int rc = upload_rows(ctx, rows, nrows, stream)) return rc;
     ExplainArgs A;
-    A.rows = ctx->ex_rows.p; A.nrows = nrows; A.chunk = chunk;
+    A.rows = ctx->blk_rows.p; A.nrows = nrows; A.chunk = chunk;
     A.len = ctx->len.p; A.off = ctx->off.p; A.lmoff = ctx->lmoff.p;
     A.lmf = ctx->lmf.p; A.lmr = ctx->lmf.p + ctx->lm_stride;
     A.coef = coef;
     for (int m = 0; m < GKM_MAXD1; m++) A.share[m] = m <= d ? share[m] : 0.0;
     A.L = L; A.d = d; A.col_begin = col_begin;
-    A.part = ctx->ex_part.p; A.part_stride = bases;
+    A.part = ctx->blk_part.p; A.part_stride = bases;
     const size_t lds = (size_t)(d + 1) * (size_t)tmax * sizeof(uint32_t); /* at most 13 x 2 047 x 4 = 106 444 bytes */
     HIPCHK(hipFuncSetAttribute((const void *)k_explain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipEvent_t e0, e1;
@@ -207,7 +197,7 @@ extern "C" int gkmhip_explain_block(gkmhip_ctx *ctx, const int *rows, int nrows,
     hipLaunchKernelGGL(k_explain, dim3((unsigned)(col_end - col_begin), (unsigned)nchunks), dim3(EX_THREADS), lds, stream, A);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e1, stream));
-    hipLaunchKernelGGL(k_explain_reduce, dim3((unsigned)(col_end - col_begin)), dim3(256), 0, stream, (const double *)ctx->ex_part.p,
+    hipLaunchKernelGGL(k_explain_reduce, dim3((unsigned)(col_end - col_begin)), dim3(256), 0, stream, (const double *)ctx->blk_part.p,
                        (int64_t)bases, nchunks, (const int *)ctx->len.p, (const int64_t *)ctx->off.p, col_begin, xscale, out);
     HIPCHK(hipGetLastError());
     ctx->ev_valid = true;

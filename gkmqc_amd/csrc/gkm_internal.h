@@ -3,7 +3,8 @@
  * C ABI is include/gkm_hip.h.
  *
  *   gkm_context.hip        errors, context, upload, per-sequence device tables (k_build_sb, k_pack_strands, k_pack_lmers),
- *                          pinned host pools, memory helpers
+ *                          pinned host pools, memory helpers, the argument checks and row upload that the launches over
+ *                          (row list) x (column range) share (check_range, check_rows, scan_range, upload_rows)
  *   gkm_gram_bitslice.hip  HOT: k_gram_bitslice (bit-sliced diagonal mismatch profiles) and its instantiation table
  *   gkm_gram.hip           launch geometry (row packing, work-item order, per-launch tables), k_build_rowplanes, k_untile,
  *                          the general kernel k_gram_direct, gkmhip_gram_rows*
@@ -11,8 +12,8 @@
  *   gkm_copyout.hip        device matrix -> the caller's host rows: row blocks, staging pieces, the stream prober
  *   gkm_explain.hip        per-base importance of a trained model (k_explain, k_explain_reduce), gkmhip_explain_block
  *   gkm_ism.hip            in-silico mutagenesis of a trained model (k_ism, k_ism_reduce, k_ism_self_base, k_ism_self),
- *                          gkmhip_ism_block, gkmhip_ism_self_profiles; hypothetical importance (k_ism_hyp,
- *                          k_ism_hyp_reduce), gkmhip_hyp_block
+ *                          gkmhip_ism_self_profiles; hypothetical importance (k_ism<true>, k_ism_hyp_reduce);
+ *                          gkmhip_ism_block and gkmhip_hyp_block, both through ism_launch<HYP>
  *   gkm_lmer.hip           l-mer weight tables of a trained model and scores from them (k_lmer_weights, k_lmer_score),
  *                          gkmhip_lmer_weights, gkmhip_lmer_score
  */
@@ -144,11 +145,12 @@ struct gkmhip_ctx {
     double sampled_hit_share = -1.0; /* share of sampled l-mer pairs of THESE sequences within d mismatches (set_sequences) */
     double last_comparisons = 0;
     const char *last_kernel = "none";
-    DevBuf<int> ex_rows;      /* gkmhip_explain_block: its row list and the partial rows of its support-vector chunks */
-    DevBuf<double> ex_part;
-    DevBuf<int> ism_rows;     /* gkmhip_ism_block: its row list, the partial rows of its support-vector chunks and their */
-    DevBuf<double> ism_part;  /* per-tile G (gkmhip_hyp_block: its row list and partial rows); gkmhip_ism_self_profiles: */
-                              /* the queries' own profiles P_m(x, x) */
+    /* gkmhip_explain_block, gkmhip_ism_block, gkmhip_hyp_block: the row list of the call (upload_rows) and the partial
+     * rows of its support-vector chunks.  One buffer each for all three: a call's kernels consume them in stream order
+     * before the next call on that stream can overwrite them (growing one is a hipFree, which waits for the device). */
+    DevBuf<int> blk_rows;
+    DevBuf<double> blk_part;
+    /* gkmhip_ism_block: the per-tile G of its chunks; gkmhip_ism_self_profiles: the queries' own profiles P_m(x, x) */
     DevBuf<double> ism_gpart;
     DevBuf<int64_t> ism_pself;
 };
@@ -166,6 +168,16 @@ int ensure_colpk(gkmhip_ctx *ctx, hipStream_t stream, bool wait = true);
 int ensure_postab(gkmhip_ctx *ctx, hipStream_t stream, bool wait = true);
 int ensure_sb(gkmhip_ctx *ctx, int W, hipStream_t stream, bool wait = true);
 bool bitslice_serves(const gkmhip_ctx *ctx); /* which kernel this context's launches take (gkm_gram.hip) */
+
+/* the prologue of a launch over (row list) x (column range) (gkm_context.hip) */
+/* 0 <= col_begin < col_end <= n of the uploaded set, or error 2 with `what` (the entry point) in front */
+int check_range(const gkmhip_ctx *ctx, int col_begin, int col_end, const char *what);
+/* rows: strictly ascending sequence indices, or error 2; *row_lmers: the l-mers of those sequences */
+int check_rows(const gkmhip_ctx *ctx, const int *rows, int nrows, double *row_lmers);
+/* the longest sequence of a column range and the bases of all of them */
+void scan_range(const gkmhip_ctx *ctx, int col_begin, int col_end, int *tmax, int64_t *bases);
+/* rows -> ctx->blk_rows, complete on return */
+int upload_rows(gkmhip_ctx *ctx, const int *rows, int nrows, hipStream_t stream);
 
 /* ------------------------------------------------------------ what a Gram launch writes */
 struct GramOut {

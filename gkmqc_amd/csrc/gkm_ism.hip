@@ -462,11 +462,73 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_self(const int *__restrict_
     }
 }
 
-int check_range(gkmhip_ctx *ctx, int col_begin, int col_end, const char *what)
+/* gkmhip_ism_block (HYP = false) and gkmhip_hyp_block (HYP = true) behind their argument checks and fold coefficients
+ * (A.fu, A.fb, A.gc): k_ism<HYP> over (rows) x [col_begin, col_end), then its reduce kernel.  3 (ism) or 4 (hypothetical)
+ * partial doubles per base; only ism keeps the per-tile G and returns base. */
+template <bool HYP>
+int ism_launch(gkmhip_ctx *ctx, IsmArgs &A, const int *rows, int nrows, int col_begin, int col_end, const double *coef,
+               double *out, double *base, hipStream_t stream)
 {
-    if (ctx->n <= 0) return set_err_msg(std::string(what) + ": no sequences uploaded", 2);
-    if (col_begin < 0 || col_end > ctx->n || col_begin >= col_end)
-        return set_err_msg(std::string(what) + ": the column range must satisfy 0 <= col_begin < col_end <= n", 2);
+    constexpr int per = HYP ? 4 : 3;
+    if (int rc = check_range(ctx, col_begin, col_end, HYP ? "gkmhip_hyp_block" : "gkmhip_ism_block")) return rc;
+    const int L = ctx->L, d = ctx->d, mb = ism_mb(L, d);
+    if (HYP && d >= L)
+        return set_err_msg("gkmhip_hyp_block: needs d < L (a pair with m = L has no matched base to credit)", 2);
+    const int tile = ism_tile(L, d);
+    double row_lmers = 0;
+    if (int rc = check_rows(ctx, rows, nrows, &row_lmers)) return rc;
+    int tmax = 0;
+    int64_t bases = 0;
+    scan_range(ctx, col_begin, col_end, &tmax, &bases);
+    double tile_lmers = 0; /* query l-mers loaded over all tiles (a tile also takes the L - 1 l-mers before it) */
+    for (int j = col_begin; j < col_end; j++) {
+        const int T = ctx->h_len[(size_t)j], nx = T - L + 1;
+        for (int t0 = 0; t0 < T; t0 += tile) tile_lmers += std::min(nx, t0 + tile) - std::max(0, t0 - L + 1);
+    }
+    const double comparisons = 2.0 * row_lmers * tile_lmers;
+    const int ntiles = (tmax + tile - 1) / tile, stride = std::min(tile, tmax);
+    const int ncols = col_end - col_begin;
+    HIPCHK(hipSetDevice(ctx->device));
+    (void)hipGetLastError(); /* the launch checks below must see this call's errors only */
+    if (ensure_lmers(ctx, stream, true)) return 4;
+    const int chunk = ism_chunk(nrows), nchunks = (nrows + chunk - 1) / chunk;
+    if (ctx->blk_part.ensure((size_t)nchunks * per * (size_t)bases, true) ||
+        (!HYP && ctx->ism_gpart.ensure((size_t)nchunks * (size_t)ncols * (size_t)ntiles, true)))
+        return 4;
+    if (int rc = upload_rows(ctx, rows, nrows, stream)) return rc;
+    A.rows = ctx->blk_rows.p; A.nrows = nrows; A.chunk = chunk;
+    A.len = ctx->len.p; A.off = ctx->off.p; A.lmoff = ctx->lmoff.p;
+    A.lmf = ctx->lmf.p; A.lmr = ctx->lmf.p + ctx->lm_stride;
+    A.coef = coef;
+    A.L = L; A.d = d; A.mb = mb; A.col_begin = col_begin;
+    A.tile = tile; A.stride = stride; A.ntiles = ntiles;
+    A.part = ctx->blk_part.p; A.part_stride = per * bases; A.gpart = HYP ? nullptr : ctx->ism_gpart.p;
+    /* at most 6 248 + 4 x (13 + 3 x 12) x 804 = 163 832 bytes (L = 12, d = 12); 44 648 at gkmQC's shape */
+    const size_t lds = ISM_LDS_FIXED + (size_t)(d + 1 + 3 * mb) * (size_t)stride * sizeof(uint32_t);
+    HIPCHK(hipFuncSetAttribute((const void *)k_ism<HYP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipEvent_t e0, e1;
+    if (gkm_launch_events(ctx, &e0, &e1)) return 4;
+    HIPCHK(hipEventRecord(e0, stream));
+    hipLaunchKernelGGL(k_ism<HYP>, dim3((unsigned)ncols, (unsigned)nchunks, (unsigned)ntiles), dim3(ISM_THREADS), lds, stream, A);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e1, stream));
+    if constexpr (HYP)
+        hipLaunchKernelGGL(k_ism_hyp_reduce, dim3((unsigned)ncols), dim3(256), 0, stream, (const double *)ctx->blk_part.p,
+                           (int64_t)per * bases, nchunks, (const int *)ctx->len.p, (const int64_t *)ctx->off.p,
+                           (const uint8_t *)ctx->codes.p, col_begin, out);
+    else
+        hipLaunchKernelGGL(k_ism_reduce, dim3((unsigned)ncols), dim3(256), 0, stream, (const double *)ctx->blk_part.p,
+                           (int64_t)per * bases, (const double *)ctx->ism_gpart.p, nchunks, ntiles, tile,
+                           (const int *)ctx->len.p, (const int64_t *)ctx->off.p, (const uint8_t *)ctx->codes.p, col_begin,
+                           out, base);
+    HIPCHK(hipGetLastError());
+    ctx->ev_valid = true;
+    ctx->last_comparisons = comparisons;
+    ctx->last_kernel = HYP ? "k_ism<true>" : "k_ism";
+    if (getenv("GKM_TRACE"))
+        fprintf(stderr, "gkmhip: %s %d rows x columns [%d, %d) -> %s (%d chunks of %d rows, %d tiles of %d positions, "
+                        "%zu bytes of LDS, %.3g comparisons)\n", HYP ? "hypothetical" : "ism", nrows, col_begin, col_end,
+                ctx->last_kernel, nchunks, chunk, ntiles, tile, lds, comparisons);
     return 0;
 }
 
@@ -478,142 +540,26 @@ extern "C" int gkmhip_ism_block(gkmhip_ctx *ctx, const int *rows, int nrows, int
 {
     if (!ctx || !rows || nrows <= 0 || !fold_u || !fold_b || !gcoef || !coef || !out)
         return set_err_msg("gkmhip_ism_block: bad arguments", 2);
-    if (int rc = check_range(ctx, col_begin, col_end, "gkmhip_ism_block")) return rc;
-    const int L = ctx->L, d = ctx->d, n = ctx->n, mb = ism_mb(L, d);
-    const int tile = ism_tile(L, d);
-    double row_lmers = 0;
-    for (int i = 0; i < nrows; i++) {
-        if (rows[i] < 0 || rows[i] >= n || (i > 0 && rows[i] <= rows[i - 1]))
-            return set_err_msg("rows must be strictly ascending sequence indices", 2);
-        row_lmers += (double)(ctx->h_len[(size_t)rows[i]] - L + 1);
-    }
-    int tmax = 0;
-    int64_t bases = 0;
-    double tile_lmers = 0; /* query l-mers loaded over all tiles (a tile also takes the L - 1 l-mers before it) */
-    for (int j = col_begin; j < col_end; j++) {
-        const int T = ctx->h_len[(size_t)j], nx = T - L + 1;
-        tmax = std::max(tmax, T);
-        bases += T;
-        for (int t0 = 0; t0 < T; t0 += tile) tile_lmers += std::min(nx, t0 + tile) - std::max(0, t0 - L + 1);
-    }
-    const double comparisons = 2.0 * row_lmers * tile_lmers;
-    const int ntiles = (tmax + tile - 1) / tile, stride = std::min(tile, tmax);
-    const int ncols = col_end - col_begin;
-    hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(hipSetDevice(ctx->device));
-    (void)hipGetLastError(); /* the launch checks below must see this call's errors only */
-    if (ensure_lmers(ctx, stream, true)) return 4;
-    const int chunk = ism_chunk(nrows), nchunks = (nrows + chunk - 1) / chunk;
-    if (ctx->ism_rows.ensure((size_t)nrows) || ctx->ism_part.ensure((size_t)nchunks * 3 * (size_t)bases, true) ||
-        ctx->ism_gpart.ensure((size_t)nchunks * (size_t)ncols * (size_t)ntiles, true))
-        return 4;
-    HIPCHK(hipMemcpyAsync(ctx->ism_rows.p, rows, (size_t)nrows * sizeof(int), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipStreamSynchronize(stream)); /* `rows` is the caller's: see gkmhip_set_sequences */
     IsmArgs A;
-    A.rows = ctx->ism_rows.p; A.nrows = nrows; A.chunk = chunk;
-    A.len = ctx->len.p; A.off = ctx->off.p; A.lmoff = ctx->lmoff.p;
-    A.lmf = ctx->lmf.p; A.lmr = ctx->lmf.p + ctx->lm_stride;
-    A.coef = coef;
     for (int m = 0; m < GKM_MAXD1; m++) {
-        A.fu[m] = m <= d ? fold_u[m] : 0.0;
-        A.fb[m] = m < mb ? fold_b[m] : 0.0;
-        A.gc[m] = m <= d ? gcoef[m] : 0.0;
+        A.fu[m] = m <= ctx->d ? fold_u[m] : 0.0;
+        A.fb[m] = m < ism_mb(ctx->L, ctx->d) ? fold_b[m] : 0.0;
+        A.gc[m] = m <= ctx->d ? gcoef[m] : 0.0;
     }
-    A.L = L; A.d = d; A.mb = mb; A.col_begin = col_begin;
-    A.tile = tile; A.stride = stride; A.ntiles = ntiles;
-    A.part = ctx->ism_part.p; A.part_stride = 3 * bases; A.gpart = ctx->ism_gpart.p;
-    /* at most 6 248 + 4 x (13 + 3 x 12) x 804 = 163 832 bytes (L = 12, d = 12); 44 648 at gkmQC's shape */
-    const size_t lds = ISM_LDS_FIXED + (size_t)(d + 1 + 3 * mb) * (size_t)stride * sizeof(uint32_t);
-    HIPCHK(hipFuncSetAttribute((const void *)k_ism<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipEvent_t e0, e1;
-    if (gkm_launch_events(ctx, &e0, &e1)) return 4;
-    HIPCHK(hipEventRecord(e0, stream));
-    hipLaunchKernelGGL(k_ism<false>, dim3((unsigned)ncols, (unsigned)nchunks, (unsigned)ntiles), dim3(ISM_THREADS), lds, stream, A);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, stream));
-    hipLaunchKernelGGL(k_ism_reduce, dim3((unsigned)ncols), dim3(256), 0, stream, (const double *)ctx->ism_part.p,
-                       (int64_t)3 * bases, (const double *)ctx->ism_gpart.p, nchunks, ntiles, tile,
-                       (const int *)ctx->len.p, (const int64_t *)ctx->off.p, (const uint8_t *)ctx->codes.p, col_begin, out,
-                       base);
-    HIPCHK(hipGetLastError());
-    ctx->ev_valid = true;
-    ctx->last_comparisons = comparisons;
-    ctx->last_kernel = "k_ism";
-    if (getenv("GKM_TRACE"))
-        fprintf(stderr, "gkmhip: ism %d rows x columns [%d, %d) -> k_ism (%d chunks of %d rows, %d tiles of %d positions, "
-                        "%zu bytes of LDS, %.3g comparisons)\n", nrows, col_begin, col_end, nchunks, chunk, ntiles, tile,
-                lds, comparisons);
-    return 0;
+    return ism_launch<false>(ctx, A, rows, nrows, col_begin, col_end, coef, out, base, (hipStream_t)stream_);
 }
 
 extern "C" int gkmhip_hyp_block(gkmhip_ctx *ctx, const int *rows, int nrows, int col_begin, int col_end,
                                 const double *share, const double *coef, double *out, void *stream_)
 {
     if (!ctx || !rows || nrows <= 0 || !share || !coef || !out) return set_err_msg("gkmhip_hyp_block: bad arguments", 2);
-    if (int rc = check_range(ctx, col_begin, col_end, "gkmhip_hyp_block")) return rc;
-    const int L = ctx->L, d = ctx->d, n = ctx->n, mb = ism_mb(L, d);
-    if (d >= L) return set_err_msg("gkmhip_hyp_block: needs d < L (a pair with m = L has no matched base to credit)", 2);
-    const int tile = ism_tile(L, d);
-    double row_lmers = 0;
-    for (int i = 0; i < nrows; i++) {
-        if (rows[i] < 0 || rows[i] >= n || (i > 0 && rows[i] <= rows[i - 1]))
-            return set_err_msg("rows must be strictly ascending sequence indices", 2);
-        row_lmers += (double)(ctx->h_len[(size_t)rows[i]] - L + 1);
-    }
-    int tmax = 0;
-    int64_t bases = 0;
-    double tile_lmers = 0; /* as gkmhip_ism_block */
-    for (int j = col_begin; j < col_end; j++) {
-        const int T = ctx->h_len[(size_t)j], nx = T - L + 1;
-        tmax = std::max(tmax, T);
-        bases += T;
-        for (int t0 = 0; t0 < T; t0 += tile) tile_lmers += std::min(nx, t0 + tile) - std::max(0, t0 - L + 1);
-    }
-    const double comparisons = 2.0 * row_lmers * tile_lmers;
-    const int ntiles = (tmax + tile - 1) / tile, stride = std::min(tile, tmax);
-    const int ncols = col_end - col_begin;
-    hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(hipSetDevice(ctx->device));
-    (void)hipGetLastError(); /* the launch checks below must see this call's errors only */
-    if (ensure_lmers(ctx, stream, true)) return 4;
-    const int chunk = ism_chunk(nrows), nchunks = (nrows + chunk - 1) / chunk;
-    if (ctx->ism_rows.ensure((size_t)nrows) || ctx->ism_part.ensure((size_t)nchunks * 4 * (size_t)bases, true)) return 4;
-    HIPCHK(hipMemcpyAsync(ctx->ism_rows.p, rows, (size_t)nrows * sizeof(int), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipStreamSynchronize(stream)); /* `rows` is the caller's: see gkmhip_set_sequences */
     IsmArgs A;
-    A.rows = ctx->ism_rows.p; A.nrows = nrows; A.chunk = chunk;
-    A.len = ctx->len.p; A.off = ctx->off.p; A.lmoff = ctx->lmoff.p;
-    A.lmf = ctx->lmf.p; A.lmr = ctx->lmf.p + ctx->lm_stride;
-    A.coef = coef;
     for (int m = 0; m < GKM_MAXD1; m++) {
-        A.fu[m] = m <= d ? share[m] : 0.0;      /* U row m: share[m] */
-        A.fb[m] = m < mb ? share[m] : 0.0;      /* B row m + 1: share[m] */
+        A.fu[m] = m <= ctx->d ? share[m] : 0.0;                    /* U row m: share[m] */
+        A.fb[m] = m < ism_mb(ctx->L, ctx->d) ? share[m] : 0.0;     /* B row m + 1: share[m] */
         A.gc[m] = 0.0;
     }
-    A.L = L; A.d = d; A.mb = mb; A.col_begin = col_begin;
-    A.tile = tile; A.stride = stride; A.ntiles = ntiles;
-    A.part = ctx->ism_part.p; A.part_stride = 4 * bases; A.gpart = nullptr;
-    const size_t lds = ISM_LDS_FIXED + (size_t)(d + 1 + 3 * mb) * (size_t)stride * sizeof(uint32_t); /* as k_ism's */
-    HIPCHK(hipFuncSetAttribute((const void *)k_ism<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipEvent_t e0, e1;
-    if (gkm_launch_events(ctx, &e0, &e1)) return 4;
-    HIPCHK(hipEventRecord(e0, stream));
-    hipLaunchKernelGGL(k_ism<true>, dim3((unsigned)ncols, (unsigned)nchunks, (unsigned)ntiles), dim3(ISM_THREADS), lds, stream,
-                       A);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, stream));
-    hipLaunchKernelGGL(k_ism_hyp_reduce, dim3((unsigned)ncols), dim3(256), 0, stream, (const double *)ctx->ism_part.p,
-                       (int64_t)4 * bases, nchunks, (const int *)ctx->len.p, (const int64_t *)ctx->off.p,
-                       (const uint8_t *)ctx->codes.p, col_begin, out);
-    HIPCHK(hipGetLastError());
-    ctx->ev_valid = true;
-    ctx->last_comparisons = comparisons;
-    ctx->last_kernel = "k_ism<true>";
-    if (getenv("GKM_TRACE"))
-        fprintf(stderr, "gkmhip: hypothetical %d rows x columns [%d, %d) -> k_ism<true> (%d chunks of %d rows, %d tiles of %d "
-                        "positions, %zu bytes of LDS, %.3g comparisons)\n", nrows, col_begin, col_end, nchunks, chunk,
-                ntiles, tile, lds, comparisons);
-    return 0;
+    return ism_launch<true>(ctx, A, rows, nrows, col_begin, col_end, coef, out, nullptr, (hipStream_t)stream_);
 }
 
 extern "C" int gkmhip_ism_self_profiles(gkmhip_ctx *ctx, int col_begin, int col_end, int64_t *prof, void *stream_)

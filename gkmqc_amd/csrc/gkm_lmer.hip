@@ -138,9 +138,7 @@ extern "C" int gkmhip_lmer_weights(gkmhip_ctx *ctx, const double *c, const uint3
 extern "C" int gkmhip_lmer_score(gkmhip_ctx *ctx, int col_begin, int col_end, const double *W, double *out, void *stream_)
 {
     if (!ctx || !W || !out) return set_err_msg("gkmhip_lmer_score: bad arguments", 2);
-    if (ctx->n <= 0) return set_err_msg("gkmhip_lmer_score: no sequences uploaded", 2);
-    if (col_begin < 0 || col_end > ctx->n || col_begin >= col_end)
-        return set_err_msg("gkmhip_lmer_score: the column range must satisfy 0 <= col_begin < col_end <= n", 2);
+    if (int rc = check_range(ctx, col_begin, col_end, "gkmhip_lmer_score")) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     HIPCHK(hipSetDevice(ctx->device));
     (void)hipGetLastError();

@@ -115,6 +115,12 @@ class Model:
             return self.alpha.copy()
         return np.where(np.arange(self.n_sv) < self.n0, -self.alpha, self.alpha)
 
+    def flat_seqs(self):
+        """The support vectors back to back, as the device takes them."""
+        off = np.zeros(self.n_sv + 1, dtype=np.int64)
+        np.cumsum([len(s) for s in self.seqs], out=off[1:])
+        return dv.FlatSequences(np.concatenate(self.seqs), off)
+
     def save(self, path):
         """Write the model file (format: INTEGRATION.md).  Floats as repr(), which reads back to the same double."""
         head = [("format", SVR_FORMAT if self.is_svr else FORMAT), ("kernel_type", self.kernel_type), ("L", self.L),
@@ -331,10 +337,16 @@ def train_svr(fasta, targets, kernel_type=4, L=10, k=6, d=3, M=50, H=50, gamma=1
 
 
 # ------------------------------------------------------------------ scoring
+def _fit_block(unit, unit_bytes, budget, cap=1 << 20):
+    """Queries per block when one query takes `unit_bytes` of device memory per unit of `unit` (support vectors, or bases
+    of the longest query; counted as at least 64): what fits in `budget` bytes, at least 1 and at most `cap`."""
+    return int(max(1, min(cap, budget // (unit_bytes * max(int(unit), 64)))))
+
+
 def default_block(n_sv, budget=BLOCK_BYTES):
     """Queries per block: the S x Qb kernel values and the Gram kernel's tile-transposed output (about as big) within
     `budget` bytes of device memory, whatever the number of queries."""
-    return int(max(1, min(1 << 20, budget // (16 * max(n_sv, 64)))))
+    return _fit_block(n_sv, 16, budget)
 
 
 def _as_queries(fasta_or_sequences):
@@ -359,34 +371,76 @@ def check_queries(model, seqs):
         raise ModelError("query %d is shorter than L = %d" % (int(short[0]), model.L))
 
 
+class _Block:
+    """Queries [q0, q1) of a _Blocks run: qb of them with nb bases, `codes`; qoff their qb + 1 offsets into seqs.codes.
+    t0 / t1: the clock before / after the block's upload."""
+
+    def __init__(self, seqs, q0, q1):
+        self.q0, self.q1, self.qb = q0, q1, q1 - q0
+        self.qoff = seqs.off[q0:q1 + 1]
+        self.codes = seqs.codes[self.qoff[0]:self.qoff[-1]]
+        self.nb = len(self.codes)
+
+    def split(self, host):
+        """One value (or row) per base of the block -> one array per query."""
+        return np.split(host, (self.qoff[1:-1] - self.qoff[0]).astype(np.int64))
+
+
+class _Blocks:
+    """`model` serving the queries `seqs` (checked) in blocks of at most qb_max = `block`, or `default`, queries.  Iterating
+    uploads, per block, [the S support vectors; the block's queries] into the model's cached context `ctx` (an LmerTable
+    has no support vectors: S = 0), takes that set's self norms into `sq` (S + qb_max doubles on `dev`) and yields the
+    _Block.  `rows`: the support vectors' sequence indices; `stream`: the current stream of `dev`, which every call takes."""
+
+    def __init__(self, model, seqs, device, block, default):
+        import torch
+        self.seqs = seqs
+        self.qb_max = min(len(seqs), int(block) if block else default)
+        if self.qb_max < 1:
+            raise ModelError("block must be at least 1")
+        self.ctx = dv.cached_context(*model.kernel_params(), device=device)
+        self.sv = model.flat_seqs() if isinstance(model, Model) else None
+        self.S = len(self.sv) if self.sv else 0
+        self.rows = np.arange(self.S, dtype=np.int32)
+        self.dev = torch.device("cuda", device)
+        self.stream = torch.cuda.current_stream(self.dev).cuda_stream
+        self.sq = torch.empty(self.S + self.qb_max, dtype=torch.float64, device=self.dev)
+
+    def most_bases(self):
+        """The bases of the largest block: what a per-base output buffer must hold."""
+        off, Q = self.seqs.off, len(self.seqs)
+        return max(int(off[min(Q, q0 + self.qb_max)] - off[q0]) for q0 in range(0, Q, self.qb_max))
+
+    def __iter__(self):
+        for q0 in range(0, len(self.seqs), self.qb_max):
+            t0 = time.perf_counter()
+            b = _Block(self.seqs, q0, min(len(self.seqs), q0 + self.qb_max))
+            b.t0 = t0
+            codes, off = b.codes, b.qoff - b.qoff[0]
+            if self.S:
+                codes = np.concatenate((self.sv.codes, codes))
+                off = np.concatenate((self.sv.off, self.sv.off[-1] + off[1:]))
+            self.ctx.set_sequences(dv.FlatSequences(codes, off), self.stream)     # (complete on return)
+            b.t1 = time.perf_counter()
+            self.ctx.self_norms(self.sq.data_ptr(), self.stream)
+            yield b
+
+
 def score(model, fasta_or_sequences, device=0, block=None, kernel=dv.KERNEL_AUTO, on_block=None):
     """Decision values of `model` for a FASTA file (or a list / FlatSequences of base codes) -> (names, scores):
     scikit-learn's `decision_function` sign, positive = like the positive set.  block: queries per device block
     (default_block).  on_block(dict) (measurements): called after every block with its size and timings."""
+    import torch
     seqs, names = _as_queries(fasta_or_sequences)
     check_queries(model, seqs)
-    return names, _score_flat(model, seqs, device, block, kernel, on_block)
-
-
-def _score_flat(model, seqs, device, block, kernel, on_block):
-    import torch
     lib = svmcv._lib()
-    S, Q = model.n_sv, len(seqs)
-    qb_max = min(Q, int(block) if block else default_block(S))
-    if qb_max < 1:
-        raise ModelError("block must be at least 1")
-    ctx = dv.cached_context(*model.kernel_params(), device=device)
+    blocks = _Blocks(model, seqs, device, block, default_block(model.n_sv))
+    ctx, S, rows, qb_max, sq, dev, stream = (blocks.ctx, blocks.S, blocks.rows, blocks.qb_max, blocks.sq, blocks.dev,
+                                             blocks.stream)
     ctx.set_kernel(kernel)
-    sv_codes = np.concatenate(model.seqs)
-    sv_off = np.zeros(S + 1, dtype=np.int64)
-    np.cumsum([len(s) for s in model.seqs], out=sv_off[1:])
-    rows = np.arange(S, dtype=np.int32)
-    dev = torch.device("cuda", device)
-    out = np.empty(Q)
+    out = np.empty(len(seqs))
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
         G = torch.empty((S, qb_max), dtype=torch.float64, device=dev)
-        sq = torch.empty(S + qb_max, dtype=torch.float64, device=dev)
         d_idx = torch.from_numpy(rows).to(dev)
         d_alpha = torch.from_numpy(model.alpha).to(dev)
         # (SVR: LIBSVM's rho, which scikit-learn's predict takes as -intercept_)
@@ -395,16 +449,8 @@ def _score_flat(model, seqs, device, block, kernel, on_block):
         d_dec = torch.empty(qb_max, dtype=torch.float64, device=dev)
         off_sv = np.array([0, S], dtype=np.int64)
         n0 = np.array([model.n0], dtype=np.int32)
-        for q0 in range(0, Q, qb_max):
-            q1 = min(Q, q0 + qb_max)
-            qb = q1 - q0
-            t0 = time.perf_counter()
-            qoff = seqs.off[q0:q1 + 1]
-            union = dv.FlatSequences(np.concatenate((sv_codes, seqs.codes[qoff[0]:qoff[-1]])),
-                                     np.concatenate((sv_off, sv_off[-1] + (qoff[1:] - qoff[0]))))
-            ctx.set_sequences(union, stream)     # (complete on return)
-            t1 = time.perf_counter()
-            ctx.self_norms(sq.data_ptr(), stream)
+        for b in blocks:
+            qb = b.qb
             ctx.gram_block(rows, S, S + qb, G.data_ptr(), qb_max, stream)
             if on_block is not None:
                 torch.cuda.current_stream().synchronize()
@@ -421,7 +467,7 @@ def _score_flat(model, seqs, device, block, kernel, on_block):
                                                       d_dec.data_ptr(), stream)
                 if rc:
                     raise svmcv.SvmError("gkmsvm_decision_signed_batch: %s" % lib.gkmsvm_last_error().decode())
-                out[q0:q1] = d_dec[:qb].cpu().numpy()
+                out[b.q0:b.q1] = d_dec[:qb].cpu().numpy()
             else:
                 rc = lib.gkmsvm_decision_batch(device, G.data_ptr(), qb_max, 1, d_idx.data_ptr(), off_sv.ctypes.data,
                                                n0.ctypes.data, d_alpha.data_ptr(), d_rho.data_ptr(), d_test.data_ptr(),
@@ -429,13 +475,18 @@ def _score_flat(model, seqs, device, block, kernel, on_block):
                 if rc:
                     raise svmcv.SvmError("gkmsvm_decision_batch: %s" % lib.gkmsvm_last_error().decode())
                 # LIBSVM's decision value for labels (0, 1) has the opposite sign of scikit-learn's
-                out[q0:q1] = -d_dec[:qb].cpu().numpy()
+                out[b.q0:b.q1] = -d_dec[:qb].cpu().numpy()
             t4 = time.perf_counter()
             if on_block is not None:
-                on_block(dict(queries=qb, upload_ms=(t1 - t0) * 1e3, norms_gram_ms=(t2 - t1) * 1e3, gram_kernel_ms=gram_ms,
-                              normalize_ms=(t3 - t2) * 1e3, decision_ms=(t4 - t3) * 1e3, wall_ms=(t4 - t0) * 1e3,
-                              comparisons=ctx.last_comparisons(), kernel=ctx.last_kernel_name()))
-    return out
+                on_block(dict(queries=qb, upload_ms=(b.t1 - b.t0) * 1e3, norms_gram_ms=(t2 - b.t1) * 1e3,
+                              gram_kernel_ms=gram_ms, normalize_ms=(t3 - t2) * 1e3, decision_ms=(t4 - t3) * 1e3,
+                              wall_ms=(t4 - b.t0) * 1e3, comparisons=ctx.last_comparisons(),
+                              kernel=ctx.last_kernel_name()))
+    return names, out
+
+
+def _longest(seqs):
+    return int(np.diff(seqs.off).max())
 
 
 # ------------------------------------------------------------------ per-base importance
@@ -460,7 +511,7 @@ def explain_shares(model):
 def default_explain_block(max_len, budget=BLOCK_BYTES):
     """Queries per block: the launch's partial rows (up to EXPLAIN_CHUNKS doubles per base) and the output within `budget`
     bytes of device memory."""
-    return int(max(1, min(1 << 20, budget // (8 * (EXPLAIN_CHUNKS + 1) * max(int(max_len), 64)))))
+    return _fit_block(max_len, 8 * (EXPLAIN_CHUNKS + 1), budget)
 
 
 def explain(model, fasta_or_sequences, device=0, block=None, on_block=None):
@@ -475,70 +526,54 @@ def explain(model, fasta_or_sequences, device=0, block=None, on_block=None):
     evenly over its k bases); for types 1, 2 and 4 the same rule on this project's c_m.  RBF and k = 0 models are refused.
     block: queries per device block (default_explain_block).  on_block(dict) (measurements): called after every block
     with its size, the explain kernel's milliseconds (HIP events), its l-mer comparisons and the block's wall time."""
+    import torch
     check_explainable(model)
     seqs, names = _as_queries(fasta_or_sequences)
     check_queries(model, seqs)
-    return names, _explain_flat(model, seqs, device, block, on_block)
-
-
-def _explain_flat(model, seqs, device, block, on_block=None):
-    import torch
-    S, Q = model.n_sv, len(seqs)
-    lens = np.diff(seqs.off)
-    qb_max = min(Q, int(block) if block else default_explain_block(int(lens.max())))
-    if qb_max < 1:
-        raise ModelError("block must be at least 1")
-    ctx = dv.cached_context(*model.kernel_params(), device=device)
+    blocks = _Blocks(model, seqs, device, block, default_explain_block(_longest(seqs)))
+    ctx, S, sq, dev = blocks.ctx, blocks.S, blocks.sq, blocks.dev
     share = explain_shares(model)
-    sv_codes = np.concatenate(model.seqs)
-    sv_off = np.zeros(S + 1, dtype=np.int64)
-    np.cumsum([len(s) for s in model.seqs], out=sv_off[1:])
-    rows = np.arange(S, dtype=np.int32)
-    dev = torch.device("cuda", device)
     out = []
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        sq = torch.empty(S + qb_max, dtype=torch.float64, device=dev)
         dual = torch.from_numpy(model.dual_coef()).to(dev)
-        most = max(int(seqs.off[min(Q, q0 + qb_max)] - seqs.off[q0]) for q0 in range(0, Q, qb_max))
-        E = torch.empty(most, dtype=torch.float64, device=dev)
-        for q0 in range(0, Q, qb_max):
-            q1 = min(Q, q0 + qb_max)
-            qb = q1 - q0
-            t0 = time.perf_counter()
-            qoff = seqs.off[q0:q1 + 1]
-            union = dv.FlatSequences(np.concatenate((sv_codes, seqs.codes[qoff[0]:qoff[-1]])),
-                                     np.concatenate((sv_off, sv_off[-1] + (qoff[1:] - qoff[0]))))
-            ctx.set_sequences(union, stream)     # (complete on return)
-            ctx.self_norms(sq.data_ptr(), stream)
+        E = torch.empty(blocks.most_bases(), dtype=torch.float64, device=dev)
+        for b in blocks:
             coef = dual / sq[:S]
-            xscale = 1.0 / sq[S:S + qb]
-            ctx.explain_block(rows, S, S + qb, share, coef.data_ptr(), xscale.data_ptr(), E.data_ptr(), stream)
-            host = E[:int(qoff[-1] - qoff[0])].cpu().numpy()
-            out.extend(np.split(host, (qoff[1:-1] - qoff[0]).astype(np.int64)))
+            xscale = 1.0 / sq[S:S + b.qb]
+            ctx.explain_block(blocks.rows, S, S + b.qb, share, coef.data_ptr(), xscale.data_ptr(), E.data_ptr(),
+                              blocks.stream)
+            out.extend(b.split(E[:b.nb].cpu().numpy()))
             if on_block is not None:
-                on_block(dict(queries=qb, explain_kernel_ms=ctx.last_kernel_ms(), comparisons=ctx.last_comparisons(),
-                              kernel=ctx.last_kernel_name(), wall_ms=(time.perf_counter() - t0) * 1e3))
-    return out
+                on_block(dict(queries=b.qb, explain_kernel_ms=ctx.last_kernel_ms(), comparisons=ctx.last_comparisons(),
+                              kernel=ctx.last_kernel_name(), wall_ms=(time.perf_counter() - b.t0) * 1e3))
+    return names, out
 
 
-def write_explanation(path, names, values):
-    """The `explain` output: one line per query, name<TAB>v0,v1,... with repr() floats (they read back to the same
-    doubles)."""
+def _write_values(path, names, values):
     with open(path, "w") as f:
         for name, v in zip(names, values):
-            f.write("%s\t%s\n" % (name, ",".join(repr(float(e)) for e in v)))
+            f.write("%s\t%s\n" % (name, ",".join(repr(float(e)) for e in np.asarray(v).reshape(-1))))
 
 
-def read_explanation(path):
-    """-> (names, [float64 array per query]) from a file written by write_explanation."""
+def _read_values(path, shape):
     names, values = [], []
     with open(path) as f:
         for line in f.read().split("\n")[:-1]:
             name, vals = line.rsplit("\t", 1)
             names.append(name)
-            values.append(np.array([float(e) for e in vals.split(",")], dtype=np.float64))
+            values.append(np.array([float(e) for e in vals.split(",")], dtype=np.float64).reshape(shape))
     return names, values
+
+
+def write_explanation(path, names, values):
+    """The `explain` output: one line per query, name<TAB>v0,v1,... with repr() floats (they read back to the same
+    doubles)."""
+    _write_values(path, names, values)
+
+
+def read_explanation(path):
+    """-> (names, [float64 array per query]) from a file written by write_explanation."""
+    return _read_values(path, (-1,))
 
 
 # ------------------------------------------------------------------ in-silico mutagenesis
@@ -565,8 +600,17 @@ def default_ism_block(max_len, d, budget=BLOCK_BYTES):
     """Queries per block: the launch's partial rows (up to 3 x ISM_CHUNKS doubles per base), the (T, 4) output, the
     mutants' self profiles (4 (d + 1) int64 per base) and the finishing temporaries within `budget` bytes of device
     memory."""
-    per_base = 8 * (3 * ISM_CHUNKS + 4 * (int(d) + 1) + 24)
-    return int(max(1, min(1 << 20, budget // (per_base * max(int(max_len), 64)))))
+    return _fit_block(max_len, 8 * (3 * ISM_CHUNKS + 4 * (int(d) + 1) + 24), budget)
+
+
+def _mutant_norms_sq(prof, c):
+    """G(y, y) = sum_m c_m P_m(y, y) of every single-base mutant y, in ascending m from 0.0 as the oracle forms it.
+    prof: the (bases, 4, d + 1) int64 profiles of gkmhip_ism_self_profiles -> (bases, 4) float64."""
+    import torch
+    g = torch.zeros(prof.shape[:2], dtype=torch.float64, device=prof.device)
+    for m in range(prof.shape[2]):
+        g.add_(prof[:, :, m].double().mul_(float(c[m])))
+    return g
 
 
 def ism(model, fasta_or_sequences, device=0, block=None, on_block=None):
@@ -580,85 +624,53 @@ def ism(model, fasta_or_sequences, device=0, block=None, on_block=None):
     block: queries per device block (default_ism_block).  on_block(dict) (measurements): called after every block with
     its size, k_ism's milliseconds (HIP events), its l-mer comparisons, the self-profile kernels' milliseconds and the
     block's wall time."""
+    import torch
     check_ism(model)
     seqs, names = _as_queries(fasta_or_sequences)
     check_queries(model, seqs)
-    return names, _ism_flat(model, seqs, device, block, on_block)
-
-
-def _ism_flat(model, seqs, device, block, on_block=None):
-    import torch
-    S, Q, d = model.n_sv, len(seqs), model.d
-    lens = np.diff(seqs.off)
-    qb_max = min(Q, int(block) if block else default_ism_block(int(lens.max()), d))
-    if qb_max < 1:
-        raise ModelError("block must be at least 1")
-    ctx = dv.cached_context(*model.kernel_params(), device=device)
+    d = model.d
+    blocks = _Blocks(model, seqs, device, block, default_ism_block(_longest(seqs), d))
+    ctx, S, sq, dev, stream = blocks.ctx, blocks.S, blocks.sq, blocks.dev, blocks.stream
     fold_u, fold_b, c = ism_coefficients(model)
-    sv_codes = np.concatenate(model.seqs)
-    sv_off = np.zeros(S + 1, dtype=np.int64)
-    np.cumsum([len(s) for s in model.seqs], out=sv_off[1:])
-    rows = np.arange(S, dtype=np.int32)
-    dev = torch.device("cuda", device)
     out = []
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        sq = torch.empty(S + qb_max, dtype=torch.float64, device=dev)
         dual = torch.from_numpy(model.dual_coef()).to(dev)
-        most = max(int(seqs.off[min(Q, q0 + qb_max)] - seqs.off[q0]) for q0 in range(0, Q, qb_max))
+        most = blocks.most_bases()
         D = torch.empty((most, 4), dtype=torch.float64, device=dev)
         prof = torch.empty((most, 4, d + 1), dtype=torch.int64, device=dev)
-        base = torch.empty(qb_max, dtype=torch.float64, device=dev)
-        for q0 in range(0, Q, qb_max):
-            q1 = min(Q, q0 + qb_max)
-            qb = q1 - q0
-            t0 = time.perf_counter()
-            qoff = seqs.off[q0:q1 + 1]
-            nb = int(qoff[-1] - qoff[0])
-            union = dv.FlatSequences(np.concatenate((sv_codes, seqs.codes[qoff[0]:qoff[-1]])),
-                                     np.concatenate((sv_off, sv_off[-1] + (qoff[1:] - qoff[0]))))
-            ctx.set_sequences(union, stream)     # (complete on return)
-            ctx.self_norms(sq.data_ptr(), stream)
+        base = torch.empty(blocks.qb_max, dtype=torch.float64, device=dev)
+        for b in blocks:
+            qb, nb = b.qb, b.nb
             ctx.ism_self_profiles(S, S + qb, prof.data_ptr(), stream)
             self_ms = ctx.last_kernel_ms() if on_block is not None else None
             coef = dual / sq[:S]
-            ctx.ism_block(rows, S, S + qb, fold_u, fold_b, c, coef.data_ptr(), D.data_ptr(), base.data_ptr(), stream)
-            # G(y, y) = sum_m c_m P_m(y, y) in ascending m from 0.0, as the oracle forms it; then
+            ctx.ism_block(blocks.rows, S, S + qb, fold_u, fold_b, c, coef.data_ptr(), D.data_ptr(), base.data_ptr(),
+                          stream)
             # score(y) - score(x) = (base + D) / sqrt(G(y, y)) - base / sq_x
-            g = torch.zeros((nb, 4), dtype=torch.float64, device=dev)
-            for m in range(d + 1):
-                g.add_(prof[:nb, :, m].double().mul_(float(c[m])))
-            per = torch.from_numpy(np.diff(qoff)).to(dev)
+            g = _mutant_norms_sq(prof[:nb], c)
+            per = torch.from_numpy(np.diff(b.qoff)).to(dev)
             bx = torch.repeat_interleave(base[:qb], per)
             sx = torch.repeat_interleave(sq[S:S + qb], per)
             res = (bx[:, None] + D[:nb]).div_(g.sqrt_()).sub_((bx / sx)[:, None])
             host = res.cpu().numpy()
-            host[np.arange(nb), seqs.codes[qoff[0]:qoff[-1]]] = 0.0
-            out.extend(np.split(host, (qoff[1:-1] - qoff[0]).astype(np.int64)))
+            host[np.arange(nb), b.codes] = 0.0
+            out.extend(b.split(host))
             if on_block is not None:
                 on_block(dict(queries=qb, ism_kernel_ms=ctx.last_kernel_ms(), comparisons=ctx.last_comparisons(),
                               kernel=ctx.last_kernel_name(), self_kernels_ms=self_ms,
-                              wall_ms=(time.perf_counter() - t0) * 1e3))
-    return out
+                              wall_ms=(time.perf_counter() - b.t0) * 1e3))
+    return names, out
 
 
 def write_ism(path, names, values):
     """The `ism` (and `hypothetical`) output: one line per query, name<TAB>v(0,A),v(0,C),v(0,G),v(0,T),v(1,A),... (4T
     values, position-major) with repr() floats (they read back to the same doubles)."""
-    with open(path, "w") as f:
-        for name, v in zip(names, values):
-            f.write("%s\t%s\n" % (name, ",".join(repr(float(e)) for e in np.asarray(v).reshape(-1))))
+    _write_values(path, names, values)
 
 
 def read_ism(path):
     """-> (names, [float64 array (T, 4) per query]) from a file written by write_ism."""
-    names, values = [], []
-    with open(path) as f:
-        for line in f.read().split("\n")[:-1]:
-            name, vals = line.rsplit("\t", 1)
-            names.append(name)
-            values.append(np.array([float(e) for e in vals.split(",")], dtype=np.float64).reshape(-1, 4))
-    return names, values
+    return _read_values(path, (-1, 4))
 
 
 # ------------------------------------------------------------------ hypothetical importance
@@ -666,8 +678,7 @@ def default_hyp_block(max_len, d, budget=BLOCK_BYTES):
     """Queries per block: the launch's partial rows (up to 4 x ISM_CHUNKS doubles per base), the raw (T, 4) values, the
     mutants' self profiles (4 (d + 1) int64 per base) and the finishing temporaries within `budget` bytes of device
     memory."""
-    per_base = 8 * (4 * ISM_CHUNKS + 4 * (int(d) + 1) + 28)
-    return int(max(1, min(1 << 20, budget // (per_base * max(int(max_len), 64)))))
+    return _fit_block(max_len, 8 * (4 * ISM_CHUNKS + 4 * (int(d) + 1) + 28), budget)
 
 
 def hypothetical(model, fasta_or_sequences, device=0, block=None, on_block=None):
@@ -681,66 +692,39 @@ def hypothetical(model, fasta_or_sequences, device=0, block=None, on_block=None)
     models `explain` serves (no RBF, no k = 0); every query length `score` accepts.  block: queries per device block
     (default_hyp_block).  on_block(dict) (measurements): called after every block with its size, k_ism<true>'s
     milliseconds (HIP events), its l-mer comparisons, the self-profile kernels' milliseconds and the block's wall time."""
+    import torch
     check_explainable(model, "hypothetical")
     seqs, names = _as_queries(fasta_or_sequences)
     check_queries(model, seqs)
-    return names, _hyp_flat(model, seqs, device, block, on_block)
-
-
-def _hyp_flat(model, seqs, device, block, on_block=None):
-    import torch
-    S, Q, d = model.n_sv, len(seqs), model.d
-    lens = np.diff(seqs.off)
-    qb_max = min(Q, int(block) if block else default_hyp_block(int(lens.max()), d))
-    if qb_max < 1:
-        raise ModelError("block must be at least 1")
-    ctx = dv.cached_context(*model.kernel_params(), device=device)
+    d = model.d
+    blocks = _Blocks(model, seqs, device, block, default_hyp_block(_longest(seqs), d))
+    ctx, S, sq, dev, stream = blocks.ctx, blocks.S, blocks.sq, blocks.dev, blocks.stream
     share = explain_shares(model)
     c = dv.mismatch_weights(model.kernel_type, model.L, model.k)[:d + 1]
-    sv_codes = np.concatenate(model.seqs)
-    sv_off = np.zeros(S + 1, dtype=np.int64)
-    np.cumsum([len(s) for s in model.seqs], out=sv_off[1:])
-    rows = np.arange(S, dtype=np.int32)
-    dev = torch.device("cuda", device)
     out = []
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        sq = torch.empty(S + qb_max, dtype=torch.float64, device=dev)
         dual = torch.from_numpy(model.dual_coef()).to(dev)
-        most = max(int(seqs.off[min(Q, q0 + qb_max)] - seqs.off[q0]) for q0 in range(0, Q, qb_max))
+        most = blocks.most_bases()
         R = torch.empty((most, 4), dtype=torch.float64, device=dev)
         prof = torch.empty((most, 4, d + 1), dtype=torch.int64, device=dev)
-        for q0 in range(0, Q, qb_max):
-            q1 = min(Q, q0 + qb_max)
-            qb = q1 - q0
-            t0 = time.perf_counter()
-            qoff = seqs.off[q0:q1 + 1]
-            nb = int(qoff[-1] - qoff[0])
-            union = dv.FlatSequences(np.concatenate((sv_codes, seqs.codes[qoff[0]:qoff[-1]])),
-                                     np.concatenate((sv_off, sv_off[-1] + (qoff[1:] - qoff[0]))))
-            ctx.set_sequences(union, stream)     # (complete on return)
-            ctx.self_norms(sq.data_ptr(), stream)
+        for b in blocks:
+            qb, nb = b.qb, b.nb
             ctx.ism_self_profiles(S, S + qb, prof.data_ptr(), stream)
             self_ms = ctx.last_kernel_ms() if on_block is not None else None
             coef = dual / sq[:S]
             xscale = 1.0 / sq[S:S + qb]
-            ctx.hyp_block(rows, S, S + qb, share, coef.data_ptr(), R.data_ptr(), stream)
-            # the mutant columns times 1 / sqrt(G(y, y)), G(y, y) = sum_m c_m P_m(y, y) in ascending m from 0.0 as _ism_flat
-            # forms it; the own column times explain's xscale
-            g = torch.zeros((nb, 4), dtype=torch.float64, device=dev)
-            for m in range(d + 1):
-                g.add_(prof[:nb, :, m].double().mul_(float(c[m])))
-            scale = 1.0 / g.sqrt_()
-            own = torch.from_numpy(seqs.codes[qoff[0]:qoff[-1]].astype(np.int64)).to(dev)
-            per = torch.from_numpy(np.diff(qoff)).to(dev)
+            ctx.hyp_block(blocks.rows, S, S + qb, share, coef.data_ptr(), R.data_ptr(), stream)
+            # the mutant columns times 1 / sqrt(G(y, y)); the own column times explain's xscale
+            scale = 1.0 / _mutant_norms_sq(prof[:nb], c).sqrt_()
+            own = torch.from_numpy(b.codes.astype(np.int64)).to(dev)
+            per = torch.from_numpy(np.diff(b.qoff)).to(dev)
             scale.scatter_(1, own[:, None], torch.repeat_interleave(xscale, per)[:, None])
-            host = (R[:nb] * scale).cpu().numpy()
-            out.extend(np.split(host, (qoff[1:-1] - qoff[0]).astype(np.int64)))
+            out.extend(b.split((R[:nb] * scale).cpu().numpy()))
             if on_block is not None:
                 on_block(dict(queries=qb, hyp_kernel_ms=ctx.last_kernel_ms(), comparisons=ctx.last_comparisons(),
                               kernel=ctx.last_kernel_name(), self_kernels_ms=self_ms,
-                              wall_ms=(time.perf_counter() - t0) * 1e3))
-    return out
+                              wall_ms=(time.perf_counter() - b.t0) * 1e3))
+    return names, out
 
 
 # ------------------------------------------------------------------ l-mer weight tables
@@ -928,13 +912,11 @@ def lmer_weights(model, device=0, on_piece=None):
     import torch
     S, L, d = model.n_sv, model.L, model.d
     ctx = dv.cached_context(*model.kernel_params(), device=device)
-    sv_off = np.zeros(S + 1, dtype=np.int64)
-    np.cumsum([len(s) for s in model.seqs], out=sv_off[1:])
     dev = torch.device("cuda", device)
     c = dv.mismatch_weights(model.kernel_type, L, model.k)[:d + 1]
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
-        ctx.set_sequences(dv.FlatSequences(np.concatenate(model.seqs), sv_off), stream)
+        ctx.set_sequences(model.flat_seqs(), stream)
         sq = torch.empty(S, dtype=torch.float64, device=dev)
         ctx.self_norms(sq.data_ptr(), stream)
         v, cv = lmer_classes(model, sq.cpu().numpy())
@@ -954,7 +936,7 @@ def lmer_weights(model, device=0, on_piece=None):
 def default_table_block(max_len, budget=BLOCK_BYTES):
     """Queries per block: the upload's per-sequence device tables (sized by the longest query, a few words per base)
     within `budget` bytes, and at most 32 768 (about `score`'s blocks of support vectors and queries together)."""
-    return int(max(1, min(1 << 15, budget // (32 * max(int(max_len), 64)))))
+    return _fit_block(max_len, 32, budget, cap=1 << 15)
 
 
 def score_with_table(table, fasta_or_sequences, device=0, block=None, on_block=None):
@@ -963,116 +945,75 @@ def score_with_table(table, fasta_or_sequences, device=0, block=None, on_block=N
     the self norms (gkmhip_self_norms) and one gather per l-mer (k_lmer_score); bit-identical for every block size.
     on_block(dict) (measurements): called after every block with its size, k_lmer_score's milliseconds and the block's
     wall time."""
+    import torch
     seqs, names = _as_queries(fasta_or_sequences)
     check_queries(table, seqs)
-    return names, _table_flat(table, seqs, device, block, on_block)
-
-
-def _table_flat(table, seqs, device, block, on_block=None):
-    import torch
-    Q = len(seqs)
-    lens = np.diff(seqs.off)
-    qb_max = min(Q, int(block) if block else default_table_block(int(lens.max())))
-    if qb_max < 1:
-        raise ModelError("block must be at least 1")
-    ctx = dv.cached_context(*table.kernel_params(), device=device)
-    dev = torch.device("cuda", device)
-    out = np.empty(Q)
+    blocks = _Blocks(table, seqs, device, block, default_table_block(_longest(seqs)))
+    ctx, sq, dev = blocks.ctx, blocks.sq, blocks.dev
+    out = np.empty(len(seqs))
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
         W = torch.from_numpy(table.W).to(dev)
-        sq = torch.empty(qb_max, dtype=torch.float64, device=dev)
-        T = torch.empty(qb_max, dtype=torch.float64, device=dev)
-        for q0 in range(0, Q, qb_max):
-            q1 = min(Q, q0 + qb_max)
-            qb = q1 - q0
-            t0 = time.perf_counter()
-            qoff = seqs.off[q0:q1 + 1]
-            ctx.set_sequences(dv.FlatSequences(seqs.codes[qoff[0]:qoff[-1]], qoff - qoff[0]), stream)
-            ctx.self_norms(sq.data_ptr(), stream)
-            ctx.lmer_score(0, qb, W.data_ptr(), T.data_ptr(), stream)
-            out[q0:q1] = (T[:qb] / sq[:qb] + table.rho).cpu().numpy()
+        T = torch.empty(blocks.qb_max, dtype=torch.float64, device=dev)
+        for b in blocks:
+            ctx.lmer_score(0, b.qb, W.data_ptr(), T.data_ptr(), blocks.stream)
+            out[b.q0:b.q1] = (T[:b.qb] / sq[:b.qb] + table.rho).cpu().numpy()
             if on_block is not None:
-                on_block(dict(queries=qb, score_kernel_ms=ctx.last_kernel_ms(), lmers=ctx.last_comparisons(),
-                              kernel=ctx.last_kernel_name(), wall_ms=(time.perf_counter() - t0) * 1e3))
-    return out
+                on_block(dict(queries=b.qb, score_kernel_ms=ctx.last_kernel_ms(), lmers=ctx.last_comparisons(),
+                              kernel=ctx.last_kernel_name(), wall_ms=(time.perf_counter() - b.t0) * 1e3))
+    return names, out
 
 
 # ------------------------------------------------------------------ command line
+def _add_train_options(p, svr):
+    p.add_argument("-t", "--kernel-type", type=int, default=4, help="kernel type 0..5 (default: 4)")
+    p.add_argument("-L", "--full-word-length", type=int, default=10, help="full word length (default: 10)")
+    p.add_argument("-k", "--non-gap-length", type=int, default=6, help="non-gap positions (default: 6)")
+    p.add_argument("-d", "--max-num-gaps", type=int, default=3, help="max gaps (default: 3)")
+    p.add_argument("-M", "--init-decay", type=int, default=50, help="initial value of the decay, -t 4/5 (default: 50)")
+    p.add_argument("-H", "--half-life-decay", type=float, default=50, help="half life of the decay, -t 4/5 (default: 50)")
+    p.add_argument("-G", "--rbf-gamma", type=float, default=1.0, help="gamma for RBF kernels, -t 3/5 (default: 1.0)")
+    p.add_argument("-C", "--regularization", type=float, default=1.0, help="regularization parameter C (default: 1.0)")
+    if svr:
+        p.add_argument("-p", "--epsilon", type=float, default=0.1, help="epsilon of the insensitive loss (default: 0.1)")
+    p.add_argument("-e", "--precision", type=float, default=0.001, help="precision parameter epsilon (default: 0.001)")
+    p.add_argument("-u", "--shrinking", type=int, choices=(0, 1), default=0, help="shrinking heuristics (default: 0)")
+
+
+def _add_arguments(p, *positionals, block=True):
+    p.add_argument("--device", type=int, default=0, help="GPU (default: 0)")
+    if block:
+        p.add_argument("--block", type=int, default=None, help="queries per device block (default: from device memory)")
+    for name in positionals:
+        p.add_argument(name)
+
+
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m gkmqc_amd.gkmpredict",
                                 description="train a gkm-SVM on all sequences / score FASTA sequences with it (MI355X)")
     sub = p.add_subparsers(dest="cmd", required=True)
     t = sub.add_parser("train", help="train on pos.fa + neg.fa and write a model file")
-    t.add_argument("-t", "--kernel-type", type=int, default=4, help="kernel type 0..5 (default: 4)")
-    t.add_argument("-L", "--full-word-length", type=int, default=10, help="full word length (default: 10)")
-    t.add_argument("-k", "--non-gap-length", type=int, default=6, help="non-gap positions (default: 6)")
-    t.add_argument("-d", "--max-num-gaps", type=int, default=3, help="max gaps (default: 3)")
-    t.add_argument("-M", "--init-decay", type=int, default=50, help="initial value of the decay, -t 4/5 (default: 50)")
-    t.add_argument("-H", "--half-life-decay", type=float, default=50, help="half life of the decay, -t 4/5 (default: 50)")
-    t.add_argument("-G", "--rbf-gamma", type=float, default=1.0, help="gamma for RBF kernels, -t 3/5 (default: 1.0)")
-    t.add_argument("-C", "--regularization", type=float, default=1.0, help="regularization parameter C (default: 1.0)")
-    t.add_argument("-e", "--precision", type=float, default=0.001, help="precision parameter epsilon (default: 0.001)")
-    t.add_argument("-u", "--shrinking", type=int, choices=(0, 1), default=0, help="shrinking heuristics (default: 0)")
-    t.add_argument("--device", type=int, default=0, help="GPU (default: 0)")
-    t.add_argument("pos_fa")
-    t.add_argument("neg_fa")
-    t.add_argument("model")
+    _add_train_options(t, svr=False)
+    _add_arguments(t, "pos_fa", "neg_fa", "model", block=False)
     v = sub.add_parser("train-svr", help="fit an epsilon-SVR to seqs.fa and targets.txt (name<TAB>value per record) "
                                          "and write a model file")
-    v.add_argument("-t", "--kernel-type", type=int, default=4, help="kernel type 0..5 (default: 4)")
-    v.add_argument("-L", "--full-word-length", type=int, default=10, help="full word length (default: 10)")
-    v.add_argument("-k", "--non-gap-length", type=int, default=6, help="non-gap positions (default: 6)")
-    v.add_argument("-d", "--max-num-gaps", type=int, default=3, help="max gaps (default: 3)")
-    v.add_argument("-M", "--init-decay", type=int, default=50, help="initial value of the decay, -t 4/5 (default: 50)")
-    v.add_argument("-H", "--half-life-decay", type=float, default=50, help="half life of the decay, -t 4/5 (default: 50)")
-    v.add_argument("-G", "--rbf-gamma", type=float, default=1.0, help="gamma for RBF kernels, -t 3/5 (default: 1.0)")
-    v.add_argument("-C", "--regularization", type=float, default=1.0, help="regularization parameter C (default: 1.0)")
-    v.add_argument("-p", "--epsilon", type=float, default=0.1, help="epsilon of the insensitive loss (default: 0.1)")
-    v.add_argument("-e", "--precision", type=float, default=0.001, help="precision parameter epsilon (default: 0.001)")
-    v.add_argument("-u", "--shrinking", type=int, choices=(0, 1), default=0, help="shrinking heuristics (default: 0)")
-    v.add_argument("--device", type=int, default=0, help="GPU (default: 0)")
-    v.add_argument("seqs_fa")
-    v.add_argument("targets")
-    v.add_argument("model")
+    _add_train_options(v, svr=True)
+    _add_arguments(v, "seqs_fa", "targets", "model", block=False)
     q = sub.add_parser("predict", help="score the sequences of query.fa: name<TAB>score per line, in file order")
-    q.add_argument("--device", type=int, default=0, help="GPU (default: 0)")
-    q.add_argument("--block", type=int, default=None, help="queries per device block (default: from device memory)")
-    q.add_argument("query_fa")
-    q.add_argument("model")
-    q.add_argument("output")
+    _add_arguments(q, "query_fa", "model", "output")
     x = sub.add_parser("explain", help="per-base importance of the sequences of query.fa: name<TAB>v0,v1,... per line")
-    x.add_argument("--device", type=int, default=0, help="GPU (default: 0)")
-    x.add_argument("--block", type=int, default=None, help="queries per device block (default: from device memory)")
-    x.add_argument("query_fa")
-    x.add_argument("model")
-    x.add_argument("output")
+    _add_arguments(x, "query_fa", "model", "output")
     z = sub.add_parser("ism", help="in-silico mutagenesis of the sequences of query.fa: name<TAB>4T values per line, "
                                    "position-major, columns A, C, G, T")
-    z.add_argument("--device", type=int, default=0, help="GPU (default: 0)")
-    z.add_argument("--block", type=int, default=None, help="queries per device block (default: from device memory)")
-    z.add_argument("query_fa")
-    z.add_argument("model")
-    z.add_argument("output")
+    _add_arguments(z, "query_fa", "model", "output")
     h = sub.add_parser("hypothetical", help="hypothetical importance of the sequences of query.fa: name<TAB>4T values per "
                                             "line, position-major, columns A, C, G, T (the ism format)")
-    h.add_argument("--device", type=int, default=0, help="GPU (default: 0)")
-    h.add_argument("--block", type=int, default=None, help="queries per device block (default: from device memory)")
-    h.add_argument("query_fa")
-    h.add_argument("model")
-    h.add_argument("output")
+    _add_arguments(h, "query_fa", "model", "output")
     w = sub.add_parser("weights", help="fold a model into its l-mer weight table: a `# key value` header, then "
                                        "LMER<TAB>weight per canonical l-mer")
-    w.add_argument("--device", type=int, default=0, help="GPU (default: 0)")
-    w.add_argument("model")
-    w.add_argument("output")
+    _add_arguments(w, "model", "output", block=False)
     r = sub.add_parser("predict-table", help="score the sequences of query.fa from an l-mer weight table: name<TAB>score "
                                              "per line, in file order (the predict format)")
-    r.add_argument("--device", type=int, default=0, help="GPU (default: 0)")
-    r.add_argument("--block", type=int, default=None, help="queries per device block (default: from device memory)")
-    r.add_argument("query_fa")
-    r.add_argument("weights")
-    r.add_argument("output")
+    _add_arguments(r, "query_fa", "weights", "output")
     return p
 
 
@@ -1090,68 +1031,63 @@ def check_train_args(a):
     return None
 
 
+def write_scores(path, names, scores):
+    """The `predict` (and `predict-table`) output: one line per query, name<TAB>score with a repr() float."""
+    with open(path, "w") as f:
+        for name, s in zip(names, scores):
+            f.write("%s\t%r\n" % (name, float(s)))
+
+
+# the commands that serve a query file: command -> (compute, writer).  compute checks that it serves the model before it
+# parses the query file, and touches the GPU only after both.
+_QUERY_COMMANDS = {
+    "predict": (score, write_scores),
+    "explain": (explain, write_explanation),
+    "ism": (ism, write_ism),
+    "hypothetical": (hypothetical, write_ism),
+    "predict-table": (score_with_table, write_scores),
+}
+
+
 def main(argv=None):
     a = build_parser().parse_args(argv)
     try:
-        if a.cmd == "train":
+        if a.cmd in ("train", "train-svr"):
+            svr = a.cmd == "train-svr"
             bad = check_train_args(a)
             if bad:
                 raise ModelError(bad)
-            for path in (a.pos_fa, a.neg_fa):
+            inputs = (a.seqs_fa, a.targets) if svr else (a.pos_fa, a.neg_fa)
+            for path in inputs:
                 if not os.path.isfile(path):
                     raise ModelError("cannot read %s" % path)
-            m = train(a.pos_fa, a.neg_fa, a.kernel_type, a.full_word_length, a.non_gap_length, a.max_num_gaps,
-                      a.init_decay, a.half_life_decay, a.rbf_gamma, a.regularization, a.precision, bool(a.shrinking),
-                      a.device)
+            kernel_args = (a.kernel_type, a.full_word_length, a.non_gap_length, a.max_num_gaps, a.init_decay,
+                           a.half_life_decay, a.rbf_gamma, a.regularization)
+            if svr:
+                m = train_svr(*inputs, *kernel_args, a.epsilon, a.precision, bool(a.shrinking), a.device)
+            else:
+                m = train(*inputs, *kernel_args, a.precision, bool(a.shrinking), a.device)
             m.save(a.model)
-            print("%d support vectors (%d negative, %d positive), rho %r -> %s"
-                  % (m.n_sv, m.n0, m.n_sv - m.n0, m.rho, a.model), file=sys.stderr)
-        elif a.cmd == "train-svr":
-            bad = check_train_args(a)
-            if bad:
-                raise ModelError(bad)
-            for path in (a.seqs_fa, a.targets):
-                if not os.path.isfile(path):
-                    raise ModelError("cannot read %s" % path)
-            m = train_svr(a.seqs_fa, a.targets, a.kernel_type, a.full_word_length, a.non_gap_length, a.max_num_gaps,
-                          a.init_decay, a.half_life_decay, a.rbf_gamma, a.regularization, a.epsilon, a.precision,
-                          bool(a.shrinking), a.device)
-            m.save(a.model)
-            print("%d support vectors, rho %r (LIBSVM's: %r), %d iterations -> %s"
-                  % (m.n_sv, m.rho, -m.rho, m.n_iter, a.model), file=sys.stderr)
+            if svr:
+                print("%d support vectors, rho %r (LIBSVM's: %r), %d iterations -> %s"
+                      % (m.n_sv, m.rho, -m.rho, m.n_iter, a.model), file=sys.stderr)
+            else:
+                print("%d support vectors (%d negative, %d positive), rho %r -> %s"
+                      % (m.n_sv, m.n0, m.n_sv - m.n0, m.rho, a.model), file=sys.stderr)
         elif a.cmd == "weights":
             m = load(a.model)
             check_table_model(m)
             lmer_weights(m, a.device).save(a.output)
         else:
+            compute, write = _QUERY_COMMANDS[a.cmd]
             if a.block is not None and a.block < 1:
                 raise ModelError("--block must be at least 1")
             if not os.path.isfile(a.query_fa):
                 raise ModelError("cannot read %s" % a.query_fa)
             m = load_lmer_table(a.weights) if a.cmd == "predict-table" else load(a.model)
-            if a.cmd == "explain":
-                check_explainable(m)
-            elif a.cmd == "ism":
-                check_ism(m)
-            elif a.cmd == "hypothetical":
-                check_explainable(m, "hypothetical")
-            seqs, names = _as_queries(a.query_fa)
-            check_queries(m, seqs)
+            names, values = compute(m, a.query_fa, a.device, a.block)
             tmp = a.output + ".tmp"
-            if a.cmd == "explain":
-                write_explanation(tmp, names, _explain_flat(m, seqs, a.device, a.block))
-            elif a.cmd == "ism":
-                write_ism(tmp, names, _ism_flat(m, seqs, a.device, a.block))
-            elif a.cmd == "hypothetical":
-                write_ism(tmp, names, _hyp_flat(m, seqs, a.device, a.block))
-            else:
-                if a.cmd == "predict-table":
-                    scores = _table_flat(m, seqs, a.device, a.block)
-                else:
-                    scores = _score_flat(m, seqs, a.device, a.block, dv.KERNEL_AUTO, None)
-                with open(tmp, "w") as f:
-                    for name, s in zip(names, scores):
-                        f.write("%s\t%r\n" % (name, float(s)))
+            write(tmp, names, values)
             os.replace(tmp, a.output)
     except (ModelError, dv.GkmError, svmcv.SvmError, OSError) as e:
         print("gkmpredict: error: %s" % e, file=sys.stderr)

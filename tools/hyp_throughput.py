@@ -21,7 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def two_pass(gp, dv, model, seqs, block, kernel_ms):
-    """gkmpredict._hyp_flat with the raw values from gkmhip_ism_block (mutant columns) and gkmhip_explain_block (own
+    """gkmpredict.hypothetical with the raw values from gkmhip_ism_block (mutant columns) and gkmhip_explain_block (own
     column) instead of gkmhip_hyp_block; kernel_ms collects [ism_block ms, explain_block ms] per block"""
     import torch
     S, Q, d = model.n_sv, len(seqs), model.d
