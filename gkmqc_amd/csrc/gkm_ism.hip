@@ -25,7 +25,7 @@
  *   k_ism<true>      (k_ism is k_ism<false>) the same enumeration, tallies, chunking and tiling with the hypothetical
  *                    fold: 4 doubles per base, no profile
  *   k_ism_hyp_reduce k_ism<true>'s partial rows summed in chunk order into the (T, 4) output, the query's own base included
- *   k_ism_self_base  P_m(x, x), exact uint64
+ *   k_ism_self_base  P_m(x, x), exact uint64 (alone: gkmhip_self_profiles, the exact norms of the interpretation paths)
  *   k_ism_self       P_m(y, y) of the three mutants at one position: P_m(x, x) plus the exact change of every pair in
  *                    which a changed l-mer takes part (about 4 L T comparisons per mutant)
  *
@@ -602,5 +602,32 @@ extern "C" int gkmhip_ism_self_profiles(gkmhip_ctx *ctx, int col_begin, int col_
     if (getenv("GKM_TRACE"))
         fprintf(stderr, "gkmhip: ism self profiles of columns [%d, %d) -> k_ism_self_base + k_ism_self (%d x %d workgroups, "
                         "%.3g comparisons)\n", col_begin, col_end, ncols, tmax, comparisons);
+    return 0;
+}
+
+extern "C" int gkmhip_self_profiles(gkmhip_ctx *ctx, int col_begin, int col_end, int64_t *pself, void *stream_)
+{
+    if (!ctx || !pself) return set_err_msg("gkmhip_self_profiles: bad arguments", 2);
+    if (int rc = check_range(ctx, col_begin, col_end, "gkmhip_self_profiles")) return rc;
+    double comparisons = 0;
+    for (int j = col_begin; j < col_end; j++) {
+        const double nx = ctx->h_len[(size_t)j] - ctx->L + 1;
+        comparisons += 2.0 * nx * nx;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    HIPCHK(hipSetDevice(ctx->device));
+    (void)hipGetLastError();
+    if (ensure_lmers(ctx, stream, true)) return 4;
+    hipEvent_t e0, e1;
+    if (gkm_launch_events(ctx, &e0, &e1)) return 4;
+    HIPCHK(hipEventRecord(e0, stream));
+    hipLaunchKernelGGL(k_ism_self_base, dim3((unsigned)(col_end - col_begin)), dim3(ISM_THREADS), 0, stream,
+                       (const int *)ctx->len.p, (const int64_t *)ctx->lmoff.p, (const uint32_t *)ctx->lmf.p,
+                       (const uint32_t *)(ctx->lmf.p + ctx->lm_stride), ctx->L, ctx->d, col_begin, pself);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e1, stream));
+    ctx->ev_valid = true;
+    ctx->last_comparisons = comparisons;
+    ctx->last_kernel = "k_ism_self_base";
     return 0;
 }

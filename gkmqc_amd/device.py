@@ -127,6 +127,8 @@ def load():
     L.gkmhip_lmer_score.argtypes = (vp, i32, i32, vp, vp, vp)
     L.gkmhip_ism_self_profiles.restype = i32
     L.gkmhip_ism_self_profiles.argtypes = (vp, i32, i32, vp, vp)
+    L.gkmhip_self_profiles.restype = i32
+    L.gkmhip_self_profiles.argtypes = (vp, i32, i32, vp, vp)
     L.gkmhip_self_norms.restype = i32
     L.gkmhip_self_norms.argtypes = (vp, vp, vp)
     L.gkmhip_normalize_rows_full.restype = i32
@@ -422,6 +424,12 @@ class GramContext:
         base of the range; include/gkm_hip.h gkmhip_ism_self_profiles)."""
         self._chk(self.lib.gkmhip_ism_self_profiles(self.handle, int(col_begin), int(col_end), prof_ptr, stream),
                   "gkmhip_ism_self_profiles")
+
+    def self_profiles(self, col_begin, col_end, pself_ptr, stream=0):
+        """The exact P_m(x, x) of the uploaded sequences [col_begin, col_end) into pself_ptr (int64, d + 1 per sequence;
+        include/gkm_hip.h gkmhip_self_profiles)."""
+        self._chk(self.lib.gkmhip_self_profiles(self.handle, int(col_begin), int(col_end), pself_ptr, stream),
+                  "gkmhip_self_profiles")
 
     def lmer_weights(self, c, v_ptr, cv_ptr, nv, u_begin, u_end, W_ptr, stream=0):
         """L-mer weights W[u - u_begin] for the codes [u_begin, u_end) from nv canonical classes (v_ptr: device uint32

@@ -11,9 +11,10 @@ The other half of a gkm-SVM next to the cross-validation of `gkmsvm.py` (the cou
     normalisation (gkmhip_normalize_block), and sums the decision values with k_decision (gkmsvm_decision_batch) --
     scikit-learn's `decision_function` of the trained SVC, bit for bit, for every block size;
   * `explain` splits each query's score over its bases (gkmhip_explain_block): per block the same upload
-    and self norms as `score`, then one launch that credits every matching l-mer pair to the query bases it matched on;
+    as `score` and the self norms from exact 64-bit profiles (gkmhip_self_profiles: the same doubles as `score`'s while
+    no profile reaches 2^31, the no-wrap domain of INTEGRATION.md §5b, and the true norms beyond), then one launch that credits every matching l-mer pair to the query bases it matched on;
   * `ism` scores every single-base substitution of each query (gkmhip_ism_block and
-    gkmhip_ism_self_profiles): per block the same upload and self norms, one launch that tallies how each l-mer pair's
+    gkmhip_ism_self_profiles): per block the same upload and exact self norms, one launch that tallies how each l-mer pair's
     mismatch count moves under a substitution, and one that counts every mutant's profile against itself;
   * `hypothetical` gives, for every position and each of the four bases, the importance that base would get there
     (gkmhip_hyp_block): ism's upload, self norms, mutant self profiles and tallies, folded the way
@@ -390,9 +391,11 @@ class _Blocks:
     """`model` serving the queries `seqs` (checked) in blocks of at most qb_max = `block`, or `default`, queries.  Iterating
     uploads, per block, [the S support vectors; the block's queries] into the model's cached context `ctx` (an LmerTable
     has no support vectors: S = 0), takes that set's self norms into `sq` (S + qb_max doubles on `dev`) and yields the
-    _Block.  `rows`: the support vectors' sequence indices; `stream`: the current stream of `dev`, which every call takes."""
+    _Block.  `rows`: the support vectors' sequence indices; `stream`: the current stream of `dev`, which every call takes.
+    exact: the norms come from the exact 64-bit self profiles (_exact_norms) instead of gkmhip_self_norms, whose 32-bit
+    profiles wrap like the reference's; the same doubles wherever no profile reaches 2^31."""
 
-    def __init__(self, model, seqs, device, block, default):
+    def __init__(self, model, seqs, device, block, default, exact=False):
         import torch
         self.seqs = seqs
         self.qb_max = min(len(seqs), int(block) if block else default)
@@ -405,6 +408,7 @@ class _Blocks:
         self.dev = torch.device("cuda", device)
         self.stream = torch.cuda.current_stream(self.dev).cuda_stream
         self.sq = torch.empty(self.S + self.qb_max, dtype=torch.float64, device=self.dev)
+        self.c = dv.mismatch_weights(model.kernel_type, model.L, model.k)[:model.d + 1] if exact else None
 
     def most_bases(self):
         """The bases of the largest block: what a per-base output buffer must hold."""
@@ -422,8 +426,24 @@ class _Blocks:
                 off = np.concatenate((self.sv.off, self.sv.off[-1] + off[1:]))
             self.ctx.set_sequences(dv.FlatSequences(codes, off), self.stream)     # (complete on return)
             b.t1 = time.perf_counter()
-            self.ctx.self_norms(self.sq.data_ptr(), self.stream)
+            if self.c is None:
+                self.ctx.self_norms(self.sq.data_ptr(), self.stream)
+            else:
+                _exact_norms(self.ctx, self.S + b.qb, self.c, self.sq, self.stream)
             yield b
+
+
+def _exact_norms(ctx, n, c, sq, stream):
+    """sq[:n] = sqrt(sum_m c_m P_m(x, x)) of the first n uploaded sequences from their exact int64 self profiles
+    (gkmhip_self_profiles), in ascending m from 0.0 as the oracle forms it: bit for bit gkmhip_self_norms' value while
+    every P_m is below 2^31, and the true norm beyond, where the 32-bit profiles of gkmhip_self_norms wrap."""
+    import torch
+    pself = torch.empty((n, len(c)), dtype=torch.int64, device=sq.device)
+    ctx.self_profiles(0, n, pself.data_ptr(), stream)
+    g = torch.zeros(n, dtype=torch.float64, device=sq.device)
+    for m in range(len(c)):
+        g.add_(pself[:, m].double().mul_(float(c[m])))
+    sq[:n] = g.sqrt_()
 
 
 def score(model, fasta_or_sequences, device=0, block=None, kernel=dv.KERNEL_AUTO, on_block=None):
@@ -522,7 +542,9 @@ def explain(model, fasta_or_sequences, device=0, block=None, on_block=None):
 
     where A_s(x)[t] credits every l-mer pair of x (forward) and s (forward or reverse complement) with m <= d mismatches
     with c_m / (L - m) times the pair's positional weights on each of the L - m query bases it matched on.
-    sum_t E(x)[t] = score(x) - model.rho.  For kernel type 0 this is GkmExplain's rule (each shared gapped k-mer split
+    sum_t E(x)[t] = score(x) - model.rho on the no-wrap domain (every mismatch profile involved below 2^31: INTEGRATION.md
+    §5b); beyond it `score` follows the reference's 32-bit wrap, while sq_s and sq_x here come from exact 64-bit self
+    profiles and the sum is the exact score less rho.  For kernel type 0 this is GkmExplain's rule (each shared gapped k-mer split
     evenly over its k bases); for types 1, 2 and 4 the same rule on this project's c_m.  RBF and k = 0 models are refused.
     block: queries per device block (default_explain_block).  on_block(dict) (measurements): called after every block
     with its size, the explain kernel's milliseconds (HIP events), its l-mer comparisons and the block's wall time."""
@@ -530,7 +552,7 @@ def explain(model, fasta_or_sequences, device=0, block=None, on_block=None):
     check_explainable(model)
     seqs, names = _as_queries(fasta_or_sequences)
     check_queries(model, seqs)
-    blocks = _Blocks(model, seqs, device, block, default_explain_block(_longest(seqs)))
+    blocks = _Blocks(model, seqs, device, block, default_explain_block(_longest(seqs)), exact=True)
     ctx, S, sq, dev = blocks.ctx, blocks.S, blocks.sq, blocks.dev
     share = explain_shares(model)
     out = []
@@ -619,7 +641,9 @@ def ism(model, fasta_or_sequences, device=0, block=None, on_block=None):
 
         ism(x)[t, b] = score(y) - score(x),   y = x with base t set to b   (0.0 where b == x[t])
 
-    with score as `score` computes it: sum_s dual_coef_s G(y, s) / (sq_s sqrt(G(y, y))) - rho.  Every
+    with score as `score` computes it, sum_s dual_coef_s G(y, s) / (sq_s sqrt(G(y, y))) - rho, on the
+    no-wrap domain (every mismatch profile involved below 2^31: INTEGRATION.md §5b); beyond it `score` follows the
+    reference's 32-bit wrap and this is the difference of the exact scores, every norm from 64-bit profiles.  Every
     model `score` serves except RBF (types 3 and 5), k = 0 included; every query length `score` accepts.
     block: queries per device block (default_ism_block).  on_block(dict) (measurements): called after every block with
     its size, k_ism's milliseconds (HIP events), its l-mer comparisons, the self-profile kernels' milliseconds and the
@@ -629,7 +653,7 @@ def ism(model, fasta_or_sequences, device=0, block=None, on_block=None):
     seqs, names = _as_queries(fasta_or_sequences)
     check_queries(model, seqs)
     d = model.d
-    blocks = _Blocks(model, seqs, device, block, default_ism_block(_longest(seqs), d))
+    blocks = _Blocks(model, seqs, device, block, default_ism_block(_longest(seqs), d), exact=True)
     ctx, S, sq, dev, stream = blocks.ctx, blocks.S, blocks.sq, blocks.dev, blocks.stream
     fold_u, fold_b, c = ism_coefficients(model)
     out = []
@@ -688,7 +712,8 @@ def hypothetical(model, fasta_or_sequences, device=0, block=None, on_block=None)
         hyp(x)[t, b] = E(y)[t],   y = x with base t set to b   (so hyp(x)[t, x[t]] = E(x)[t])
 
     with E the per-base importance `explain` computes, y's own norm sqrt(G(y, y)) included.  Times the
-    one-hot of x it is explain(x), bit for bit; each mutant column is explain of that mutant at t, bit for bit.  The
+    one-hot of x it is explain(x), bit for bit; each mutant column is explain of that mutant at t, bit for bit, inside
+    and beyond the no-wrap domain (all norms from exact 64-bit self profiles, as explain's: INTEGRATION.md §5b).  The
     models `explain` serves (no RBF, no k = 0); every query length `score` accepts.  block: queries per device block
     (default_hyp_block).  on_block(dict) (measurements): called after every block with its size, k_ism<true>'s
     milliseconds (HIP events), its l-mer comparisons, the self-profile kernels' milliseconds and the block's wall time."""
@@ -697,7 +722,7 @@ def hypothetical(model, fasta_or_sequences, device=0, block=None, on_block=None)
     seqs, names = _as_queries(fasta_or_sequences)
     check_queries(model, seqs)
     d = model.d
-    blocks = _Blocks(model, seqs, device, block, default_hyp_block(_longest(seqs), d))
+    blocks = _Blocks(model, seqs, device, block, default_hyp_block(_longest(seqs), d), exact=True)
     ctx, S, sq, dev, stream = blocks.ctx, blocks.S, blocks.sq, blocks.dev, blocks.stream
     share = explain_shares(model)
     c = dv.mismatch_weights(model.kernel_type, model.L, model.k)[:d + 1]
@@ -904,8 +929,9 @@ def lmer_weights(model, device=0, on_piece=None):
 
         W(u) = sum_s (dual_coef_s / sq_s) sum_q w_s[q] (c[m(u, f_q)] + c[m(u, rc(f_q))])      (c[m] = 0 for m > d)
 
-    so that score(x) = sum_p w_x[p] W(u_p) / sq_x + rho.  Every model `score` serves except RBF (types 3 and 5), k = 0
-    included.  The support vectors' self norms come from one gkmhip_self_norms launch, the classes (v, cv) from the host
+    so that score(x) = sum_p w_x[p] W(u_p) / sq_x + rho on the no-wrap domain (sq_s from exact 64-bit
+    self profiles, so beyond it the table holds the exact model where `score` follows the reference's wrap).  Every model `score` serves except RBF (types 3 and 5), k = 0
+    included.  The support vectors' self norms come from one gkmhip_self_profiles launch, the classes (v, cv) from the host
     (lmer_classes), W from k_lmer_weights over all 4^L codes in pieces of TABLE_PIECE.  on_piece(dict) (measurements):
     called after every piece with its codes, kernel milliseconds (HIP events) and l-mer comparisons."""
     check_table_model(model)
@@ -918,7 +944,7 @@ def lmer_weights(model, device=0, on_piece=None):
         stream = torch.cuda.current_stream().cuda_stream
         ctx.set_sequences(model.flat_seqs(), stream)
         sq = torch.empty(S, dtype=torch.float64, device=dev)
-        ctx.self_norms(sq.data_ptr(), stream)
+        _exact_norms(ctx, S, c, sq, stream)
         v, cv = lmer_classes(model, sq.cpu().numpy())
         d_v = torch.from_numpy(v.view(np.int32)).to(dev)
         d_cv = torch.from_numpy(cv).to(dev)
@@ -941,14 +967,14 @@ def default_table_block(max_len, budget=BLOCK_BYTES):
 
 def score_with_table(table, fasta_or_sequences, device=0, block=None, on_block=None):
     """Decision values from an l-mer weight table for a FASTA file (or a list / FlatSequences of base codes) -> (names,
-    scores): sum_p w_x[p] W(u_p) / sq_x + rho, `score`'s value up to rounding.  Only the queries are uploaded: per block
-    the self norms (gkmhip_self_norms) and one gather per l-mer (k_lmer_score); bit-identical for every block size.
+    scores): sum_p w_x[p] W(u_p) / sq_x + rho, `score`'s value up to rounding on the no-wrap domain (INTEGRATION.md §5b;
+    beyond it the exact score).  Only the queries are uploaded: per block the exact self norms (gkmhip_self_profiles) and one gather per l-mer (k_lmer_score); bit-identical for every block size.
     on_block(dict) (measurements): called after every block with its size, k_lmer_score's milliseconds and the block's
     wall time."""
     import torch
     seqs, names = _as_queries(fasta_or_sequences)
     check_queries(table, seqs)
-    blocks = _Blocks(table, seqs, device, block, default_table_block(_longest(seqs)))
+    blocks = _Blocks(table, seqs, device, block, default_table_block(_longest(seqs)), exact=True)
     ctx, sq, dev = blocks.ctx, blocks.sq, blocks.dev
     out = np.empty(len(seqs))
     with torch.cuda.device(dev):

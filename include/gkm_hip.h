@@ -165,6 +165,17 @@ int gkmhip_hyp_block(gkmhip_ctx *ctx, const int *rows, int nrows, int col_begin,
  * Work is enqueued on `stream`; last_kernel_ms / last_comparisons / last_kernel_name describe k_ism_self_base + k_ism_self. */
 int gkmhip_ism_self_profiles(gkmhip_ctx *ctx, int col_begin, int col_end, int64_t *prof, void *stream);
 
+/* Exact self profiles: for every uploaded sequence j of [col_begin, col_end),
+ *   pself[(j - col_begin) (d + 1) + m] = P_m(x_j, x_j), m = 0..d,
+ * the integer mismatch profile of x_j against itself (forward l-mers against forward and reverse-complement l-mers) in
+ * 64 bits.  gkmhip_self_norms keeps the reference's 32-bit profile, which wraps once a profile reaches 2^31 (a long
+ * low-complexity sequence with large positional weights); below that, sum_m c_m (double)pself[m] in ascending m from 0.0
+ * is bit for bit the square of gkmhip_self_norms' value.  explain, ism, hypothetical and the l-mer tables take their
+ * norms from here.
+ *   pself DEVICE, (col_end - col_begin) (d + 1) int64; nothing else is written.
+ * Work is enqueued on `stream`; last_kernel_ms / last_comparisons / last_kernel_name describe k_ism_self_base. */
+int gkmhip_self_profiles(gkmhip_ctx *ctx, int col_begin, int col_end, int64_t *pself, void *stream);
+
 /* L-mer weight table: for every code u of [u_begin, u_end) (an l-mer packed as gkm_bitslice.h's
  * lmer_entry packs it, first base in the highest pair, no weight byte),
  *   W[u - u_begin] = sum_{i ascending} cv[i] * (cf + cr),   cf = c[m(u, v[i])] if that mismatch count is <= d, else 0.0,

@@ -47,3 +47,17 @@ def test_random_block_sweep(built, seed, monkeypatch, capsys):
     monkeypatch.setattr(sys, "argv", ["fuzz_block.py", "--seconds", "12", "--seed", str(seed)])
     mod.main()
     assert "block fuzz ok" in capsys.readouterr().out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", [15, 16])
+def test_random_interpretation_sweep(built, seed, monkeypatch, capsys):
+    """tools/fuzz_interpret.py: explain / ism / hypothetical tallies and the mutants' self profiles on random shapes (tiled
+    and k = 0 included), weights and row / column subsets, dense-hit sequences mixed with iid ones -- bit for bit the CPU
+    references."""
+    spec = importlib.util.spec_from_file_location("fuzz_interpret", os.path.join(ROOT, "tools", "fuzz_interpret.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    monkeypatch.setattr(sys, "argv", ["fuzz_interpret.py", "--seconds", "12", "--seed", str(seed)])
+    mod.main()                                   # raises SystemExit with the failing case on a mismatch
+    assert "interpret fuzz ok" in capsys.readouterr().out
