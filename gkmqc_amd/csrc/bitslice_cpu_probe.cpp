@@ -94,6 +94,59 @@ extern "C" int bsprobe_profile(int W, int L, int d, const uint8_t *A, int lenA, 
     return 0;
 }
 
+/* ---- the two entries of one shift side by side (tests/test_group_any.py) ----------------------
+ * Runs window_hits (Bv == nullptr, as the kernel calls it) and window_group_any on the same planes: hit_or[g] = OR of the
+ * hit words of group g, any[g] = what window_group_any delivers.  Bhi / Blo: W words.  *top_plane: does this (L, d) count
+ * matches and threshold on the top plane?  Returns 1 for an (L, d) that is not in the device table. */
+template <int W, int L, int D, int GRP>
+static void run_group_any(const uint32_t *Ahi, const uint32_t *Alo, const uint32_t *AV, const uint32_t *Bhi, const uint32_t *Blo,
+                          uint32_t *hit_or, uint32_t *any)
+{
+    uint32_t hit[W];
+    window_hits<W, L, D>(Ahi, Alo, AV, Bhi, Blo, (const uint32_t *)nullptr, hit);
+    for (int g = 0; g < W / GRP; g++) {
+        hit_or[g] = 0u;
+        for (int k = 0; k < GRP; k++) hit_or[g] |= hit[g * GRP + k];
+    }
+    window_group_any<W, L, D, GRP>(Ahi, Alo, AV, Bhi, Blo, any);
+}
+
+#define GCASE(LL, DD) \
+    if (L == LL && d == DD) { run_group_any<10, LL, DD, 5>(Ahi, Alo, AV, Bhi, Blo, hit_or, any); *top_plane = top_plane_serves(LL, DD) ? 1 : 0; return 0; }
+#define GCASE_L(LL) GCASE(LL, 0) GCASE(LL, 1) GCASE(LL, 2) GCASE(LL, 3) GCASE(LL, 4)
+
+/* W = 10, groups of five: the table behind gkm_pick_bitslice (gkm_gram_bitslice.hip) */
+extern "C" int bsprobe_group_any(int L, int d, const uint32_t *Ahi, const uint32_t *Alo, const uint32_t *AV, const uint32_t *Bhi,
+                                 const uint32_t *Blo, uint32_t *hit_or, uint32_t *any, int *top_plane)
+{
+    GCASE_L(5) GCASE_L(6) GCASE_L(7) GCASE_L(8) GCASE_L(9) GCASE_L(10) GCASE_L(11) GCASE_L(12)
+    GCASE(11, 5) GCASE(12, 5) GCASE(12, 6)
+    return 1;
+}
+
+/* the table builders, for the same test: the three planes of a row segment (out[plane * W + w]) ... */
+extern "C" void bsprobe_row_planes(const uint8_t *codes, int len, int s0, int W, int L, uint32_t *out)
+{
+    for (int pl = 0; pl < 3; pl++)
+        for (int w = 0; w < W; w++) out[pl * W + w] = row_plane_word(codes, len, s0, w, W, L, pl);
+}
+/* ... words 0 .. nx-1 of a column strand's two bit planes ... */
+extern "C" void bsprobe_sb_words(const uint8_t *codes, int T, int strand, int W, int L, int nx, uint32_t *hi, uint32_t *lo)
+{
+    for (int x = 0; x < nx; x++) {
+        hi[x] = sb_word(codes, T, strand, x, W, L, 0);
+        lo[x] = sb_word(codes, T, strand, x, W, L, 1);
+    }
+}
+/* ... and the validity plane that one piece (bit rows b0 .. b0+nb-1, cnt owned windows) contributes to a packed lane */
+extern "C" void bsprobe_piece_valid(int b0, int nb, int cnt, int W, uint32_t *out)
+{
+    for (int w = 0; w < W; w++) {
+        out[w] = 0u;
+        for (int b = 0; b < 32; b++) out[w] |= piece_bit((const uint8_t *)nullptr, 0, b0, nb, 0, cnt, b, w, W, 2) << b;
+    }
+}
+
 /* ---- packed lanes: several row sequences against one column sequence ------------------------
  * Packs the rows with gkmpack::pack_rows, checks the packing invariants, builds every lane's
  * planes from its pieces, runs the lane program and attributes each hit to its piece's row.

@@ -20,7 +20,11 @@
  *      sliding power-of-two tree  w2[x]=Z[x]+Z[x+1], w4[x]=w2[x]+w2[x+2], w8[x]=w4[x]+w4[x+4];
  *   5. counts are kept in NB planes + a sticky overflow plane; windows with count <= d and
  *      a valid start on both sides are the HITS (about 0.1-0.4 % of all windows on iid
- *      sequences), the only places where weights are touched.
+ *      sequences), the only places where weights are touched.  window_hits thresholds a count of
+ *      MISMATCHES (count <= d: no plane from bitlen(d) up is set); the kernel's entry,
+ *      window_group_any, counts MATCHES plus a constant bias wherever that makes the threshold the
+ *      top count plane alone ((L, d) = (11,3), (10,3), (12,4) among others), and hands back the
+ *      OR of the hits over a group of words: one op per word for threshold, validity and OR.
  * Cost: ~1.1-1.4 integer VALU ops per l-mer comparison instead of ~5-6.
  *
  * Everything here is plain C++ on uint32_t so that the very same code runs per lane on
@@ -296,6 +300,125 @@ GKM_HD void window_hits(const uint32_t *Ahi, const uint32_t *Alo, const uint32_t
             }
         }
         hit[w] = Bv ? lop3<TT_NA_B_C>(cnt_exceeds<D>(cnt), AV[w], Bv[w]) : (~cnt_exceeds<D>(cnt) & AV[w]);
+    }
+}
+
+/*
+ * The same shift as window_hits, but delivering what the kernel's hit list wants: per group of GRP consecutive words the
+ * OR over the group of "window has <= D mismatches and a valid row-side start" (no column-side validity: window_hits with
+ * Bv == nullptr is the specification -- any[g] == hit[g*GRP] | .. | hit[g*GRP + GRP-1] wherever AV is a plane the tables
+ * build, see below).
+ *
+ * Where the bias allows it the count is kept in MATCHES: with M = L - c matches, c <= D is M >= L - D, and with the
+ * constant beta = 2^(P-1) - (L - D) added once per shift (P = bitlen(L) planes), "hit" is M + beta >= 2^(P-1): THE TOP
+ * PLANE ALONE, provided 0 <= beta and L + beta < 2^P (no wrap).  beta = 0 costs nothing, beta = 1 enters the first
+ * window's column sum as a carry-in (ColumnSumBiased); larger biases keep the mismatch count.  (11,3): beta 0; (10,3):
+ * beta 1; (12,4): beta 0.  Threshold, row validity and the group's OR are then ONE op per word, any | (top & AV[w]),
+ * where the mismatch count needs ~(b3 | b2) & AV[w] per word and two three-input ORs per group of five.
+ *   - match bits are the mismatch expression with the inverted truth table: one xor and one lop3 per word, as before;
+ *   - the up/down counter does not care what it counts;
+ *   - Z[x] = Z[x - W] >> 1 now shifts a MISMATCH into bit row 31 of the extension words (window_hits shifts a match in).
+ *     Both are fiction about bases behind the lane's 32 * W; only windows i >= segment_capacity(W, L) see them, and no
+ *     piece owns those (row_plane_word: i < cap; piece_bit: li < cnt <= nb * W - (L - 1)), so AV is 0 there and the two
+ *     entries agree on every bit that a table-built AV lets through (tests/test_group_any.py).
+ */
+constexpr bool top_plane_serves(int L, int D)
+{
+    const int beta = (1 << (bitlen(L) - 1)) - (L - D);
+    return (beta == 0 || beta == 1) && L + beta < (1 << bitlen(L));
+}
+constexpr int top_plane_bias(int L, int D) { return (1 << (bitlen(L) - 1)) - (L - D); }
+
+constexpr int TT_NOT_A_OR_BXC = 0x09; /* ~(a | (b ^ c)) */
+constexpr int TT_A_OR_BC = 0xF8;      /* a | (b & c) */
+constexpr int TT_XNOR_AB = 0xC3;      /* ~(a ^ b) */
+
+/* ColumnSum with an optional carry-in of one: N planes + CIN.  Even N: the leftover half adder takes the one as its third
+ * input (x ^ y ^ 1, maj(x, y, 1)): the same two ops.  Odd N: s + 1 = (~s, carry s): one op more. */
+template <int N, bool CIN>
+struct ColumnSumBiased {
+    static constexpr int NC = (N + (CIN ? 1 : 0)) / 2;
+    static GKM_HD uint32_t run(const uint32_t *x, uint32_t *carry)
+    {
+        uint32_t s = x[0];
+        int nc = 0;
+#pragma unroll
+        for (int i = 1; i + 1 < N; i += 2) {
+            carry[nc++] = lop3<TT_MAJ>(s, x[i], x[i + 1]);
+            s = lop3<TT_XOR3>(s, x[i], x[i + 1]);
+        }
+        if constexpr (N % 2 == 0) {
+            carry[nc++] = CIN ? (s | x[N - 1]) : (s & x[N - 1]);
+            s = CIN ? lop3<TT_XNOR_AB>(s, x[N - 1], x[N - 1]) : (s ^ x[N - 1]);
+        } else if constexpr (CIN) {
+            carry[nc++] = s;
+            s = ~s;
+        }
+        return s;
+    }
+};
+
+template <int I, int NB, int MX, int N, bool CIN>
+GKM_HD void plane_sum_columns_biased(const uint32_t *x, Cnt<NB, MX> &r)
+{
+    if constexpr (N >= 1 && I < Cnt<NB, MX>::P) {
+        using CS = ColumnSumBiased<N, CIN>;
+        uint32_t carry[CS::NC > 0 ? CS::NC : 1];
+        r.b[I] = CS::run(x, carry);
+        plane_sum_columns_biased<I + 1, NB, MX, CS::NC, false>(carry, r);
+    }
+}
+
+template <int W, int L, int D, int GRP>
+GKM_HD void window_group_any(const uint32_t *Ahi, const uint32_t *Alo, const uint32_t *AV, const uint32_t *Bhi,
+                             const uint32_t *Blo, uint32_t *any)
+{
+    static_assert(L >= 2 && L <= 12, "L out of range");
+    static_assert(W % GRP == 0, "a shift is a whole number of groups");
+    if constexpr (!top_plane_serves(L, D)) {
+        uint32_t hit[W];
+        window_hits<W, L, D>(Ahi, Alo, AV, Bhi, Blo, (const uint32_t *)nullptr, hit);
+#pragma unroll
+        for (int w0 = 0; w0 < W; w0 += GRP) {
+            uint32_t a = hit[w0];
+#pragma unroll
+            for (int g = 1; g + 1 < GRP; g += 2) a = lop3<TT_OR3>(a, hit[w0 + g], hit[w0 + g + 1]);
+            if (GRP % 2 == 0) a |= hit[w0 + GRP - 1];
+            any[w0 / GRP] = a;
+        }
+    } else {
+        constexpr int P = bitlen(L);
+        constexpr int BETA = top_plane_bias(L, D);
+        constexpr int NX = W + L - 1;
+        uint32_t Z[NX]; /* MATCH bits */
+#pragma unroll
+        for (int w = 0; w < W; w++) Z[w] = lop3<TT_NOT_A_OR_BXC>(Ahi[w] ^ Bhi[w], Alo[w], Blo[w]);
+#pragma unroll
+        for (int x = W; x < NX; x++) Z[x] = Z[x - W] >> 1; /* word x == word x-W one bit up; bit row 31: a mismatch */
+
+        Cnt<P, L + BETA> cnt; /* matches + BETA: 0 .. L + BETA < 2^P, exact in P planes */
+        static_assert(Cnt<P, L + BETA>::P == P && !Cnt<P, L + BETA>::OV, "the biased count fills exactly its planes");
+        cnt.ovf = 0u;
+        plane_sum_columns_biased<0, P, L + BETA, L, BETA == 1>(Z, cnt);
+#pragma unroll
+        for (int w = 0; w < W; w++) {
+            if (w > 0) { /* the up/down counter of window_hits, stepping a count of matches */
+                const uint32_t zout = Z[w - 1], zin = Z[w + L - 1];
+                const uint32_t old0 = cnt.b[0];
+                cnt.b[0] = lop3<TT_XOR3>(old0, zin, zout);
+                uint32_t t = lop3<TT_BXC_AND_AXC>(old0, zin, zout);
+#pragma unroll
+                for (int i = 1; i < P; i++) {
+                    const uint32_t old = cnt.b[i];
+                    cnt.b[i] = old ^ t;
+                    if (i + 1 < P) t = lop3<TT_A_AND_BXC>(t, old, zout);
+                }
+            }
+            /* threshold + row validity + the group's OR: one op */
+            const uint32_t top = cnt.b[P - 1];
+            if (w % GRP == 0) any[w / GRP] = top & AV[w];
+            else any[w / GRP] = lop3<TT_A_OR_BC>(any[w / GRP], top, AV[w]);
+        }
     }
 }
 

@@ -400,9 +400,17 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : PK == 4 ? GKM_BS_WAVES : GKM_BS_PAC
 #pragma unroll
                 for (int u = 0; u < BS_DU; u++) {
                     if (d0 + u < T) {
-                        uint32_t hit[W];
-                        window_hits<W, L, D>(Ahi, Alo, AV, bh + u, bl + u, (const uint32_t *)nullptr, hit);
-                        const uint32_t vbase = lane_tag | pack_meta(d0 + u, 0, 0);
+                        /* per group the OR of its words' hits, straight from the count (gkm_bitslice.h: where the bias
+                         * allows, the top plane of a count of matches -- one op per word for threshold, validity and OR) */
+                        uint32_t grp_any[W / BS_GRP];
+                        window_group_any<W, L, D, BS_GRP>(Ahi, Alo, AV, bh + u, bl + u, grp_any);
+                        /* the shift's origin word: the delta field is wave-uniform, so it is shifted into place by the
+                         * scalar unit (the empty asm pins it to an SGPR) and ORed in at full rate; left alone, hipcc emits
+                         * one half-rate v_lshl_or_b32 with the shift as an SGPR operand.  The second group's `| w0` is one
+                         * v_or_b32 per shift, the first group's none. */
+                        uint32_t s_delta = pack_meta(d0 + u, 0, 0);
+                        asm("" : "+s"(s_delta));
+                        const uint32_t vbase = lane_tag | s_delta;
 #pragma unroll
                         for (int w0 = 0; w0 < W; w0 += BS_GRP) {
                             /* wave-level compaction at the source, once per group of BS_GRP words: the lanes with a hit in the
@@ -410,10 +418,7 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : PK == 4 ? GKM_BS_WAVES : GKM_BS_PAC
                              * (ballot + mbcnt); one EXEC-masked ds_write2st64_b32, no divergent control flow.  (Round 5: these
                              * pushes -- two per shift whatever the hits -- cost 14 % of config 2's kernel and 23 % of gkmQC's
                              * shape when doubled, profiles/r5_trip_sensitivity.txt: 8 bytes per record, not 24.) */
-                            uint32_t any = hit[w0];
-#pragma unroll
-                            for (int g = 1; g + 1 < BS_GRP; g += 2) any = lop3<TT_OR3>(any, hit[w0 + g], hit[w0 + g + 1]);
-                            if (BS_GRP % 2 == 0) any |= hit[w0 + BS_GRP - 1];
+                            const uint32_t any = grp_any[w0 / BS_GRP];
                             const unsigned long long mask = __ballot(any != 0u);
                             const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
                                                                             __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
