@@ -125,6 +125,14 @@ def load():
     L.gkmhip_lmer_weights.argtypes = (vp, vp, vp, vp, i32, ctypes.c_uint32, ctypes.c_uint32, vp, vp)
     L.gkmhip_lmer_score.restype = i32
     L.gkmhip_lmer_score.argtypes = (vp, i32, i32, vp, vp, vp)
+    L.gkmhip_scan_lmers.restype = i32
+    L.gkmhip_scan_lmers.argtypes = (vp, vp, vp, i64, vp, vp)
+    L.gkmhip_scan_profiles.restype = i32
+    L.gkmhip_scan_profiles.argtypes = (vp, vp, i64, vp, i32, i32, i64, vp, vp)
+    L.gkmhip_scan_score.restype = i32
+    L.gkmhip_scan_score.argtypes = (vp, vp, i64, vp, i32, i32, i64, vp, vp, vp)
+    L.gkmhip_scan_group.restype = i32
+    L.gkmhip_scan_group.argtypes = (vp, i32, i32)
     L.gkmhip_ism_self_profiles.restype = i32
     L.gkmhip_ism_self_profiles.argtypes = (vp, i32, i32, vp, vp)
     L.gkmhip_self_profiles.restype = i32
@@ -449,6 +457,27 @@ class GramContext:
         doubles indexed by code (include/gkm_hip.h gkmhip_lmer_score)."""
         self._chk(self.lib.gkmhip_lmer_score(self.handle, int(col_begin), int(col_end), W_ptr, out_ptr, stream),
                   "gkmhip_lmer_score")
+
+    def scan_lmers(self, codes_ptr, valid_ptr, nbases, lm_ptr, stream=0):
+        """One word per forward l-mer of `nbases` device base codes into lm_ptr (nbases - L + 1 uint32): the code, bit 31
+        set where the l-mer covers a base whose valid byte is 0 (include/gkm_hip.h gkmhip_scan_lmers)."""
+        self._chk(self.lib.gkmhip_scan_lmers(self.handle, codes_ptr, valid_ptr, int(nbases), lm_ptr, stream),
+                  "gkmhip_scan_lmers")
+
+    def scan_profiles(self, lm_ptr, nlm, wt_ptr, width, stride, nwin, prof_ptr, stream=0):
+        """The exact self profiles of `nwin` windows of `width` bases at `stride`, the first at lm_ptr, into prof_ptr
+        (int64, d + 1 per window): wt_ptr = width - L + 1 device bytes (include/gkm_hip.h gkmhip_scan_profiles)."""
+        self._chk(self.lib.gkmhip_scan_profiles(self.handle, lm_ptr, int(nlm), wt_ptr, int(width), int(stride), int(nwin),
+                                                prof_ptr, stream), "gkmhip_scan_profiles")
+
+    def scan_score(self, lm_ptr, nlm, wt_ptr, width, stride, nwin, W_ptr, out_ptr, stream=0):
+        """sum_p wt[p] W[l-mer p of the window] of the same windows into out_ptr (include/gkm_hip.h gkmhip_scan_score)."""
+        self._chk(self.lib.gkmhip_scan_score(self.handle, lm_ptr, int(nlm), wt_ptr, int(width), int(stride), int(nwin),
+                                             W_ptr, out_ptr, stream), "gkmhip_scan_score")
+
+    def scan_group(self, width, stride):
+        """Windows per stretch of k_scan_profiles for (L, width, stride); 0 where the scan refuses them."""
+        return self.lib.gkmhip_scan_group(self.handle, int(width), int(stride))
 
     def self_norms(self, sq_ptr, stream=0):
         self._chk(self.lib.gkmhip_self_norms(self.handle, sq_ptr, stream), "gkmhip_self_norms")

@@ -25,7 +25,10 @@ The other half of a gkm-SVM next to the cross-validation of `gkmsvm.py` (the cou
   * `train_svr` fits an epsilon-SVR to one real target per sequence: the same Gram matrix, LIBSVM's
     2l-variable problem solved by the GPU solver with a linear term per position (svmcv.train_svr_folds); its model
     scores through the signed decision (gkmsvm_decision_signed_batch) -- scikit-learn's `SVR.predict`, bit for bit --
-    and serves `explain`, `ism`, `hypothetical` and `weights` like a C-SVC model.
+    and serves `explain`, `ism`, `hypothetical` and `weights` like a C-SVC model;
+  * `scan` takes a weight table along sequences of any length and scores every window of W bases at a stride (DESIGN.md
+    §5i, gkmhip_scan_profiles and gkmhip_scan_score): `predict-table`'s value for each window cut out, bit for bit, with
+    the self norms of overlapping windows counted together; windows over a non-ACGT character have no score.
 
     python -m gkmqc_amd.gkmpredict train [-t -L -k -d -M -H -G -C -e -u] pos.fa neg.fa model.txt
     python -m gkmqc_amd.gkmpredict train-svr [-t -L -k -d -M -H -G -C -p -e -u] seqs.fa targets.txt model.txt
@@ -35,6 +38,7 @@ The other half of a gkm-SVM next to the cross-validation of `gkmsvm.py` (the cou
     python -m gkmqc_amd.gkmpredict hypothetical [--block Qb] query.fa model.txt out.txt
     python -m gkmqc_amd.gkmpredict weights model.txt weights.txt
     python -m gkmqc_amd.gkmpredict predict-table [--block Qb] query.fa weights.txt out.txt
+    python -m gkmqc_amd.gkmpredict scan --width W [--stride s] [--chunk B] seqs.fa weights.txt out.bedgraph
 """
 import argparse
 import logging
@@ -440,10 +444,17 @@ def _exact_norms(ctx, n, c, sq, stream):
     import torch
     pself = torch.empty((n, len(c)), dtype=torch.int64, device=sq.device)
     ctx.self_profiles(0, n, pself.data_ptr(), stream)
-    g = torch.zeros(n, dtype=torch.float64, device=sq.device)
+    sq[:n] = _norms_from_profiles(pself, c)
+
+
+def _norms_from_profiles(pself, c):
+    """sqrt(sum_m c_m P_m) of every row of the (rows, d + 1) int64 device profiles `pself`, in ascending m from 0.0: the
+    one epilogue of _exact_norms and `scan`, so that both form the same double from the same profile."""
+    import torch
+    g = torch.zeros(pself.shape[0], dtype=torch.float64, device=pself.device)
     for m in range(len(c)):
         g.add_(pself[:, m].double().mul_(float(c[m])))
-    sq[:n] = g.sqrt_()
+    return g.sqrt_()
 
 
 def score(model, fasta_or_sequences, device=0, block=None, kernel=dv.KERNEL_AUTO, on_block=None):
@@ -989,6 +1000,172 @@ def score_with_table(table, fasta_or_sequences, device=0, block=None, on_block=N
     return names, out
 
 
+# ------------------------------------------------------------------ scanning long sequences
+SCAN_MAX_WIDTH = 2047     # a window is a query of its own: the longest sequence the kernels' norms are defined for
+_WHITESPACE = np.array([9, 10, 11, 12, 13, 32], dtype=np.uint8)
+
+
+def read_long_fasta(path):
+    """A FASTA file -> [(name, codes, valid)] with records of any length, uncut: name is the header after '>', codes
+    the uint8 base codes (A, C, G, T = 0..3 in either case; 0 at any other character) and valid the bool mask of the
+    bases that are A, C, G or T.  Lines before the first header are ignored, as is white space inside a record."""
+    with open(path, "rb") as f:
+        data = np.frombuffer(f.read(), dtype=np.uint8)
+    lut = np.full(256, 255, dtype=np.uint8)
+    lut[_ACGT] = np.arange(4, dtype=np.uint8)
+    lut[np.frombuffer(b"acgt", dtype=np.uint8)] = np.arange(4, dtype=np.uint8)
+    nls = np.flatnonzero(data == 10)
+    starts = np.concatenate(([0], nls + 1))                                # where lines begin
+    starts = starts[starts < len(data)]
+    heads = starts[data[starts] == ord(">")]
+    ends = np.append(nls, len(data))[np.searchsorted(nls, heads)]          # where the header lines end
+    out = []
+    for i, (h, end) in enumerate(zip(heads.tolist(), ends.tolist())):
+        name = data[h + 1:end].tobytes().decode("utf-8", "replace").rstrip("\r")
+        body = data[end + 1:heads[i + 1] if i + 1 < len(heads) else len(data)]
+        body = body[~np.isin(body, _WHITESPACE)]
+        codes = lut[body]
+        valid = codes != 255
+        codes[~valid] = 0
+        out.append((name, codes, valid))
+    return out
+
+
+def _as_scan_records(fasta_or_sequences):
+    if isinstance(fasta_or_sequences, (str, bytes, os.PathLike)):
+        return read_long_fasta(fasta_or_sequences)
+    out = []
+    for i, x in enumerate(fasta_or_sequences):
+        x = np.asarray(x, dtype=np.uint8)
+        valid = x < 4
+        out.append(("seq%d" % i, np.where(valid, x, 0).astype(np.uint8), valid))
+    return out
+
+
+def scan_window_count(T, width, stride):
+    """Windows of `width` bases at starts 0, stride, 2 stride, ... that lie inside T bases."""
+    return 0 if T < width else (int(T) - int(width)) // int(stride) + 1
+
+
+def window_validity(valid, width, stride):
+    """-> bool per window: the window covers no invalid base."""
+    bad = np.zeros(len(valid) + 1, dtype=np.int64)
+    np.cumsum(~np.asarray(valid, dtype=bool), out=bad[1:])
+    a = np.arange(scan_window_count(len(valid), width, stride), dtype=np.int64) * int(stride)
+    return bad[a + int(width)] == bad[a]
+
+
+def scan_chunk_plan(T, width, stride, chunk):
+    """The chunks of a record of T bases -> [(w0, w1, b0, b1)]: windows [w0, w1) from the bases [b0, b1), at most
+    max(chunk, width) of them; every window in exactly one chunk.  Consecutive chunks share the bases between the next
+    window's start and the last window's end (width - 1 of them at stride 1)."""
+    nw = scan_window_count(T, width, stride)
+    per = (max(int(chunk), int(width)) - int(width)) // int(stride) + 1
+    return [(w0, min(nw, w0 + per), w0 * stride, (min(nw, w0 + per) - 1) * stride + width) for w0 in range(0, nw, per)]
+
+
+def default_scan_chunk(d, budget=BLOCK_BYTES):
+    """Bases per chunk: at stride 1 a base costs its code, mask and l-mer word, a window's d + 1 int64 profile counts and
+    the doubles of the epilogue, within `budget` bytes of device memory."""
+    return int(budget // (8 * (int(d) + 1) + 64))
+
+
+def check_scan(table, width, stride, chunk=None):
+    """What `scan` refuses before it reads anything or touches the device."""
+    if not isinstance(table, LmerTable):
+        raise ModelError("scan: needs an l-mer weight table (gkmpredict weights), not a model")
+    check_table_model(table, "scan")
+    if int(width) < table.L:
+        raise ModelError("scan: the width %d is below L = %d" % (width, table.L))
+    if int(width) > SCAN_MAX_WIDTH:
+        raise ModelError("scan: the width %d is above %d, the longest sequence a score is defined for"
+                         % (width, SCAN_MAX_WIDTH))
+    if int(stride) < 1:
+        raise ModelError("scan: the stride must be at least 1")
+    if chunk is not None and int(chunk) < int(width):
+        raise ModelError("scan: a chunk must hold at least one window (%d bases)" % width)
+
+
+def scan(table, fasta_or_sequences, width, stride=1, device=0, chunk=None, on_chunk=None):
+    """The score of every window of `width` bases at starts 0, stride, 2 stride, ... of each record of a FASTA file (or of
+    each of a list of uint8 code arrays, values >= 4 invalid), records of any length -> [(name, starts, scores)], starts
+    int64 and scores float64 per record.  A window's score is score_with_table's for the window cut out as a sequence,
+    bit for bit, whatever `chunk` and whatever precedes the record; NaN where the window covers a character other than
+    A, C, G, T (either case).  A record shorter than `width` has no windows; it is an error if none has any.
+    chunk: bases per device chunk (default_scan_chunk).  on_chunk(dict) (measurements): called after every chunk with
+    its windows, k_scan_profiles' milliseconds (HIP events), its l-mer comparisons and the chunk's wall time."""
+    check_scan(table, width, stride, chunk)
+    width, stride = int(width), int(stride)
+    records = _as_scan_records(fasta_or_sequences)
+    if not any(len(codes) >= width for _, codes, _ in records):
+        raise ModelError("scan: no record holds a window of %d bases" % width)
+    import torch
+    L, d = table.L, table.d
+    chunk = int(chunk) if chunk else default_scan_chunk(d)
+    ctx = dv.cached_context(*table.kernel_params(), device=device)
+    dev = torch.device("cuda", device)
+    c = dv.mismatch_weights(table.kernel_type, L, table.k)[:d + 1]
+    wt = dv.position_weights(table.kernel_type, width - L + 1, table.M, table.H)
+    out = []
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        W = torch.from_numpy(table.W).to(dev)
+        d_wt = torch.from_numpy(wt).to(dev)
+        for name, codes, valid in records:
+            nw = scan_window_count(len(codes), width, stride)
+            scores = np.empty(nw)
+            ok = window_validity(valid, width, stride)
+            for w0, w1, b0, b1 in scan_chunk_plan(len(codes), width, stride, chunk):
+                t0 = time.perf_counter()
+                d_codes = torch.from_numpy(codes[b0:b1]).to(dev)
+                d_valid = torch.from_numpy(valid[b0:b1].view(np.uint8)).to(dev)
+                nlm, nwin = b1 - b0 - L + 1, w1 - w0
+                lm = torch.empty(nlm, dtype=torch.int32, device=dev)
+                ctx.scan_lmers(d_codes.data_ptr(), d_valid.data_ptr(), b1 - b0, lm.data_ptr(), stream)
+                prof = torch.empty((nwin, d + 1), dtype=torch.int64, device=dev)
+                ctx.scan_profiles(lm.data_ptr(), nlm, d_wt.data_ptr(), width, stride, nwin, prof.data_ptr(), stream)
+                if on_chunk is not None:
+                    info = dict(windows=nwin, bases=b1 - b0, profile_kernel_ms=ctx.last_kernel_ms(),
+                                comparisons=ctx.last_comparisons(), kernel=ctx.last_kernel_name())
+                T = torch.empty(nwin, dtype=torch.float64, device=dev)
+                ctx.scan_score(lm.data_ptr(), nlm, d_wt.data_ptr(), width, stride, nwin, W.data_ptr(), T.data_ptr(),
+                               stream)
+                sq = _norms_from_profiles(prof, c)
+                scores[w0:w1] = (T / sq + table.rho).cpu().numpy()
+                if on_chunk is not None:
+                    info["wall_ms"] = (time.perf_counter() - t0) * 1e3
+                    on_chunk(info)
+            scores[~ok] = np.nan
+            out.append((name, np.arange(nw, dtype=np.int64) * stride, scores))
+    return out
+
+
+def write_scan(path, results, width):
+    """The `scan` output: one line per scored window, name<TAB>start<TAB>end<TAB>score (0-based start, end = start +
+    width, the score at %.17g, which reads back to the same double); windows without a score (NaN) are left out.
+    -> how many were left out."""
+    omitted = 0
+    with open(path, "w") as f:
+        for name, starts, scores in results:
+            keep = ~np.isnan(scores)
+            omitted += int((~keep).sum())
+            for i in range(0, len(starts), 1 << 16):
+                k = keep[i:i + (1 << 16)]
+                f.write("".join("%s\t%d\t%d\t%.17g\n" % (name, a, a + width, v) for a, v in
+                                zip(starts[i:i + (1 << 16)][k].tolist(), scores[i:i + (1 << 16)][k].tolist())))
+    return omitted
+
+
+def read_scan(path):
+    """-> [(name, start, end, score)] from a file written by write_scan."""
+    out = []
+    with open(path) as f:
+        for line in f.read().split("\n")[:-1]:
+            name, a, b, v = line.rsplit("\t", 3)
+            out.append((name, int(a), int(b), float(v)))
+    return out
+
+
 # ------------------------------------------------------------------ command line
 def _add_train_options(p, svr):
     p.add_argument("-t", "--kernel-type", type=int, default=4, help="kernel type 0..5 (default: 4)")
@@ -1040,6 +1217,13 @@ def build_parser():
     r = sub.add_parser("predict-table", help="score the sequences of query.fa from an l-mer weight table: name<TAB>score "
                                              "per line, in file order (the predict format)")
     _add_arguments(r, "query_fa", "weights", "output")
+    n = sub.add_parser("scan", help="score every window of --width bases of the sequences of seqs.fa (any length) from an "
+                                    "l-mer weight table: name<TAB>start<TAB>end<TAB>score per window, windows over a "
+                                    "non-ACGT character left out")
+    n.add_argument("--width", type=int, required=True, help="bases per window (L..2047)")
+    n.add_argument("--stride", type=int, default=1, help="bases between window starts (default: 1)")
+    n.add_argument("--chunk", type=int, default=None, help="bases per device chunk (default: from device memory)")
+    _add_arguments(n, "seqs_fa", "weights", "output", block=False)
     return p
 
 
@@ -1104,6 +1288,17 @@ def main(argv=None):
             m = load(a.model)
             check_table_model(m)
             lmer_weights(m, a.device).save(a.output)
+        elif a.cmd == "scan":
+            if not os.path.isfile(a.seqs_fa):
+                raise ModelError("cannot read %s" % a.seqs_fa)
+            tab = load_lmer_table(a.weights)
+            check_scan(tab, a.width, a.stride, a.chunk)
+            results = scan(tab, a.seqs_fa, a.width, a.stride, a.device, a.chunk)
+            tmp = a.output + ".tmp"
+            omitted = write_scan(tmp, results, a.width)
+            os.replace(tmp, a.output)
+            print("%d windows scored, %d over a non-ACGT character left out -> %s"
+                  % (sum(len(r[1]) for r in results) - omitted, omitted, a.output), file=sys.stderr)
         else:
             compute, write = _QUERY_COMMANDS[a.cmd]
             if a.block is not None and a.block < 1:

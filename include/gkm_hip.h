@@ -204,6 +204,33 @@ int gkmhip_lmer_weights(gkmhip_ctx *ctx, const double *c, const uint32_t *v, con
  * k_lmer_score. */
 int gkmhip_lmer_score(gkmhip_ctx *ctx, int col_begin, int col_end, const double *W, double *out, void *stream);
 
+/* ---- scanning a long sequence with an l-mer weight table (gkm_scan.hip) ----
+ * The score of every window of `width` bases (L <= width <= 2047) at a stride, each as if the window were a sequence of
+ * its own.  The long sequence does not go through gkmhip_set_sequences: these calls take the context for L and d only,
+ * and plain DEVICE pointers.  With n = width - L + 1, wt the n positional weights every window shares (DEVICE, n bytes:
+ * gkm_position_weights of n) and window i = the l-mers [i stride, i stride + n) of lm:
+ *
+ * gkmhip_scan_lmers: lm[p] = the code of the forward l-mer at base p (first base in the highest pair), bit 31 set when
+ * it covers a base whose valid[] byte is 0.  codes, valid: nbases bytes each (codes 0..3); lm: nbases - L + 1 words. */
+int gkmhip_scan_lmers(gkmhip_ctx *ctx, const uint8_t *codes, const uint8_t *valid, int64_t nbases, uint32_t *lm,
+                      void *stream);
+/* prof[i (d + 1) + m] = P_m of window i against itself, m = 0..d, exact in 64 bits:
+ *   sum_{p, q in window i} wt[p - a_i] wt[q - a_i] ([m(f_p, f_q) = m] + [m(f_p, rc f_q) = m])
+ * -- gkmhip_self_profiles' value for the window cut out as a sequence.  lm may point into a longer array (the first
+ * window's first l-mer); nlm: the words readable from there, at least (nwin - 1) stride + n.  A flagged l-mer takes part
+ * in no pair (the caller drops the windows that hold one).  One workgroup serves a stretch of gkmhip_scan_group
+ * consecutive windows and compares every l-mer pair of the stretch once per strand, not once per window.
+ * last_kernel_ms / last_comparisons (the pair comparisons made, strands counted singly) / last_kernel_name describe
+ * k_scan_profiles. */
+int gkmhip_scan_profiles(gkmhip_ctx *ctx, const uint32_t *lm, int64_t nlm, const uint8_t *wt, int width, int stride,
+                         int64_t nwin, int64_t *prof, void *stream);
+/* out[i] = sum_p wt[p] W[code(lm[i stride + p])], summed as gkmhip_lmer_score sums a sequence (bit-identical to it for
+ * the window cut out).  W: DEVICE, 4^L doubles.  last_* describe k_scan_score. */
+int gkmhip_scan_score(gkmhip_ctx *ctx, const uint32_t *lm, int64_t nlm, const uint8_t *wt, int width, int stride,
+                      int64_t nwin, const double *W, double *out, void *stream);
+/* windows per stretch of k_scan_profiles: a function of (L, width, stride) only; 0 for arguments the scan refuses */
+int gkmhip_scan_group(const gkmhip_ctx *ctx, int width, int stride);
+
 /* sqnorm[i] = sqrt(G(i,i)) for all uploaded sequences (device array of n doubles), computed
  * from the diagonal band only (~1 % of the work of the whole matrix).  Replaces
  * gkmkernel_kernelfunc_sqnorm_single, src/libgkm.c:723-759. */
