@@ -124,6 +124,43 @@ extern "C" int bsprobe_group_any(int L, int d, const uint32_t *Ahi, const uint32
     return 1;
 }
 
+/* ---- the grouped-validity entry (tests/test_group_validity.py) ----------------------------------
+ * window_group_any_grouped on the planes given, with AVg built from AV the way k_gram_bitslice builds it: any_grouped[g];
+ * beside it top_or[g] = OR over the group of the top planes with every window valid (window_group_any with AV = ~0), so
+ * that the test can state any_grouped == top_or & AVg, and avg[g] itself.  Returns 1 for an (L, d) outside the device
+ * table, 2 for one whose threshold is not the top plane (the grouped entry does not exist there). */
+template <int W, int L, int D, int GRP>
+static int run_group_any_grouped(const uint32_t *Ahi, const uint32_t *Alo, const uint32_t *AV, const uint32_t *Bhi,
+                                 const uint32_t *Blo, uint32_t *any_grouped, uint32_t *top_or, uint32_t *avg)
+{
+    if constexpr (!top_plane_serves(L, D)) {
+        return 2;
+    } else {
+        uint32_t ones[W];
+        for (int w = 0; w < W; w++) ones[w] = 0xFFFFFFFFu;
+        window_group_any<W, L, D, GRP>(Ahi, Alo, ones, Bhi, Blo, top_or);
+        for (int g = 0; g < W / GRP; g++) {
+            avg[g] = 0u;
+            for (int k = 0; k < GRP; k++) avg[g] |= AV[g * GRP + k];
+        }
+        window_group_any_grouped<W, L, D, GRP>(Ahi, Alo, avg, Bhi, Blo, any_grouped);
+        return 0;
+    }
+}
+
+#define GGCASE(LL, DD) \
+    if (L == LL && d == DD) return run_group_any_grouped<10, LL, DD, 5>(Ahi, Alo, AV, Bhi, Blo, any_grouped, top_or, avg);
+#define GGCASE_L(LL) GGCASE(LL, 0) GGCASE(LL, 1) GGCASE(LL, 2) GGCASE(LL, 3) GGCASE(LL, 4)
+
+extern "C" int bsprobe_group_any_grouped(int L, int d, const uint32_t *Ahi, const uint32_t *Alo, const uint32_t *AV,
+                                         const uint32_t *Bhi, const uint32_t *Blo, uint32_t *any_grouped, uint32_t *top_or,
+                                         uint32_t *avg)
+{
+    GGCASE_L(5) GGCASE_L(6) GGCASE_L(7) GGCASE_L(8) GGCASE_L(9) GGCASE_L(10) GGCASE_L(11) GGCASE_L(12)
+    GGCASE(11, 5) GGCASE(12, 5) GGCASE(12, 6)
+    return 1;
+}
+
 /* the table builders, for the same test: the three planes of a row segment (out[plane * W + w]) ... */
 extern "C" void bsprobe_row_planes(const uint8_t *codes, int len, int s0, int W, int L, uint32_t *out)
 {

@@ -422,6 +422,70 @@ GKM_HD void window_group_any(const uint32_t *Ahi, const uint32_t *Alo, const uin
     }
 }
 
+/*
+ * window_group_any's top-plane path with the row validity applied once per GROUP instead of once per word:
+ *     AVg[g] = AV[g*GRP] | .. | AV[g*GRP + GRP-1]        (built once per wave by the caller)
+ *     any[g] = (top[g*GRP] | .. | top[g*GRP + GRP-1]) & AVg[g]
+ * For GRP = 5 that is two three-input ORs and one AND per group where window_group_any spends one op per word, and W / GRP
+ * registers of validity instead of W.  Only for (L, D) whose threshold is the top plane (top_plane_serves).
+ *
+ * What it delivers is a SUPERSET of window_group_any's any[g]: bit row b of group g is flagged when SOME window of the five
+ * has <= D mismatches and SOME window of the five is owned -- not necessarily the same one.  It is for a consumer that
+ * evaluates every window of a flagged (bit row, group) itself and lets the windows nobody owns add nothing, which is what
+ * the same-length variant of k_gram_bitslice does (its trip tests m <= d per window and reads the row weight by position
+ * from a table with L - 1 zero bytes behind the row's last l-mer).  The extra flags are confined to groups that are owned
+ * in part: with table-built planes whose pieces own multiples of GRP windows unless they finish their row, only the group
+ * that holds the row's last l-mer nB - 1 is such a group, and the windows it adds are positions nB .. nB + GRP - 2 of the
+ * row (tests/test_group_validity.py).  The several-pieces variants, whose row weights are indexed by distance and have
+ * no zero guard, keep window_group_any.
+ */
+template <int W, int L, int D, int GRP>
+GKM_HD void window_group_any_grouped(const uint32_t *Ahi, const uint32_t *Alo, const uint32_t *AVg, const uint32_t *Bhi,
+                                     const uint32_t *Blo, uint32_t *any)
+{
+    static_assert(L >= 2 && L <= 12, "L out of range");
+    static_assert(W % GRP == 0, "a shift is a whole number of groups");
+    static_assert(top_plane_serves(L, D), "the grouped form exists for the top-plane (L, D) pairs only");
+    constexpr int P = bitlen(L);
+    constexpr int BETA = top_plane_bias(L, D);
+    constexpr int NX = W + L - 1;
+    uint32_t Z[NX]; /* MATCH bits, as in window_group_any */
+#pragma unroll
+    for (int w = 0; w < W; w++) Z[w] = lop3<TT_NOT_A_OR_BXC>(Ahi[w] ^ Bhi[w], Alo[w], Blo[w]);
+#pragma unroll
+    for (int x = W; x < NX; x++) Z[x] = Z[x - W] >> 1;
+
+    Cnt<P, L + BETA> cnt;
+    static_assert(Cnt<P, L + BETA>::P == P && !Cnt<P, L + BETA>::OV, "the biased count fills exactly its planes");
+    cnt.ovf = 0u;
+    plane_sum_columns_biased<0, P, L + BETA, L, BETA == 1>(Z, cnt);
+    uint32_t top[W];
+#pragma unroll
+    for (int w = 0; w < W; w++) {
+        if (w > 0) {
+            const uint32_t zout = Z[w - 1], zin = Z[w + L - 1];
+            const uint32_t old0 = cnt.b[0];
+            cnt.b[0] = lop3<TT_XOR3>(old0, zin, zout);
+            uint32_t t = lop3<TT_BXC_AND_AXC>(old0, zin, zout);
+#pragma unroll
+            for (int i = 1; i < P; i++) {
+                const uint32_t old = cnt.b[i];
+                cnt.b[i] = old ^ t;
+                if (i + 1 < P) t = lop3<TT_A_AND_BXC>(t, old, zout);
+            }
+        }
+        top[w] = cnt.b[P - 1];
+        if (w % GRP == GRP - 1) { /* the group is complete: OR of its top planes, three at a time, then its validity */
+            const int w0 = w - (GRP - 1);
+            uint32_t a = top[w0];
+#pragma unroll
+            for (int g = 1; g + 1 < GRP; g += 2) a = lop3<TT_OR3>(a, top[w0 + g], top[w0 + g + 1]);
+            if (GRP % 2 == 0) a |= top[w0 + GRP - 1];
+            any[w0 / GRP] = a & AVg[w0 / GRP];
+        }
+    }
+}
+
 /* ------------------------------------------------------------------ tables */
 /* Word w of a ROW SEGMENT plane.  Segment base i = b*W + w is sequence position s0 + i.
  * plane 0/1: hi/lo bit of the base code (0 beyond the end of the sequence);

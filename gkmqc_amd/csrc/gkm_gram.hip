@@ -326,6 +326,15 @@ static int plan_bitslice(const gkmhip_ctx *ctx, const int *rows, int nrows, int 
             const int cap = gkmbs::segment_capacity(W, L) / own_mult * own_mult;
             if (pc.b0 != 0 || pc.p0 % cap != 0 || pc.p0 / cap > 7 || slot > 63 || (pc.cnt % own_mult != 0 && pc.p0 + pc.cnt != row_windows))
                 return set_err_msg("gram: same-length packing broke its own rule", 2);
+            /* The counting loop applies row validity per GROUP of five lane positions where the top plane is the threshold
+             * (k_gram_bitslice GROUP_VALID), so a trip may be handed a group of which the lane owns only a part, and every
+             * window of it that the lane does not own has to read a zero row weight.  That holds if no position at or above
+             * cap is owned (those groups stay unowned whole) and the `over` windows that round the piece's last group up to
+             * five fall into the L - 1 zero bytes behind the row's last l-mer in the positional weight table (POSTAB_PAD):
+             * only a piece that finishes its row may have any, and no more than L - 1. */
+            const int over = (pc.cnt + own_mult - 1) / own_mult * own_mult - pc.cnt;
+            if (pc.cnt > cap || (over != 0 && (pc.p0 + pc.cnt != row_windows || over > L - 1)))
+                return set_err_msg("gram: a group of the same-length packing reaches past the weight table's zero guard", 2);
             P.lane_piece[(size_t)pc.lane * 2] = (slot << gkmbs::META_SLOT_SHIFT) | ((uint32_t)(pc.p0 / cap) << gkmbs::META_PIECE_SHIFT);
         }
     }

@@ -163,6 +163,31 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : PK == 4 ? GKM_BS_WAVES : GKM_BS_PAC
         Alo[w] = A.rowplanes[(((size_t)tile * 3 + 1) * W + w) * 64 + lane];
         AV[w] = A.rowplanes[(((size_t)tile * 3 + 2) * W + w) * 64 + lane];
     }
+    /* ROW VALIDITY PER GROUP (same length, top-plane (L, d) only): the counting loop keeps the OR of the validity words of
+     * each group of BS_GRP words -- W / BS_GRP registers instead of W -- and applies it to the OR of the group's top planes
+     * (gkm_bitslice.h window_group_any_grouped): 3 ops per group instead of 5.  What it flags beyond the per-word form
+     * is a (bit row, group) in which a window nobody owns has <= d mismatches while another window of the five is owned.
+     * A trip evaluates all five windows of a pushed group anyway and tests m <= d per window; the extra records only have
+     * to add nothing, i.e. every window they bring in must read a zero row weight:
+     *   - a lane that does not finish its row owns A.cap windows, a multiple of five (gkm_pack.h own_mult), from lane
+     *     position 0: its groups are owned whole or not at all -- nothing extra.  Positions at or above A.cap, which
+     *     include everything the extension words' fiction touches (A.cap <= segment_capacity), are unowned whole groups;
+     *   - the lane that finishes its row owns positions 0 .. cnt - 1 with pi * A.cap + cnt = nB: only the group that holds
+     *     cnt - 1 is owned in part, and its unowned windows are the row's positions nB .. nB + 3 at most.  Their weight
+     *     bytes are among the L - 1 >= 4 zeros behind wt[nB - 1] in the positional table (POSTAB_PAD layout): they add 0;
+     *   - a lane without a piece has no validity bit at all.
+     * gkm_gram.hip plan_bitslice checks the packing against exactly these three statements before the launch.  The
+     * several-pieces variants keep per-word validity: their row weights are indexed by distance, with no zero guard. */
+    constexpr bool GROUP_VALID = UNIF && gkmbs::top_plane_serves(L, D);
+    uint32_t AVg[W / BS_GRP];
+    if constexpr (GROUP_VALID) {
+#pragma unroll
+        for (int g = 0; g < W / BS_GRP; g++) {
+            AVg[g] = AV[g * BS_GRP];
+#pragma unroll
+            for (int k = 1; k < BS_GRP; k++) AVg[g] |= AV[g * BS_GRP + k];
+        }
+    }
 
     /* one wavefront per workgroup: the LDS traffic of a wave is ordered, no barriers needed */
     /* (several pieces: the piece-start mask stays in a register of its lane and a trip fetches it by ds_bpermute_b32 -- the
@@ -253,7 +278,9 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : PK == 4 ? GKM_BS_WAVES : GKM_BS_PAC
          * What makes every window of a pushed group safe to evaluate without its hit bit:
          *   row side     the lanes of a same-length problem own window counts that are multiples of 5 (gkm_pack.h
          *                own_mult), so a group is owned whole or not at all; windows past the row's last l-mer (the
-         *                row's last lane) read the zero bytes behind the positional weight table;
+         *                row's last lane) read the zero bytes behind the positional weight table -- which is also what
+         *                lets the counting loop apply row validity per group (AVg above): the records that adds bring
+         *                in such windows only;
          *   column side  the packed strands are CYCLIC (k_pack_strands), so a window that runs over the strand's end is
          *                the very l-mer the cyclic bit planes of the counting loop compared; it is not an l-mer of the
          *                sequence and reads a zero weight (the L - 1 zero bytes); a window PAST the end (q + k >= T) is
@@ -403,7 +430,10 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : PK == 4 ? GKM_BS_WAVES : GKM_BS_PAC
                         /* per group the OR of its words' hits, straight from the count (gkm_bitslice.h: where the bias
                          * allows, the top plane of a count of matches -- one op per word for threshold, validity and OR) */
                         uint32_t grp_any[W / BS_GRP];
-                        window_group_any<W, L, D, BS_GRP>(Ahi, Alo, AV, bh + u, bl + u, grp_any);
+                        if constexpr (GROUP_VALID) /* a superset per group: see AVg above */
+                            window_group_any_grouped<W, L, D, BS_GRP>(Ahi, Alo, AVg, bh + u, bl + u, grp_any);
+                        else
+                            window_group_any<W, L, D, BS_GRP>(Ahi, Alo, AV, bh + u, bl + u, grp_any);
                         /* the shift's origin word: the delta field is wave-uniform, so it is shifted into place by the
                          * scalar unit (the empty asm pins it to an SGPR) and ORed in at full rate; left alone, hipcc emits
                          * one half-rate v_lshl_or_b32 with the shift as an SGPR operand.  The second group's `| w0` is one
