@@ -16,6 +16,8 @@
  *                          gkmhip_ism_block and gkmhip_hyp_block, both through ism_launch<HYP>
  *   gkm_lmer.hip           l-mer weight tables of a trained model and scores from them (k_lmer_weights, k_lmer_score),
  *                          gkmhip_lmer_weights, gkmhip_lmer_score
+ *   gkm_limp.hip           per-base importance tables of a trained model and explanations from them (k_lmer_importance,
+ *                          k_lmer_explain, k_lmer_hyp), gkmhip_lmer_importance, gkmhip_lmer_explain, gkmhip_lmer_hyp
  *   gkm_scan.hip           every window of a long sequence scored from an l-mer weight table (k_scan_lmers, k_scan_profiles,
  *                          k_scan_score), gkmhip_scan_lmers, gkmhip_scan_profiles, gkmhip_scan_score, gkmhip_scan_group
  */

@@ -125,6 +125,12 @@ def load():
     L.gkmhip_lmer_weights.argtypes = (vp, vp, vp, vp, i32, ctypes.c_uint32, ctypes.c_uint32, vp, vp)
     L.gkmhip_lmer_score.restype = i32
     L.gkmhip_lmer_score.argtypes = (vp, i32, i32, vp, vp, vp)
+    L.gkmhip_lmer_importance.restype = i32
+    L.gkmhip_lmer_importance.argtypes = (vp, vp, vp, vp, i32, ctypes.c_uint32, ctypes.c_uint32, vp, vp)
+    L.gkmhip_lmer_explain.restype = i32
+    L.gkmhip_lmer_explain.argtypes = (vp, i32, i32, vp, vp, vp, vp)
+    L.gkmhip_lmer_hyp.restype = i32
+    L.gkmhip_lmer_hyp.argtypes = (vp, i32, i32, vp, vp, vp)
     L.gkmhip_scan_lmers.restype = i32
     L.gkmhip_scan_lmers.argtypes = (vp, vp, vp, i64, vp, vp)
     L.gkmhip_scan_profiles.restype = i32
@@ -457,6 +463,33 @@ class GramContext:
         doubles indexed by code (include/gkm_hip.h gkmhip_lmer_score)."""
         self._chk(self.lib.gkmhip_lmer_score(self.handle, int(col_begin), int(col_end), W_ptr, out_ptr, stream),
                   "gkmhip_lmer_score")
+
+    def lmer_importance(self, share, v_ptr, cv_ptr, nv, u_begin, u_end, V_ptr, stream=0):
+        """Per-base importance V[(u - u_begin) L + i] for the codes [u_begin, u_end) from nv canonical classes (v_ptr:
+        device uint32 codes, cv_ptr: device doubles) into V_ptr: share = d + 1 host doubles (include/gkm_hip.h
+        gkmhip_lmer_importance)."""
+        share = np.ascontiguousarray(share, dtype=np.float64)
+        if len(share) != self.d + 1:
+            raise GkmError("lmer_importance: share needs d + 1 = %d values" % (self.d + 1))
+        if not 0 <= int(u_begin) < int(u_end) <= 4 ** self.L:
+            raise GkmError("lmer_importance: the code range must satisfy 0 <= u_begin < u_end <= 4^L")
+        if int(nv) < 0:
+            raise GkmError("lmer_importance: nv must not be negative")
+        self._chk(self.lib.gkmhip_lmer_importance(self.handle, share.ctypes.data, v_ptr, cv_ptr, int(nv), int(u_begin),
+                                                  int(u_end), V_ptr, stream), "gkmhip_lmer_importance")
+
+    def lmer_explain(self, col_begin, col_end, V_ptr, xscale_ptr, E_ptr, stream=0):
+        """xscale_j sum_i w_j[t-i] V[code(u_{t-i})][i] for every base t of the uploaded sequences [col_begin, col_end)
+        into E_ptr (the bases of the range back to back): V_ptr = 4^L x L device doubles, xscale_ptr = one device double
+        per sequence (include/gkm_hip.h gkmhip_lmer_explain)."""
+        self._chk(self.lib.gkmhip_lmer_explain(self.handle, int(col_begin), int(col_end), V_ptr, xscale_ptr, E_ptr,
+                                               stream), "gkmhip_lmer_explain")
+
+    def lmer_hyp(self, col_begin, col_end, V_ptr, R_ptr, stream=0):
+        """The same sum, unscaled, with base t set to each of A, C, G, T into R_ptr (4 doubles per base of the range;
+        include/gkm_hip.h gkmhip_lmer_hyp)."""
+        self._chk(self.lib.gkmhip_lmer_hyp(self.handle, int(col_begin), int(col_end), V_ptr, R_ptr, stream),
+                  "gkmhip_lmer_hyp")
 
     def scan_lmers(self, codes_ptr, valid_ptr, nbases, lm_ptr, stream=0):
         """One word per forward l-mer of `nbases` device base codes into lm_ptr (nbases - L + 1 uint32): the code, bit 31

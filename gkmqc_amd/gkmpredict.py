@@ -28,7 +28,11 @@ The other half of a gkm-SVM next to the cross-validation of `gkmsvm.py` (the cou
     and serves `explain`, `ism`, `hypothetical` and `weights` like a C-SVC model;
   * `scan` takes a weight table along sequences of any length and scores every window of W bases at a stride (DESIGN.md
     §5i, gkmhip_scan_profiles and gkmhip_scan_score): `predict-table`'s value for each window cut out, bit for bit, with
-    the self norms of overlapping windows counted together; windows over a non-ACGT character have no score.
+    the self norms of overlapping windows counted together; windows over a non-ACGT character have no score;
+  * `importance-table` folds a model (not RBF, not k = 0) into one value per (l-mer, offset) (DESIGN.md §5j,
+    gkmhip_lmer_importance); `explain-table` and `hypothetical-table` serve `explain`'s and `hypothetical`'s values from
+    it, up to rounding, with only the queries uploaded: their self norms, then L gathers per base (gkmhip_lmer_explain)
+    or 4 L (gkmhip_lmer_hyp).
 
     python -m gkmqc_amd.gkmpredict train [-t -L -k -d -M -H -G -C -e -u] pos.fa neg.fa model.txt
     python -m gkmqc_amd.gkmpredict train-svr [-t -L -k -d -M -H -G -C -p -e -u] seqs.fa targets.txt model.txt
@@ -39,6 +43,9 @@ The other half of a gkm-SVM next to the cross-validation of `gkmsvm.py` (the cou
     python -m gkmqc_amd.gkmpredict weights model.txt weights.txt
     python -m gkmqc_amd.gkmpredict predict-table [--block Qb] query.fa weights.txt out.txt
     python -m gkmqc_amd.gkmpredict scan --width W [--stride s] [--chunk B] seqs.fa weights.txt out.bedgraph
+    python -m gkmqc_amd.gkmpredict importance-table model.txt table.npz
+    python -m gkmqc_amd.gkmpredict explain-table [--block Qb] query.fa table.npz out.txt
+    python -m gkmqc_amd.gkmpredict hypothetical-table [--block Qb] query.fa table.npz out.txt
 """
 import argparse
 import logging
@@ -1000,6 +1007,200 @@ def score_with_table(table, fasta_or_sequences, device=0, block=None, on_block=N
     return names, out
 
 
+# ------------------------------------------------------------------ per-base importance tables
+IMPORTANCE_FORMAT = "gkmqc-lmer-importance-1"
+_IMPORTANCE_INTS = ("kernel_type", "L", "k", "d", "M")
+_IMPORTANCE_FLOATS = ("H", "rho")
+_IMPORTANCE_KEYS = ("format",) + _IMPORTANCE_INTS + _IMPORTANCE_FLOATS + ("V",)
+
+
+class LmerImportanceTable:
+    """A trained model folded into one value per (l-mer, offset): V (float64, (4^L, L), indexed by code
+    and by the offset from the l-mer's first base; V[rc(u), L-1-i] == V[u, i] and V.sum(1) is the weight table's W) plus
+    what explaining needs -- the kernel parameters and rho; no support vectors."""
+
+    def __init__(self, V, kernel_type, L, k, d, M, H, rho):
+        self.kernel_type, self.L, self.k, self.d, self.M = int(kernel_type), int(L), int(k), int(d), int(M)
+        self.H, self.rho = float(H), float(rho)
+        bad = dv.check_parameters(self.kernel_type, self.L, self.k, self.d)
+        if bad:
+            raise ModelError("kernel parameters rejected: %s" % bad)
+        check_table_model(self, "importance table")
+        check_explainable(self, "importance table")
+        if not 0 <= self.M <= 255 or not (np.isfinite(self.H) and np.isfinite(self.rho)):
+            raise ModelError("M must lie in 0..255, H and rho must be finite")
+        self.V = np.ascontiguousarray(V, dtype=np.float64)
+        if self.V.shape != (4 ** self.L, self.L):
+            raise ModelError("an importance table for L = %d needs (4^L, L) = (%d, %d) values"
+                             % (self.L, 4 ** self.L, self.L))
+
+    def kernel_params(self):
+        return (self.kernel_type, self.L, self.k, self.d, self.M, self.H, 1.0)
+
+    def save(self, path):
+        """Write the table file (format: INTEGRATION.md §5b) to exactly `path`: an uncompressed .npz with the format
+        tag, the scalar parameters and the rows of the canonical l-mers in ascending order (the other half follows from
+        V[rc(u), L-1-i] == V[u, i])."""
+        head = {key: np.int64(getattr(self, key)) for key in _IMPORTANCE_INTS}
+        head.update({key: np.float64(getattr(self, key)) for key in _IMPORTANCE_FLOATS})
+        tmp = path + ".tmp"
+        with open(tmp, "wb") as f:
+            np.savez(f, format=np.array(IMPORTANCE_FORMAT), V=self.V[canonical_codes(self.L)], **head)
+        os.replace(tmp, path)
+
+
+def load_importance_table(path):
+    """Read a table file written by LmerImportanceTable.save; anything malformed raises ModelError with the reason."""
+    with open(path, "rb") as f:
+        try:
+            with np.load(f, allow_pickle=False) as z:
+                got = {key: z[key] for key in z.files}
+        except Exception as e:   # (not a zip archive, a truncated member, a pickled object, ...)
+            raise ModelError("%s: not an importance table file: %s" % (path, e))
+    missing = [key for key in _IMPORTANCE_KEYS if key not in got]
+    if missing:
+        raise ModelError("%s: missing key(s): %s" % (path, ", ".join(missing)))
+    extra = [key for key in got if key not in _IMPORTANCE_KEYS]
+    if extra:
+        raise ModelError("%s: key(s) %s do not belong to format %s" % (path, ", ".join(extra), IMPORTANCE_FORMAT))
+    fmt = got["format"]
+    if fmt.shape != () or fmt.dtype.kind != "U" or str(fmt) != IMPORTANCE_FORMAT:
+        raise ModelError("%s: format %r, expected %r" % (path, fmt.tolist(), IMPORTANCE_FORMAT))
+    val = {}
+    for key, kinds in [(key, "iu") for key in _IMPORTANCE_INTS] + [(key, "f") for key in _IMPORTANCE_FLOATS]:
+        if got[key].shape != () or got[key].dtype.kind not in kinds:
+            raise ModelError("%s: %s must be one %s" % (path, key, "integer" if kinds == "iu" else "float"))
+        val[key] = got[key].item()
+    L = val["L"]
+    bad = dv.check_parameters(val["kernel_type"], L, val["k"], val["d"])
+    if bad:
+        raise ModelError("%s: kernel parameters rejected: %s" % (path, bad))
+    can = canonical_codes(L)
+    Vc = got["V"]
+    if Vc.dtype != np.float64 or Vc.shape != (len(can), L):
+        raise ModelError("%s: V is %s %r, expected float64 (%d, %d): one row per canonical l-mer of L = %d"
+                         % (path, Vc.dtype, Vc.shape, len(can), L, L))
+    rc = lmer_rc(can, L)
+    pal = can == rc
+    if Vc[pal].tobytes() != Vc[pal][:, ::-1].tobytes():
+        raise ModelError("%s: the row of a palindromic l-mer is not its own mirror image" % path)
+    V = np.empty((4 ** L, L), dtype=np.float64)
+    V[rc] = Vc[:, ::-1]
+    V[can] = Vc
+    try:
+        return LmerImportanceTable(V, val["kernel_type"], L, val["k"], val["d"], val["M"], val["H"], val["rho"])
+    except ModelError as e:
+        raise ModelError("%s: %s" % (path, e))
+
+
+def lmer_importance(model, device=0, on_piece=None):
+    """The per-base importance table of `model` -> LmerImportanceTable:
+
+        V(u, i) = sum over classes (v, cv) of cv (share[m(u, v)] [u[i] == v[i]] + share[m(u, rc v)] [u[i] == rc(v)[i]])
+
+    with lmer_weights' classes and self norms and explain's shares, so that explain(x)[t] = sum_i w_x[t-i] V(u_{t-i}, i)
+    / sq_x up to rounding.  The models `explain` serves (no RBF, no k = 0), checked before the device is touched.  V comes
+    from k_lmer_importance over all 4^L codes in pieces of TABLE_PIECE.  on_piece(dict) (measurements): called after
+    every piece with its codes, kernel milliseconds (HIP events) and l-mer comparisons."""
+    check_explainable(model, "lmer_importance")
+    import torch
+    S, L, d = model.n_sv, model.L, model.d
+    ctx = dv.cached_context(*model.kernel_params(), device=device)
+    dev = torch.device("cuda", device)
+    c = dv.mismatch_weights(model.kernel_type, L, model.k)[:d + 1]
+    share = explain_shares(model)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        ctx.set_sequences(model.flat_seqs(), stream)
+        sq = torch.empty(S, dtype=torch.float64, device=dev)
+        _exact_norms(ctx, S, c, sq, stream)
+        v, cv = lmer_classes(model, sq.cpu().numpy())
+        d_v = torch.from_numpy(v.view(np.int32)).to(dev)
+        d_cv = torch.from_numpy(cv).to(dev)
+        V = torch.empty((4 ** L, L), dtype=torch.float64, device=dev)
+        for u0 in range(0, 4 ** L, TABLE_PIECE):
+            u1 = min(4 ** L, u0 + TABLE_PIECE)
+            ctx.lmer_importance(share, d_v.data_ptr(), d_cv.data_ptr(), len(v), u0, u1, V.data_ptr() + 8 * L * u0, stream)
+            if on_piece is not None:
+                on_piece(dict(codes=u1 - u0, classes=len(v), kernel_ms=ctx.last_kernel_ms(),
+                              comparisons=ctx.last_comparisons(), kernel=ctx.last_kernel_name()))
+        Vh = V.cpu().numpy()
+    return LmerImportanceTable(Vh, model.kernel_type, L, model.k, d, model.M, model.H, model.rho)
+
+
+def default_imptable_block(max_len, d=None, budget=BLOCK_BYTES):
+    """Queries per block of explain_with_table (d None) or hypothetical_with_table: the upload's per-sequence device
+    tables and the per-base output -- for the hypothetical table also the mutants' self profiles (4 (d + 1) int64 per
+    base) and the finishing temporaries -- within `budget` bytes, and at most 32 768 (as default_table_block)."""
+    per_base = 40 if d is None else 8 * (4 * (int(d) + 1) + 28)
+    return _fit_block(max_len, per_base, budget, cap=1 << 15)
+
+
+def explain_with_table(itable, fasta_or_sequences, device=0, block=None, on_block=None):
+    """Per-base importance from an importance table for a FASTA file (or a list / FlatSequences of base codes) ->
+    (names, [float64 array of one value per base, per query]): sum_i w_x[t-i] V(u_{t-i}, i) / sq_x, `explain`'s value up
+    to rounding.  Only the queries are uploaded: per block the exact self norms (gkmhip_self_profiles) and L gathers per
+    base (k_lmer_explain); bit-identical for every block size.  on_block(dict) (measurements): called after every block
+    with its size, k_lmer_explain's milliseconds and the block's wall time."""
+    import torch
+    seqs, names = _as_queries(fasta_or_sequences)
+    check_queries(itable, seqs)
+    blocks = _Blocks(itable, seqs, device, block, default_imptable_block(_longest(seqs)), exact=True)
+    ctx, sq, dev = blocks.ctx, blocks.sq, blocks.dev
+    out = []
+    with torch.cuda.device(dev):
+        V = torch.from_numpy(itable.V).to(dev)
+        E = torch.empty(blocks.most_bases(), dtype=torch.float64, device=dev)
+        for b in blocks:
+            xscale = 1.0 / sq[:b.qb]
+            ctx.lmer_explain(0, b.qb, V.data_ptr(), xscale.data_ptr(), E.data_ptr(), blocks.stream)
+            out.extend(b.split(E[:b.nb].cpu().numpy()))
+            if on_block is not None:
+                on_block(dict(queries=b.qb, explain_kernel_ms=ctx.last_kernel_ms(), gathers=ctx.last_comparisons(),
+                              kernel=ctx.last_kernel_name(), wall_ms=(time.perf_counter() - b.t0) * 1e3))
+    return names, out
+
+
+def hypothetical_with_table(itable, fasta_or_sequences, device=0, block=None, on_block=None):
+    """Hypothetical importance from an importance table for a FASTA file (or a list / FlatSequences of base codes) ->
+    (names, [float64 array (T, 4) per query], columns A, C, G, T): hyp[t, b] = explain_with_table(y)[t] for y = x with
+    base t set to b, bit for bit (hyp[t, x[t]] = explain_with_table(x)[t]), and `hypothetical`'s value up to rounding.
+    Only the queries are uploaded: per block their exact self norms, every mutant's self profile
+    (gkmhip_ism_self_profiles) and 4 L gathers per base (k_lmer_hyp); bit-identical for every block size.
+    on_block(dict) (measurements): called after every block with its size, k_lmer_hyp's milliseconds, the self-profile
+    kernels' milliseconds and the block's wall time."""
+    import torch
+    seqs, names = _as_queries(fasta_or_sequences)
+    check_queries(itable, seqs)
+    d = itable.d
+    blocks = _Blocks(itable, seqs, device, block, default_imptable_block(_longest(seqs), d), exact=True)
+    ctx, sq, dev, stream = blocks.ctx, blocks.sq, blocks.dev, blocks.stream
+    c = blocks.c
+    out = []
+    with torch.cuda.device(dev):
+        V = torch.from_numpy(itable.V).to(dev)
+        most = blocks.most_bases()
+        R = torch.empty((most, 4), dtype=torch.float64, device=dev)
+        prof = torch.empty((most, 4, d + 1), dtype=torch.int64, device=dev)
+        for b in blocks:
+            qb, nb = b.qb, b.nb
+            ctx.ism_self_profiles(0, qb, prof.data_ptr(), stream)
+            self_ms = ctx.last_kernel_ms() if on_block is not None else None
+            xscale = 1.0 / sq[:qb]
+            ctx.lmer_hyp(0, qb, V.data_ptr(), R.data_ptr(), stream)
+            # the mutant columns times 1 / sqrt(G(y, y)); the own column times explain's xscale (as `hypothetical`)
+            scale = 1.0 / _mutant_norms_sq(prof[:nb], c).sqrt_()
+            own = torch.from_numpy(b.codes.astype(np.int64)).to(dev)
+            per = torch.from_numpy(np.diff(b.qoff)).to(dev)
+            scale.scatter_(1, own[:, None], torch.repeat_interleave(xscale, per)[:, None])
+            out.extend(b.split((R[:nb] * scale).cpu().numpy()))
+            if on_block is not None:
+                on_block(dict(queries=qb, hyp_kernel_ms=ctx.last_kernel_ms(), gathers=ctx.last_comparisons(),
+                              kernel=ctx.last_kernel_name(), self_kernels_ms=self_ms,
+                              wall_ms=(time.perf_counter() - b.t0) * 1e3))
+    return names, out
+
+
 # ------------------------------------------------------------------ scanning long sequences
 SCAN_MAX_WIDTH = 2047     # a window is a query of its own: the longest sequence the kernels' norms are defined for
 _WHITESPACE = np.array([9, 10, 11, 12, 13, 32], dtype=np.uint8)
@@ -1224,6 +1425,15 @@ def build_parser():
     n.add_argument("--stride", type=int, default=1, help="bases between window starts (default: 1)")
     n.add_argument("--chunk", type=int, default=None, help="bases per device chunk (default: from device memory)")
     _add_arguments(n, "seqs_fa", "weights", "output", block=False)
+    i = sub.add_parser("importance-table", help="fold a model into its per-base importance table: one value per (l-mer, "
+                                                "offset), a binary .npz file")
+    _add_arguments(i, "model", "output", block=False)
+    e = sub.add_parser("explain-table", help="per-base importance of the sequences of query.fa from an importance "
+                                             "table: name<TAB>v0,v1,... per line (the explain format)")
+    _add_arguments(e, "query_fa", "table", "output")
+    y = sub.add_parser("hypothetical-table", help="hypothetical importance of the sequences of query.fa from an "
+                                                  "importance table: name<TAB>4T values per line (the ism format)")
+    _add_arguments(y, "query_fa", "table", "output")
     return p
 
 
@@ -1256,6 +1466,8 @@ _QUERY_COMMANDS = {
     "ism": (ism, write_ism),
     "hypothetical": (hypothetical, write_ism),
     "predict-table": (score_with_table, write_scores),
+    "explain-table": (explain_with_table, write_explanation),
+    "hypothetical-table": (hypothetical_with_table, write_ism),
 }
 
 
@@ -1288,6 +1500,10 @@ def main(argv=None):
             m = load(a.model)
             check_table_model(m)
             lmer_weights(m, a.device).save(a.output)
+        elif a.cmd == "importance-table":
+            m = load(a.model)
+            check_explainable(m, "importance-table")
+            lmer_importance(m, a.device).save(a.output)
         elif a.cmd == "scan":
             if not os.path.isfile(a.seqs_fa):
                 raise ModelError("cannot read %s" % a.seqs_fa)
@@ -1305,7 +1521,12 @@ def main(argv=None):
                 raise ModelError("--block must be at least 1")
             if not os.path.isfile(a.query_fa):
                 raise ModelError("cannot read %s" % a.query_fa)
-            m = load_lmer_table(a.weights) if a.cmd == "predict-table" else load(a.model)
+            if a.cmd == "predict-table":
+                m = load_lmer_table(a.weights)
+            elif a.cmd in ("explain-table", "hypothetical-table"):
+                m = load_importance_table(a.table)
+            else:
+                m = load(a.model)
             names, values = compute(m, a.query_fa, a.device, a.block)
             tmp = a.output + ".tmp"
             write(tmp, names, values)

@@ -204,6 +204,44 @@ int gkmhip_lmer_weights(gkmhip_ctx *ctx, const double *c, const uint32_t *v, con
  * k_lmer_score. */
 int gkmhip_lmer_score(gkmhip_ctx *ctx, int col_begin, int col_end, const double *W, double *out, void *stream);
 
+/* Per-base importance table: for every code u of [u_begin, u_end) and offset i = 0..L-1 (offset 0 is the
+ * l-mer's first base, in the highest pair),
+ *   V[(u - u_begin) L + i] = sum_{j ascending} cv[j] * (tf + tr),   tf = share[m(u, v[j])] if that mismatch count is <= d
+ *                                                                   and base i of u equals base i of v[j], else 0.0,
+ *                                                                   tr the same for rc(v[j]),
+ * the sum from 0.0 in that order whatever the range, the launch or the run (no atomics), so V[rc(u)][L-1-i] and V[u][i]
+ * are bit-identical.  With (v, cv) the classes of gkmhip_lmer_weights and share[m] = c[m] / (L - m), sum_i V[u][i] is
+ * that table's W[u] and explain(x)[t] = sum_i w_x[t-i] V[u_{t-i}][i] / sq_x.  L and d are the context's; no sequences
+ * need be uploaded.
+ *   share HOST, d + 1 doubles (tests pass unit vectors to count single mismatch classes);
+ *   v     DEVICE, nv l-mer codes; cv DEVICE, nv doubles;
+ *   V     DEVICE, (u_end - u_begin) L doubles, row-major; nothing else is written.
+ * 0 <= u_begin < u_end <= 4^L.  Work is enqueued on `stream`; last_kernel_ms / last_comparisons (2 nv (u_end - u_begin))
+ * / last_kernel_name describe k_lmer_importance. */
+int gkmhip_lmer_importance(gkmhip_ctx *ctx, const double *share, const uint32_t *v, const double *cv, int nv,
+                           uint32_t u_begin, uint32_t u_end, double *V, void *stream);
+
+/* Explanations from an importance table: for every uploaded sequence j of [col_begin, col_end) and each of its bases t,
+ *   E[off[j] - off[col_begin] + t] = xscale[j - col_begin] * sum_{i ascending} w_j[t-i] V[code(u_{t-i}) L + i]
+ * over the offsets i = 0..L-1 whose l-mer t - i exists (the context's forward l-mer table), from 0.0.  One thread per
+ * base and a fixed order: bit-identical whatever range or neighbours the sequence has.
+ *   V      DEVICE, 4^L x L doubles (gkmhip_lmer_importance over all codes);
+ *   xscale DEVICE, col_end - col_begin doubles (explaining: 1 / sqnorm_j);
+ *   E      DEVICE, one double per base of the range.
+ * Work is enqueued on `stream`; last_kernel_ms / last_comparisons (the values gathered, L per l-mer) / last_kernel_name
+ * describe k_lmer_explain. */
+int gkmhip_lmer_explain(gkmhip_ctx *ctx, int col_begin, int col_end, const double *V, const double *xscale, double *E,
+                        void *stream);
+
+/* Raw hypothetical importance from an importance table: for sequence j of the range, each base t and each base b (0..3),
+ *   R[4 (off[j] - off[col_begin] + t) + b] = sum_{i ascending} w_j[t-i] V[code(u_{t-i} with base i set to b) L + i],
+ * gkmhip_lmer_explain's sum (unscaled) of the mutant y = x_j with base t set to b, at t; at b = x_j[t] that of x_j itself,
+ * bit for bit.
+ *   V DEVICE, 4^L x L doubles; R DEVICE, 4 doubles per base of the range.
+ * Work is enqueued on `stream`; last_kernel_ms / last_comparisons (the values gathered, 4 L per l-mer) / last_kernel_name
+ * describe k_lmer_hyp. */
+int gkmhip_lmer_hyp(gkmhip_ctx *ctx, int col_begin, int col_end, const double *V, double *R, void *stream);
+
 /* ---- scanning a long sequence with an l-mer weight table (gkm_scan.hip) ----
  * The score of every window of `width` bases (L <= width <= 2047) at a stride, each as if the window were a sequence of
  * its own.  The long sequence does not go through gkmhip_set_sequences: these calls take the context for L and d only,
