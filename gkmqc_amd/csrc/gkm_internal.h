@@ -20,6 +20,8 @@
  *                          k_lmer_explain, k_lmer_hyp), gkmhip_lmer_importance, gkmhip_lmer_explain, gkmhip_lmer_hyp
  *   gkm_scan.hip           every window of a long sequence scored from an l-mer weight table (k_scan_lmers, k_scan_profiles,
  *                          k_scan_score), gkmhip_scan_lmers, gkmhip_scan_profiles, gkmhip_scan_score, gkmhip_scan_group
+ *   gkm_delta.hip          variant effects from an l-mer weight table: every SNV of every position and a list of variants
+ *                          (k_delta_sat, k_delta_variants), gkmhip_delta_sat, gkmhip_delta_variants
  */
 #ifndef GKM_INTERNAL_H
 #define GKM_INTERNAL_H
@@ -157,6 +159,8 @@ struct gkmhip_ctx {
     /* gkmhip_ism_block: the per-tile G of its chunks; gkmhip_ism_self_profiles: the queries' own profiles P_m(x, x) */
     DevBuf<double> ism_gpart;
     DevBuf<int64_t> ism_pself;
+    /* gkmhip_delta_variants: the alternate bases of the call (its variant table goes through upload_rows) */
+    DevBuf<uint8_t> delta_alt;
 };
 
 /* the pair of events the next Gram kernel is bracketed by (gkm_context.hip) */

@@ -139,6 +139,10 @@ def load():
     L.gkmhip_scan_score.argtypes = (vp, vp, i64, vp, i32, i32, i64, vp, vp, vp)
     L.gkmhip_scan_group.restype = i32
     L.gkmhip_scan_group.argtypes = (vp, i32, i32)
+    L.gkmhip_delta_sat.restype = i32
+    L.gkmhip_delta_sat.argtypes = (vp, vp, i64, i64, i64, vp, vp, vp)
+    L.gkmhip_delta_variants.restype = i32
+    L.gkmhip_delta_variants.argtypes = (vp, vp, vp, i64, vp, i32, vp, i64, vp, vp, vp)
     L.gkmhip_ism_self_profiles.restype = i32
     L.gkmhip_ism_self_profiles.argtypes = (vp, i32, i32, vp, vp)
     L.gkmhip_self_profiles.restype = i32
@@ -511,6 +515,23 @@ class GramContext:
     def scan_group(self, width, stride):
         """Windows per stretch of k_scan_profiles for (L, width, stride); 0 where the scan refuses them."""
         return self.lib.gkmhip_scan_group(self.handle, int(width), int(stride))
+
+    def delta_sat(self, lm_ptr, nlm, t_begin, t_end, W_ptr, out_ptr, stream=0):
+        """Every SNV of the positions [t_begin, t_end) of the bases the nlm words at lm_ptr cover -> out_ptr, (t_end -
+        t_begin) x 4 doubles: the change in the summed W of the l-mers over the position (include/gkm_hip.h
+        gkmhip_delta_sat)."""
+        self._chk(self.lib.gkmhip_delta_sat(self.handle, lm_ptr, int(nlm), int(t_begin), int(t_end), W_ptr, out_ptr, stream),
+                  "gkmhip_delta_sat")
+
+    def delta_variants(self, lm_ptr, codes_ptr, nbases, var, alt, W_ptr, out_ptr, stream=0):
+        """One delta per row (pos, ref_len, alt_off, alt_len) of the HOST int32 array var, alt the HOST uint8 array of all
+        alternate bases; lm_ptr / codes_ptr: the device words and codes of the nbases bases (include/gkm_hip.h
+        gkmhip_delta_variants)."""
+        var = np.ascontiguousarray(var, dtype=np.int32).reshape(-1, 4)
+        alt = np.ascontiguousarray(alt, dtype=np.uint8)
+        self._chk(self.lib.gkmhip_delta_variants(self.handle, lm_ptr, codes_ptr, int(nbases), var.ctypes.data, len(var),
+                                                 alt.ctypes.data if len(alt) else None, len(alt), W_ptr, out_ptr, stream),
+                  "gkmhip_delta_variants")
 
     def self_norms(self, sq_ptr, stream=0):
         self._chk(self.lib.gkmhip_self_norms(self.handle, sq_ptr, stream), "gkmhip_self_norms")

@@ -269,6 +269,34 @@ int gkmhip_scan_score(gkmhip_ctx *ctx, const uint32_t *lm, int64_t nlm, const ui
 /* windows per stretch of k_scan_profiles: a function of (L, width, stride) only; 0 for arguments the scan refuses */
 int gkmhip_scan_group(const gkmhip_ctx *ctx, int width, int stride);
 
+/* ---- variant effects from an l-mer weight table: deltaSVM (gkm_delta.hip) ----
+ * The change in the summed weights of the l-mers a variant touches.  For a base string z with n = len(z) - L + 1 l-mers
+ * u_0 .. u_{n-1}, S(z) = ((0.0 + W[u_0]) + W[u_1]) + ... + W[u_{n-1}] in plain double additions, 0.0 when n < 1.  No
+ * positional weights enter (a variant has no window).  Like the scan calls these take the context for L only and plain
+ * DEVICE pointers unless said otherwise; W: DEVICE, 4^L doubles; lm: the words of gkmhip_scan_lmers over the same bases.
+ * Every value is one lane's own chain of additions: it depends on W and the bases around the variant only, not on the
+ * launch, the other variants or the run.
+ *
+ * gkmhip_delta_sat: every SNV of the positions [t_begin, t_end) of the nlm + L - 1 bases that lm covers:
+ *   out[(t - t_begin) * 4 + b] = S(context of t with base t replaced by b) - S(context of t),
+ * the context being the bases [max(0, t - (L-1)), min(nlm + L - 1, t + L)), whose l-mers are lm[max(0, t-L+1) ..
+ * min(t, nlm-1)]; the base at t is read from those words.  +0.0 at b = the base at t; all four NaN when a word of the
+ * context is flagged (bit 31).  out: (t_end - t_begin) x 4 doubles, 16-byte aligned.  last_comparisons: the W gathers
+ * made (four per l-mer over a position); last_kernel_ms / last_kernel_name describe k_delta_sat. */
+#define GKMHIP_DELTA_MAX_ALLELE 255
+int gkmhip_delta_sat(gkmhip_ctx *ctx, const uint32_t *lm, int64_t nlm, int64_t t_begin, int64_t t_end, const double *W,
+                     double *out, void *stream);
+/* out[i] = S(x[a:pos] + alt_i + x[pos+r:e]) - S(x[a:e]) for variant i = (pos, r, alt_off, alt_len), four int32 in a
+ * row of var, replacing the r bases from pos by the alt_len bases alt[alt_off ..]; a = max(0, pos - (L-1)), e =
+ * min(nbases, pos + r + (L-1)); both alleles at most GKMHIP_DELTA_MAX_ALLELE bases, either may be empty.  var (nvar x 4)
+ * and alt (nalt base codes) are HOST arrays: every variant is checked against nbases and nalt before anything is
+ * launched (error 2 names the first that fails), and both are on the device when the call returns.  codes: DEVICE, nbases
+ * base codes 0..3; lm: DEVICE, their nbases - L + 1 words (not read, and may be NULL, when nbases < L).  Validity is the
+ * caller's: flags in lm are ignored (a variant over an invalid base has no value; gkmpredict.delta makes it NaN).
+ * last_comparisons: the W gathers made (the l-mers of both strings); last_* describe k_delta_variants. */
+int gkmhip_delta_variants(gkmhip_ctx *ctx, const uint32_t *lm, const uint8_t *codes, int64_t nbases, const int32_t *var,
+                          int nvar, const uint8_t *alt, int64_t nalt, const double *W, double *out, void *stream);
+
 /* sqnorm[i] = sqrt(G(i,i)) for all uploaded sequences (device array of n doubles), computed
  * from the diagonal band only (~1 % of the work of the whole matrix).  Replaces
  * gkmkernel_kernelfunc_sqnorm_single, src/libgkm.c:723-759. */
