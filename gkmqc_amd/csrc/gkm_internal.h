@@ -22,6 +22,10 @@
  *                          k_scan_score), gkmhip_scan_lmers, gkmhip_scan_profiles, gkmhip_scan_score, gkmhip_scan_group
  *   gkm_delta.hip          variant effects from an l-mer weight table: every SNV of every position and a list of variants
  *                          (k_delta_sat, k_delta_variants), gkmhip_delta_sat, gkmhip_delta_variants
+ *   gkm_nullidx.hip        the genome window index of null-sequence sampling: window keys and flag planes, cell counts,
+ *                          a stable radix sort of the window starts (k_nullidx_keys, k_nullidx_hist, k_nix_*,
+ *                          k_nullidx_digits, k_nullidx_scatter), gkmhip_nullidx_keys, gkmhip_nullidx_cells,
+ *                          gkmhip_nullidx_sort, gkmhip_nullidx_tile, gkmhip_nullidx_scratch_bytes; needs no context
  */
 #ifndef GKM_INTERNAL_H
 #define GKM_INTERNAL_H

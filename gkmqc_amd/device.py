@@ -143,6 +143,16 @@ def load():
     L.gkmhip_delta_sat.argtypes = (vp, vp, i64, i64, i64, vp, vp, vp)
     L.gkmhip_delta_variants.restype = i32
     L.gkmhip_delta_variants.argtypes = (vp, vp, vp, i64, vp, i32, vp, i64, vp, vp, vp)
+    L.gkmhip_nullidx_tile.restype = i32
+    L.gkmhip_nullidx_tile.argtypes = ()
+    L.gkmhip_nullidx_scratch_bytes.restype = i64
+    L.gkmhip_nullidx_scratch_bytes.argtypes = (i64, i32)
+    L.gkmhip_nullidx_keys.restype = i32
+    L.gkmhip_nullidx_keys.argtypes = (i32, vp, i64, i32, vp, vp, vp, vp, vp)
+    L.gkmhip_nullidx_cells.restype = i32
+    L.gkmhip_nullidx_cells.argtypes = (i32, vp, i64, i32, vp, vp, i64, vp)
+    L.gkmhip_nullidx_sort.restype = i32
+    L.gkmhip_nullidx_sort.argtypes = (i32, vp, i64, i32, vp, vp, i64, vp)
     L.gkmhip_ism_self_profiles.restype = i32
     L.gkmhip_ism_self_profiles.argtypes = (vp, i32, i32, vp, vp)
     L.gkmhip_self_profiles.restype = i32
@@ -592,6 +602,89 @@ def cross_kernel(seqs, rows, kernel_type, L, k, d, M=50, H=50.0, gamma=1.0, devi
             return dict(K=G, sqnorm=sq, rows=rows, kernel=ctx.last_kernel_name())
     finally:
         ctx.close()
+
+
+# ------------------------------------------------------------------ the genome window index (no context)
+NULLIDX_MAX_WIDTH = 2047
+NULLIDX_NOKEY = 0xFFFFFFFF
+
+
+def nullidx_tile():
+    """Windows per workgroup of k_nullidx_keys (include/gkm_hip.h gkmhip_nullidx_tile)."""
+    return load().gkmhip_nullidx_tile()
+
+
+def nullidx_check(T, width):
+    """Raise for what the index refuses: a width outside 1..2047, 2^31 - 1 bytes or more."""
+    if not 1 <= int(width) <= NULLIDX_MAX_WIDTH:
+        raise GkmError("the window width must lie in 1..%d, not %d" % (NULLIDX_MAX_WIDTH, int(width)))
+    if int(T) >= 2 ** 31 - 1:
+        raise GkmError("a record of %d bytes is too long for the index (fewer than 2^31 - 1)" % int(T))
+
+
+def nullidx_build(raw, width, device=0, times=None):
+    """The window index of one chromosome on the GPU (include/gkm_hip.h gkmhip_nullidx_*).
+
+    raw: the record's FASTA letters, uint8, case kept, no line breaks; width: the window width t.
+    Returns dict(key=uint32 [max(0, T - t)] (NULLIDX_NOKEY where the window holds an N), pos=int32 [len], ptr=int32
+    [t + 1, t + 1], len=int, na / cg / rp = uint8 [(T + 7) // 8], numpy.packbits' layout).
+    times: a dict that receives the seconds of upload, keys, cells, sort and download, each ended by a synchronise."""
+    import time
+    import torch
+    L = load()
+    raw = np.ascontiguousarray(raw, dtype=np.uint8)
+    T, t = len(raw), int(width)
+    nullidx_check(T, t)
+    nwin, cells, nb = max(0, T - t), (t + 1) ** 2, (T + 7) // 8
+    if T == 0:
+        z = np.zeros(0, np.uint8)
+        return dict(key=np.zeros(0, np.uint32), pos=np.zeros(0, np.int32), ptr=np.zeros((t + 1, t + 1), np.int32), len=0,
+                    na=z, cg=z.copy(), rp=z.copy())
+    dev = torch.device("cuda", device)
+
+    def chk(rc, what):
+        if rc:
+            raise GkmError("%s failed (%d): %s" % (what, rc, L.gkmhip_last_error().decode()))
+
+    def lap(name, t0):
+        if times is not None:
+            torch.cuda.current_stream().synchronize()
+            times[name] = times.get(name, 0.0) + time.perf_counter() - t0
+        return time.perf_counter()
+
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        t0 = time.perf_counter()
+        d_seq = torch.from_numpy(raw if raw.flags.writeable else raw.copy()).to(dev)
+        t0 = lap("upload", t0)
+        nbp = (nb + 7) // 8 * 8     # (every plane starts 8-byte aligned)
+        d_planes = torch.empty((3, nbp), dtype=torch.uint8, device=dev)
+        d_key = torch.empty(max(nwin, 1), dtype=torch.int32, device=dev)
+        d_pos = torch.empty(max(nwin, 1), dtype=torch.int32, device=dev)
+        d_ptr = torch.empty(cells + 1, dtype=torch.int32, device=dev)
+        sbytes = L.gkmhip_nullidx_scratch_bytes(T, t)
+        if sbytes < 0:
+            raise GkmError("gkmhip_nullidx_scratch_bytes: " + L.gkmhip_last_error().decode())
+        d_scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
+        t0 = lap("allocate", t0)
+        chk(L.gkmhip_nullidx_keys(device, d_seq.data_ptr(), T, t, d_key.data_ptr(), d_planes[0].data_ptr(),
+                                  d_planes[1].data_ptr(), d_planes[2].data_ptr(), stream), "gkmhip_nullidx_keys")
+        t0 = lap("keys", t0)
+        chk(L.gkmhip_nullidx_cells(device, d_key.data_ptr(), T, t, d_ptr.data_ptr(), d_scratch.data_ptr(), sbytes, stream),
+            "gkmhip_nullidx_cells")
+        t0 = lap("cells", t0)
+        chk(L.gkmhip_nullidx_sort(device, d_key.data_ptr(), T, t, d_pos.data_ptr(), d_scratch.data_ptr(), sbytes, stream),
+            "gkmhip_nullidx_sort")
+        t0 = lap("sort", t0)
+        ptr = d_ptr.cpu().numpy()
+        n = int(ptr[cells])
+        planes = d_planes[:, :nb].cpu().numpy()
+        out = dict(key=d_key[:nwin].cpu().numpy().view(np.uint32), pos=d_pos[:n].cpu().numpy(),
+                   ptr=ptr[:cells].reshape(t + 1, t + 1).copy(), len=n,
+                   na=np.ascontiguousarray(planes[0]), cg=np.ascontiguousarray(planes[1]),
+                   rp=np.ascontiguousarray(planes[2]))
+        lap("download", t0)
+        return out
 
 
 _CTX_CACHE = {}

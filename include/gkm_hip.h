@@ -297,6 +297,33 @@ int gkmhip_delta_sat(gkmhip_ctx *ctx, const uint32_t *lm, int64_t nlm, int64_t t
 int gkmhip_delta_variants(gkmhip_ctx *ctx, const uint32_t *lm, const uint8_t *codes, int64_t nbases, const int32_t *var,
                           int nvar, const uint8_t *alt, int64_t nalt, const double *W, double *out, void *stream);
 
+/* ---- the genome window index of null-sequence sampling (gkm_nullidx.hip) ----
+ * One chromosome: seq = T raw FASTA bytes, line breaks removed, case kept; t = the window width, 1 <= t <= 2047.  Per byte:
+ * na (one of nN), cg (one of cgCG), rp (one of acgt); any other byte sets none.  The windows are the starts i in
+ * [0, T - t): nwin = max(0, T - t) of them (the start T - t is not one).  NA_i, CG_i, RP_i: the flags summed over
+ * [i, i + t).  A window is indexed iff NA_i == 0, under the key CG_i (t + 1) + RP_i.  These calls take no context: a
+ * device index, plain DEVICE pointers and a stream.  Each refuses t outside 1..2047 and T >= 2^31 - 1 (error 2) before
+ * it looks at anything else, and launches nothing then.  Every output is the same bytes on every run.
+ *
+ * gkmhip_nullidx_keys: key[i] for the nwin windows (0xFFFFFFFF where NA_i > 0) and the three flags of all T bases packed
+ * eight per byte, the first base in the highest bit, the last byte zero-padded: na, cg, rp of (T + 7) / 8 bytes each,
+ * 8-byte aligned.  One workgroup serves gkmhip_nullidx_tile() consecutive windows. */
+int gkmhip_nullidx_tile(void);
+int gkmhip_nullidx_keys(int device, const uint8_t *seq, int64_t T, int t, uint32_t *key, uint8_t *na, uint8_t *cg, uint8_t *rp,
+                        void *stream);
+/* the bytes of DEVICE scratch the two calls below ask for (the sort's two pairs of buffers and its digit counts), -1
+ * for arguments they refuse */
+int64_t gkmhip_nullidx_scratch_bytes(int64_t T, int t);
+/* ptr[c (t + 1) + r] = the number of indexed windows with a key below c (t + 1) + r (an empty cell carries the running
+ * total) and ptr[(t + 1)^2] = their number, len: (t + 1)^2 + 1 int32.  key: what gkmhip_nullidx_keys wrote for (T, t). */
+int gkmhip_nullidx_cells(int device, const uint32_t *key, int64_t T, int t, int32_t *ptr, void *scratch, int64_t scratch_bytes,
+                         void *stream);
+/* pos[0 .. len): the indexed window starts ordered by key, ascending inside a key; pos has room for nwin int32 and
+ * what lies behind len is the starts of the windows that hold an N.  A stable least-significant-digit radix sort over
+ * the key bits in which no atomic places an element. */
+int gkmhip_nullidx_sort(int device, const uint32_t *key, int64_t T, int t, int32_t *pos, void *scratch, int64_t scratch_bytes,
+                        void *stream);
+
 /* sqnorm[i] = sqrt(G(i,i)) for all uploaded sequences (device array of n doubles), computed
  * from the diagonal band only (~1 % of the work of the whole matrix).  Replaces
  * gkmkernel_kernelfunc_sqnorm_single, src/libgkm.c:723-759. */
