@@ -190,12 +190,13 @@ extern "C" void bsprobe_piece_valid(int b0, int nb, int cnt, int W, uint32_t *ou
  * P_out[i*(d+1)+m] for row i.  Returns 0, or a negative code naming the violated invariant. */
 template <int W, int L, int D>
 static int run_packed(const uint8_t *codes, const int64_t *off, const int *rows, int nrows, int col,
-                      const uint8_t *wd, int32_t *P_out, int *lanes_used)
+                      const uint8_t *wd, int32_t *P_out, int *lanes_used, int max_rows = gkmpack::MAX_ROWS, int own_mult = 1,
+                      int rider_w = 0)
 {
     using namespace gkmpack;
     std::vector<int> nwin((size_t)nrows);
     for (int i = 0; i < nrows; i++) nwin[(size_t)i] = (int)(off[rows[i] + 1] - off[rows[i]]) - L + 1;
-    const Packing P = pack_rows(rows, nwin.data(), nrows, W, L);
+    const Packing P = pack_rows(rows, nwin.data(), nrows, W, L, max_rows, 0, own_mult, rider_w);
     *lanes_used = (int)P.lanes_used;
     /* invariants: every window of every row owned exactly once; pieces inside their lane; all
      * pieces of a row in one tile; limits respected */
@@ -206,8 +207,8 @@ static int run_packed(const uint8_t *codes, const int64_t *off, const int *rows,
     for (const Piece &pc : P.pieces) {
         if (pc.b0 < 0 || pc.nb <= 0 || pc.b0 + pc.nb > 32) return -1;
         if (pc.cnt <= 0 || pc.cnt > pc.nb * W - (L - 1)) return -2;
-        if (pc.b0 != lane_bits[(size_t)pc.lane]) return -3; /* contiguous, in order */
-        lane_bits[(size_t)pc.lane] += pc.nb;
+        if (pc.rider ? pc.b0 < lane_bits[(size_t)pc.lane] : pc.b0 != lane_bits[(size_t)pc.lane]) return -3; /* contiguous, in order */
+        lane_bits[(size_t)pc.lane] = pc.b0 + pc.nb;
         if (++lane_np[(size_t)pc.lane] > MAX_PIECES) return -4;
         const int t = pc.lane / LANES;
         const int i = P.tile_out[(size_t)t * MAX_ROWS + pc.slot];
@@ -309,6 +310,101 @@ extern "C" int bsprobe_profile_packed(int W, int L, int d, const uint8_t *codes,
     PCASE(10, 11, 3) PCASE(20, 11, 3) PCASE(10, 12, 4) PCASE(20, 12, 4) PCASE(20, 10, 3) PCASE(10, 6, 2) PCASE(20, 6, 2)
     PCASE(5, 11, 3)
     return 1;
+}
+
+/* The same with the packing of a same-length launch that carries RIDERS (gkm_pack.h RIDER_B0; 64 residents per tile, pieces
+ * of whole groups of five, riders of RIDER_W windows): the rider pieces go through the lane program as pieces like any
+ * other -- their bits in the planes, their windows attributed to their row. */
+#define RCASE(WW, LL, DD) \
+    if (W == WW && L == LL && d == DD) \
+        return run_packed<WW, LL, DD>(codes, off, rows, nrows, col, wd, P, lanes_used, 64, 5, gkmpack::RIDER_W);
+extern "C" int bsprobe_profile_riders(int W, int L, int d, const uint8_t *codes, const int64_t *off, const int *rows,
+                                      int nrows, int col, const uint8_t *wd, int32_t *P, int *lanes_used)
+{
+    RCASE(10, 11, 3) RCASE(10, 10, 3)
+    return 1;
+}
+
+/* The packing of a same-length launch as gkm_gram.hip plan_bitslice asks for it (W = 10 words, 64 residents per tile, whole
+ * groups of five; rider_w = 0: without riders), for tests/test_rider_packing.py.  pieces_out[k][8] = lane, b0, nb, slot,
+ * row, p0, cnt, rider; tags_out[k] = the rider pieces' tag words (0 for residents); tile_rows_out[t][MAX_ROWS],
+ * tile_outs_out likewise; tile_nrows_out[t].  *check_out = same_length_packing_check.  Returns the number of pieces, or
+ * -1 if the arrays are too small; *ntiles_out the tiles. */
+extern "C" int packprobe_same_length(const int *rows, const int *nwin, int nrows, int L, int rider_w, int split_jump,
+                                     int *pieces_out, int max_pieces, int *tags_out, int *tile_rows_out, int *tile_outs_out,
+                                     int *tile_nrows_out, int max_tiles, int *ntiles_out, int *nriders_out, int *check_out)
+{
+    using namespace gkmpack;
+    const int W = 10, own_mult = 5;
+    const Packing P = pack_rows(rows, nwin, nrows, W, L, 64, split_jump, own_mult, rider_w);
+    *ntiles_out = P.ntiles;
+    *nriders_out = P.nriders;
+    if ((int)P.pieces.size() > max_pieces || P.ntiles > max_tiles) return -1;
+    std::vector<int> rw(P.pieces.size());
+    for (size_t k = 0; k < P.pieces.size(); k++) {
+        const Piece &pc = P.pieces[k];
+        int *o = pieces_out + k * 8;
+        o[0] = pc.lane; o[1] = pc.b0; o[2] = pc.nb; o[3] = pc.slot; o[4] = pc.row; o[5] = pc.p0; o[6] = pc.cnt; o[7] = pc.rider;
+        tags_out[k] = pc.rider ? (int)pack_rider_tag(pc.slot, pc.p0 - RIDER_B0 * W) : 0;
+        rw[k] = nwin[P.tile_out[(size_t)(pc.lane / LANES) * MAX_ROWS + pc.slot]];
+    }
+    for (int t = 0; t < P.ntiles; t++) {
+        tile_nrows_out[t] = P.tile_nrows[(size_t)t];
+        for (int r = 0; r < MAX_ROWS; r++) {
+            tile_rows_out[t * MAX_ROWS + r] = P.tile_row[(size_t)t * MAX_ROWS + r];
+            tile_outs_out[t * MAX_ROWS + r] = P.tile_out[(size_t)t * MAX_ROWS + r];
+        }
+    }
+    *check_out = same_length_packing_check(P, rw.data(), own_mult, rider_w, rider_w > 0 ? RIDER_SLOTS : 64);
+    return (int)P.pieces.size();
+}
+
+/* One lane's image as k_build_rowplanes builds it from the lane's pieces (pieces[k][8] as above): planes_out[3][W] (hi, lo,
+ * window ownership) and pk_out[2 W + 2], the 2-bit packed positions. */
+extern "C" void packprobe_lane_image(const uint8_t *codes, const int64_t *off, const int *pieces, int npieces, int W,
+                                     uint32_t *planes_out, uint32_t *pk_out)
+{
+    for (int x = 0; x < 3 * W; x++) planes_out[x] = 0u;
+    for (int x = 0; x < 2 * W + 2; x++) pk_out[x] = 0u;
+    for (int k = 0; k < npieces; k++) {
+        const int *pc = pieces + k * 8;
+        const uint8_t *seq = codes + off[pc[4]];
+        const int len = (int)(off[pc[4] + 1] - off[pc[4]]);
+        for (int w = 0; w < W; w++)
+            for (int b = 0; b < 32; b++) {
+                uint32_t bits[3];
+                for (int pl = 0; pl < 3; pl++) {
+                    bits[pl] = piece_bit(seq, len, pc[1], pc[2], pc[5], pc[6], b, w, W, pl);
+                    planes_out[pl * W + w] |= bits[pl] << b;
+                }
+                const int i = b * W + w;
+                pk_out[i >> 4] |= ((bits[0] << 1) | bits[1]) << (2 * (i & 15));
+            }
+    }
+}
+
+/* gkm_pack.h same_length_packing_check -- what plan_bitslice calls before a same-length launch -- on a layout handed in as
+ * pieces[k][8] (sorted by lane, then bit row), every row with row_windows l-mers: 0, or the code of the first failure */
+extern "C" int packprobe_check_layout(const int *pieces, int npieces, int row_windows, int L, int rider_w, int max_slots)
+{
+    gkmpack::Packing P;
+    P.W = 10;
+    P.L = L;
+    std::vector<int> rw((size_t)npieces, row_windows);
+    for (int k = 0; k < npieces; k++) {
+        const int *o = pieces + k * 8;
+        gkmpack::Piece pc;
+        pc.lane = o[0]; pc.b0 = o[1]; pc.nb = o[2]; pc.slot = o[3]; pc.row = o[4]; pc.p0 = o[5]; pc.cnt = o[6]; pc.rider = o[7];
+        P.pieces.push_back(pc);
+    }
+    return gkmpack::same_length_packing_check(P, rw.data(), 5, rider_w, max_slots);
+}
+
+extern "C" int packprobe_rider_tag_slot(int tag) { return rider_tag_slot((uint32_t)tag); }
+extern "C" int packprobe_rider_tag_pos(int tag) { return rider_tag_pos((uint32_t)tag); }
+extern "C" int packprobe_rider_consts(int which)
+{
+    return which == 0 ? gkmpack::RIDER_B0 : which == 1 ? gkmpack::RIDER_NB : which == 2 ? gkmpack::RIDER_W : gkmpack::RIDER_SLOTS;
 }
 
 /* ---- row sharding layout (gkm_shard.h) for tests/test_sharding.py ---- */

@@ -718,7 +718,8 @@ GKM_HD HitValue resolve_hit_packed(int b, int w, int delta, int strand, uint32_t
  *   bits 21..31  shift delta (0..2046): ms >> 21
  *   (k_gram_bitslice's same-length variant also keeps, set once per wave by the source lane:
  *   bits  4..6   piece index of the lane within its row (the lane holds sequence positions pi * capacity ..)
- *   bits 13..18  row slot of the lane; (ms >> 11) & 0xFC is its byte offset in a profile row) */
+ *   bits 13..18  row slot of the lane; (ms >> 11) & 0xFC is its byte offset in a profile row -- bits 13..19 and 0x1FC where
+ *                tiles carry riders and a tile's profiles have 128 slots) */
 constexpr uint32_t META_LANE_SHIFT = 7;
 constexpr uint32_t META_PIECE_SHIFT = 4;
 constexpr uint32_t META_SLOT_SHIFT = 13;
@@ -726,6 +727,14 @@ GKM_HD uint32_t pack_meta(int delta, int w, int strand, int even_adj = 0)
 {
     return (uint32_t)w | ((uint32_t)strand << 4) | ((uint32_t)(strand & even_adj) << 5) | ((uint32_t)delta << 21);
 }
+/* The same-length variant with RIDERS (gkm_pack.h RIDER_B0): a lane's second tag word describes the rider piece in its top
+ * two bit rows -- row slot * 4 in bits 2..8 (the byte offset in a profile row, second copy included), and from bit 9 up,
+ * signed, what lane position i0 has to be moved by to become the l-mer's position in the rider (piece k of a layout with
+ * W words: k * rider_w - RIDER_B0 * W), so that a trip's row weight is still at "base + i0". */
+constexpr uint32_t RIDER_TAG_POS_SHIFT = 9;
+GKM_HD uint32_t pack_rider_tag(int slot, int pos_base) { return ((uint32_t)pos_base << RIDER_TAG_POS_SHIFT) | ((uint32_t)slot << 2); }
+GKM_HD int rider_tag_slot(uint32_t t) { return (int)((t >> 2) & 127u); }
+GKM_HD int rider_tag_pos(uint32_t t) { return (int)((int32_t)t >> RIDER_TAG_POS_SHIFT); }
 GKM_HD int rec_w(uint32_t r) { return (int)(r & 15u); }
 GKM_HD int rec_delta(uint32_t r) { return (int)(r >> 21); }
 GKM_HD int rec_strand(uint32_t r) { return (int)((r >> 4) & 1u); }

@@ -229,8 +229,9 @@ bool bitslice_serves(const gkmhip_ctx *ctx)
 /* ---- the bit-sliced launch, host side: what a launch needs that depends on the rows and not on the device ---- */
 struct BitslicePlan {
     gkmpack::Packing pk;              /* rows -> lanes (gkm_pack.h) */
-    int slots = 64;                   /* row slots per tile: 64 or 128 */
-    bool packed = false, same_length = false;
+    int slots = 64;                   /* row slots per tile: 64 or 128 (the kernel's profiles) */
+    int s_slots = 64;                 /* ... of the tile-transposed output: slots, or gkmpack::RIDER_SLOTS with riders */
+    bool packed = false, same_length = false, riders = false;
     bs_kernel_t kernel = nullptr;
     const char *name = "";
     size_t dyn_lds = 0;
@@ -261,11 +262,11 @@ static int plan_bitslice(const gkmhip_ctx *ctx, const int *rows, int nrows, int 
     const int own_mult = 5;
     /* (a jump in the row list -- a multi-GPU rank's two folded row blocks -- closes the tile where that means fewer work
      * items: gkm_pack.h) */
-    auto pack = [&](int max_rows) {
-        gkmpack::Packing a = gkmpack::pack_rows(rows, nwin.data(), nrows, 10, L, max_rows, 0, own_mult);
+    auto pack = [&](int max_rows, int rider_w = 0) {
+        gkmpack::Packing a = gkmpack::pack_rows(rows, nwin.data(), nrows, 10, L, max_rows, 0, own_mult, rider_w);
         if (mode == COLS_FULL || mode == COLS_RANGE || rows[nrows - 1] - rows[0] + 1 == nrows)
             return a; /* (no jump, or every tile visits the same columns) */
-        gkmpack::Packing b = gkmpack::pack_rows(rows, nwin.data(), nrows, 10, L, max_rows, gkmpack::LANES, own_mult);
+        gkmpack::Packing b = gkmpack::pack_rows(rows, nwin.data(), nrows, 10, L, max_rows, gkmpack::LANES, own_mult, rider_w);
         return gkmpack::triangle_items(b) < gkmpack::triangle_items(a) ? b : a;
     };
     /* At most 64 rows per tile unless that leaves lanes empty (rows shorter than half a lane): the 64-slot kernels keep a
@@ -280,16 +281,53 @@ static int plan_bitslice(const gkmhip_ctx *ctx, const int *rows, int nrows, int 
             P.slots = gkmpack::MAX_ROWS;
         }
     }
-    const gkmpack::Packing &pk = P.pk;
-    const int W = pk.W, ntiles = pk.ntiles, slots = P.slots;
     /* everything but a same-length problem whose rows fill whole lanes -- ragged one-piece data too -- takes the
      * several-pieces variants */
-    bool packed = !unif || slots != 64;
-    for (size_t k = 1; k < pk.pieces.size() && !packed; k++) packed = pk.pieces[k].lane == pk.pieces[k - 1].lane;
+    bool packed = !unif || P.slots != 64;
+    for (size_t k = 1; k < P.pk.pieces.size() && !packed; k++) packed = P.pk.pieces[k].lane == P.pk.pieces[k - 1].lane;
     P.packed = packed;
-    P.kernel = gkm_pick_bitslice(!packed ? 4 : slots == 64 ? 1 : 2, L, d);
+    /* The same-length variants' contract with the packing -- the three statements of k_gram_bitslice's GROUP_VALID comment
+     * for residents and rider pieces, and the lanes: one resident piece, a rider piece only above its last bit row
+     * (gkm_pack.h same_length_packing_check; tests/test_rider_packing.py runs the same function).  The counting loop
+     * applies row validity per GROUP of five lane positions where the top plane is the threshold, so a trip may be handed a
+     * group of which a piece owns only a part, and every window of it that the piece does not own has to read a zero row
+     * weight: no position at or above the lane capacity is owned, and the windows that round a piece's last group up to
+     * five fall into the L - 1 zero bytes behind the row's last l-mer in the positional weight table (POSTAB_PAD) -- only
+     * a piece that finishes its row may have any, and no more than L - 1. */
+    auto layout_check = [&](const gkmpack::Packing &pk, int rider_w, int max_slots) {
+        std::vector<int> rw(pk.pieces.size());
+        for (size_t k = 0; k < pk.pieces.size(); k++) rw[k] = ctx->h_len[(size_t)pk.pieces[k].row] - L + 1;
+        return gkmpack::same_length_packing_check(pk, rw.data(), own_mult, rider_w, max_slots);
+    };
+    /* RIDERS (gkm_pack.h RIDER_B0): where the residents of a same-length problem leave the lanes' top two bit rows empty,
+     * further rows of the tile live there -- 66 rows per tile instead of 64 at 300 bp -- and the launch takes the rider
+     * variant of the kernel, with 128 profile slots per tile.  Kept where whole rows fit as riders, the layout passes the
+     * check, and the tiles do not get more.  They get FEWER from 33 tiles on (152 instead of 157 for 10 000 rows: the
+     * gain).  Below that, and wherever else the count comes out equal, riders COST a triangular launch: every tile ends
+     * two rows later, so it has up to 3 % more work items (70 rows: 136 against 134; 1 000: 8 920 against 8 680), and a
+     * wave's trips execute 1.2 % more instructions.  That is accepted: such launches take under 3 ms, and small problems
+     * -- the ones a test can check against the oracle -- then run the very path the large ones do.
+     * A layout that fails the check is not an error: the launch packs without riders, as before there were any. */
+    if (!packed && gkm_pick_bitslice(5, L, d) != nullptr) {
+        gkmpack::Packing withr = pack(64, gkmpack::RIDER_W);
+        if (withr.nriders > 0 && withr.ntiles <= P.pk.ntiles && layout_check(withr, gkmpack::RIDER_W, gkmpack::RIDER_SLOTS) == 0) {
+            P.pk = std::move(withr);
+            P.riders = true;
+            P.slots = gkmpack::MAX_ROWS;
+            P.s_slots = gkmpack::RIDER_SLOTS;
+        }
+    }
+    if (!P.riders) P.s_slots = P.slots;
+    const gkmpack::Packing &pk = P.pk;
+    const int W = pk.W, ntiles = pk.ntiles, slots = P.slots;
+    P.kernel = gkm_pick_bitslice(P.riders ? 5 : !packed ? 4 : slots == 64 ? 1 : 2, L, d);
     P.name = !packed ? "k_gram_bitslice<same length>" : slots == 64 ? "k_gram_bitslice<packed>" : "k_gram_bitslice<packed,128>";
     if (!P.kernel) return set_err_msg("bit-sliced kernel not instantiated for this (L, d)", 5);
+    if (!packed && !P.riders) { /* (a layout with riders passed the check before it was taken) */
+        const int chk = layout_check(pk, 0, slots);
+        if (chk == 2) return set_err_msg("gram: a group of the same-length packing reaches past the weight table's zero guard", 2);
+        if (chk) return set_err_msg("gram: same-length packing broke its own rule", 2);
+    }
     const int NP = packed ? gkmpack::MAX_PIECES : 1, LPW = packed ? NP : 2;
     /* GKM_LDS_PAD=<bytes> (experiments): extra dynamic LDS per wave, i.e. fewer waves per CU -- how much does the
      * kernel depend on its occupancy? */
@@ -307,6 +345,7 @@ static int plan_bitslice(const gkmhip_ctx *ctx, const int *rows, int nrows, int 
     std::vector<int> fill(nl, 0);
     for (const gkmpack::Piece &pc : pk.pieces) {
         const int k = fill[(size_t)pc.lane]++;
+        if (k >= gkmpack::MAX_PIECES) return set_err_msg("gram: too many pieces in a lane", 2);
         int *dd = &P.desc[((size_t)pc.lane * gkmpack::MAX_PIECES + k) * 5];
         dd[0] = pc.row; dd[1] = pc.b0; dd[2] = pc.nb; dd[3] = pc.p0; dd[4] = pc.cnt;
         P.lane_mask[(size_t)pc.lane] |= 1u << pc.b0;
@@ -324,18 +363,12 @@ static int plan_bitslice(const gkmhip_ctx *ctx, const int *rows, int nrows, int 
             /* row slot and piece index where the record's origin word wants them (gkm_bitslice.h); the piece index is the
              * piece's first position over the lane capacity: pieces of a same-length problem fill whole lanes */
             const int cap = gkmbs::segment_capacity(W, L) / own_mult * own_mult;
-            if (pc.b0 != 0 || pc.p0 % cap != 0 || pc.p0 / cap > 7 || slot > 63 || (pc.cnt % own_mult != 0 && pc.p0 + pc.cnt != row_windows))
-                return set_err_msg("gram: same-length packing broke its own rule", 2);
-            /* The counting loop applies row validity per GROUP of five lane positions where the top plane is the threshold
-             * (k_gram_bitslice GROUP_VALID), so a trip may be handed a group of which the lane owns only a part, and every
-             * window of it that the lane does not own has to read a zero row weight.  That holds if no position at or above
-             * cap is owned (those groups stay unowned whole) and the `over` windows that round the piece's last group up to
-             * five fall into the L - 1 zero bytes behind the row's last l-mer in the positional weight table (POSTAB_PAD):
-             * only a piece that finishes its row may have any, and no more than L - 1. */
-            const int over = (pc.cnt + own_mult - 1) / own_mult * own_mult - pc.cnt;
-            if (pc.cnt > cap || (over != 0 && (pc.p0 + pc.cnt != row_windows || over > L - 1)))
-                return set_err_msg("gram: a group of the same-length packing reaches past the weight table's zero guard", 2);
-            P.lane_piece[(size_t)pc.lane * 2] = (slot << gkmbs::META_SLOT_SHIFT) | ((uint32_t)(pc.p0 / cap) << gkmbs::META_PIECE_SHIFT);
+            /* (the layout itself was checked as a whole above the loop; here: the slot with the second copy's offset) */
+            if (slot >= (uint32_t)slots || k > 1) return set_err_msg("gram: same-length packing broke its own rule", 2);
+            if (pc.rider) /* lane position i0 of bit row 30 is l-mer i0 + p0 - 30 W of the rider */
+                P.lane_piece[(size_t)pc.lane * 2 + 1] = gkmbs::pack_rider_tag((int)slot, pc.p0 - gkmpack::RIDER_B0 * W);
+            else
+                P.lane_piece[(size_t)pc.lane * 2] = (slot << gkmbs::META_SLOT_SHIFT) | ((uint32_t)(pc.p0 / cap) << gkmbs::META_PIECE_SHIFT);
         }
     }
     P.cbeg.assign((size_t)ntiles, 0);
@@ -423,7 +456,7 @@ static int enqueue_bitslice(gkmhip_ctx *ctx, const BitslicePlan &P, int nrows, G
     PinBuf *hb = pin_acquire(blob.size());
     if (!hb) return set_err_msg("gram: pinned host buffer for the launch tables", 4);
     if (scr.tables.ensure(blob.size(), true) || scr.rowplanes.ensure(nl * 3 * W, true) || scr.rowpk.ensure(nl * (size_t)rpw, true) ||
-        (out.G && scr.S.ensure((size_t)P.soff[(size_t)ntiles] * (size_t)P.slots, true))) {
+        (out.G && scr.S.ensure((size_t)P.soff[(size_t)ntiles] * (size_t)P.s_slots, true))) {
         pin_release(hb);
         return 4;
     }
@@ -480,8 +513,12 @@ static int enqueue_bitslice(gkmhip_ctx *ctx, const BitslicePlan &P, int nrows, G
     if (out.G) {
         int span = 0;
         for (int t = 0; t < ntiles; t++) span = std::max(span, P.cend[(size_t)t] - P.cbeg[(size_t)t]);
-        const dim3 ug((unsigned)((span + 63) / 64), (unsigned)(ntiles * (P.slots / UT_SLOTS)));
-        if (P.slots != 64)
+        const dim3 ug((unsigned)((span + 63) / 64), (unsigned)(ntiles * (P.s_slots / UT_SLOTS)));
+        static_assert(gkmpack::RIDER_SLOTS % UT_SLOTS == 0, "k_untile moves UT_SLOTS row slots per block");
+        if (P.riders)
+            hipLaunchKernelGGL(k_untile<gkmpack::RIDER_SLOTS>, ug, dim3(64), 0, stream, scr.S.p, A.tile_soff, A.tile_cbeg, A.tile_cend,
+                               A.tile_nrows, A.tile_row, A.tile_out, A.out);
+        else if (P.slots != 64)
             hipLaunchKernelGGL(k_untile<gkmpack::MAX_ROWS>, ug, dim3(64), 0, stream, scr.S.p, A.tile_soff, A.tile_cbeg, A.tile_cend,
                                A.tile_nrows, A.tile_row, A.tile_out, A.out);
         else
@@ -498,6 +535,7 @@ static int enqueue_bitslice(gkmhip_ctx *ctx, const BitslicePlan &P, int nrows, G
                     fa.numRegs, (size_t)fa.sharedSizeBytes, P.dyn_lds, per_cu);
     }
     ctx->last_kernel = P.name;
+    ctx->last_riders = P.riders ? pk.nriders : 0;
     return 0;
 }
 
@@ -544,6 +582,7 @@ static int enqueue_direct(gkmhip_ctx *ctx, const int *rows, int nrows, int mode,
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e1, stream));
     ctx->last_kernel = "k_gram_direct";
+    ctx->last_riders = 0;
     return 0;
 }
 

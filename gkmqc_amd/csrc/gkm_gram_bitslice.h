@@ -11,7 +11,8 @@ struct BsArgs {
     const uint32_t *rowplanes;  /* [tile][plane 3][W][64] */
     const uint32_t *lane_mask;  /* [tile*64] bit rows at which a piece starts */
     const uint32_t *lane_piece; /* several pieces: [tile*64][MAX_PIECES] row slot | centre offset << 7 | owned windows << 20;
-                                 * same length: [tile*64][2], word 0 = row slot and piece index as the origin word holds them */
+                                 * same length: [tile*64][2], word 0 = row slot and piece index as the origin word holds them,
+                                 * word 1 = the tag of the lane's rider piece (gkm_bitslice.h pack_rider_tag) */
     const int *tile_row, *tile_out, *tile_nrows, *tile_cbeg, *tile_cend; /* columns [cbeg, cend) per tile */
     const uint32_t *rowpk;      /* [tile*64 + lane][rpw] the lanes' positions, 2-bit packed (k_build_rowplanes) */
     const uint32_t *colpk;      /* [seq][pkw][strand] 2-bit packed strands, the two strands interleaved        */
@@ -38,7 +39,8 @@ struct BsArgs {
      * and 1000 instead of 509 ms on the peak-like set -- the waves of a CU then hit the same dense column
      * regions at the same moment and all wait on the hit path together. */
     int ntiles;
-    /* raw Gram values leave the kernel tile-transposed: S[(tile_soff[tile] + j - cbeg) * NSLOT + row slot],
+    /* raw Gram values leave the kernel tile-transposed: S[(tile_soff[tile] + j - cbeg) * slots + row slot] (slots: 64, 128,
+     * or gkmpack::RIDER_SLOTS where tiles carry riders),
      * 64 consecutive doubles per store instruction; k_untile turns them into rows of G */
     double *S;
     const int64_t *tile_soff;
@@ -72,7 +74,8 @@ constexpr int BS_DU = GKM_BS_DU; /* shifts per SB register refill (the SB tables
 constexpr uint32_t POSTAB_PAD = 5;
 
 typedef void (*bs_kernel_t)(const BsArgs);
-/* the instantiation for W = 10 words per lane and packing variant pk (k_gram_bitslice's PK), or nullptr */
+/* the instantiation for W = 10 words per lane and packing variant pk (k_gram_bitslice's PK: 4 same length, 5 same length
+ * with riders, 1 / 2 several pieces per lane), or nullptr */
 bs_kernel_t gkm_pick_bitslice(int pk, int L, int d);
 
 #endif

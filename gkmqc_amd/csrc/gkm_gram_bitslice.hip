@@ -59,26 +59,33 @@ constexpr int BS_CAP = BS_TRIP + 64;
  * control flow besides the push.
  */
 template <int W, int L, int D, int PK>
-__global__ __launch_bounds__(64, D > 4 ? 1 : PK == 4 ? GKM_BS_WAVES : GKM_BS_PACKED_WAVES) void k_gram_bitslice(const BsArgs A)
+__global__ __launch_bounds__(64, D > 4 ? 1 : (PK == 4 || PK == 5) ? GKM_BS_WAVES : GKM_BS_PACKED_WAVES) void k_gram_bitslice(const BsArgs A)
 {
-    /* PK = 4: problems whose sequences all have the same length (gkmQC's own 600-bp subsets, BASELINE configs 1-3): a row
-     *         takes k = ceil(windows / 310) whole lanes, piece pi of it starts at sequence position pi * capacity, and all
-     *         a trip needs of the source lane -- its row slot and pi -- rides in the record's origin word (9 spare bits,
-     *         set once per wave): no piece table, no permute, and the row l-mer's weight comes from the column's own table
-     *         by position (same length, same weights);
+    /* PK = 4: problems whose sequences all have the same length (gkmQC's own 600-bp subsets, BASELINE configs 1-3): a
+     *         RESIDENT row takes k = ceil(windows / 310) lanes from bit row 0, piece pi of it starts at sequence position pi *
+     *         capacity, and all a trip needs of the source lane -- its row slot and pi -- rides in the record's origin word
+     *         (9 spare bits, set once per wave): no piece table, no permute, and the row l-mer's weight comes from the
+     *         column's own table by position (same length, same weights);
+     *      5: the same with RIDERS (gkm_pack.h RIDER_B0): where the residents end at or below bit row 30 (300 bp: bit rows
+     *         0..29), bit rows 30 and 31 of the lanes hold further rows of the tile, ten owned windows and the L - 1 bases of
+     *         overlap per lane -- a 300-bp rider in 29 lanes, two riders per tile, 66 rows instead of 64 for the same
+     *         instructions.  The counting loop sees only other bits in planes it sweeps anyway; a trip whose bit row is 30
+     *         takes row slot and position base from the source lane's RIDER TAG (an LDS table of 64 words, filled once per
+     *         wave) instead of the origin word.  128 profile slots per tile; launches without riders take PK = 4;
      *      1: everything else -- several pieces per lane (gkm_pack.h), up to 64 rows per tile; 2: up to 128 rows per tile.
      * (Rounds 2-5 also had one-piece variants for ragged lengths, PK = 0 / 3: piece entries in an LDS table / fetched by
      * ds_bpermute_b32, hits resolved one by one.  Once the group records below served ragged data through PK = 1 they were
      * left with L < 5 only, where the general kernel k_gram_direct now serves: git history has them.) */
     constexpr bool PACKED = PK == 1 || PK == 2;
-    constexpr bool UNIF = PK == 4;
-    static_assert(PACKED || UNIF, "PK = 4, 1 or 2");
+    constexpr bool UNIF = PK == 4 || PK == 5;
+    constexpr bool RIDERS = PK == 5;
+    static_assert(PACKED || UNIF, "PK = 4, 5, 1 or 2");
     static_assert(L >= 5, "the L - 1 zero bytes either side of a weight table cover a group of five windows");
     using namespace gkmbs;
     /* LDS per wave.  STATIC, one array carved by hand:
      *   accl   [(D + 1) * NSLOT]     mismatch profiles [m][row slot]                              1-2.5 KB
      *   s_list [2][CAP]              the hit list: two-word group records (below)                 1 KB
-     *   lpiece [64 * NP | 0]         piece entries of the several-pieces variants                 0-1 KB
+     *   lpiece [64 * NP | 64 | 0]    piece entries of the several-pieces variants / the lanes' rider tags   0-1 KB
      * DYNAMIC: the column's two 2-bit packed strands, interleaved word by word (2 * pkw words: 0.2 KB at 300 bp, 0.3 KB
      * at 600 bp), then the weight tables: the column's weights by l-mer position (gkm_gram_bitslice.h POSTAB_PAD; ~T + L
      * + 16 bytes), behind it the row side's -- none in the same-length variant (the rows read the column's table), the
@@ -92,14 +99,17 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : PK == 4 ? GKM_BS_WAVES : GKM_BS_PAC
      * (2.5 KB at d = 4) cost a wave per SIMD, so the host packs at most 64 rows into a tile unless
      * that would leave lanes empty (many rows shorter than half a lane). */
     constexpr int NP = PACKED ? gkmpack::MAX_PIECES : 1;   /* pieces per lane */
-    constexpr int NSLOT = PK == 2 ? gkmpack::MAX_ROWS : 64; /* row slots per tile */
+    constexpr int NSLOT = (PK == 2 || RIDERS) ? gkmpack::MAX_ROWS : 64; /* row slots per tile (profiles in LDS) */
+    /* ... and per work item of the tile-transposed output: a tile with riders has at most 64 + MAX_RIDERS rows */
+    constexpr int SSLOT = RIDERS ? gkmpack::RIDER_SLOTS : NSLOT;
+    static_assert(gkmpack::RIDER_SLOTS <= gkmpack::MAX_ROWS, "the riders' row slots have profiles");
     /* GROUP RECORDS: a record of the hit list is TWO words -- the OR of the five hit words of a group of words (which bit
      * rows of the lane hold a hit somewhere in the group) and the origin -- and a trip finds the hits among the five
      * windows of (bit row, group) itself, from the packed strands it reads anyway (see `trip`). */
     constexpr int LIST_ARRAYS = 2;
     constexpr int ACC_WORDS = (D + 1) * NSLOT, LIST_WORDS = LIST_ARRAYS * BS_CAP;
     /* per piece of the several-pieces variants: row slot | centre offset << 7 | owned windows << 20 */
-    constexpr int LPIECE_WORDS = PACKED ? 64 * NP : 0;
+    constexpr int LPIECE_WORDS = PACKED ? 64 * NP : RIDERS ? 64 : 0;
     constexpr int STATIC_WORDS = ACC_WORDS + LIST_WORDS + LPIECE_WORDS;
     __shared__ uint32_t s_mem[STATIC_WORDS];
     uint32_t *const accl = s_mem; /* mismatch profiles [m][row slot] */
@@ -171,7 +181,9 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : PK == 4 ? GKM_BS_WAVES : GKM_BS_PAC
      * to add nothing, i.e. every window they bring in must read a zero row weight:
      *   - a lane that does not finish its row owns A.cap windows, a multiple of five (gkm_pack.h own_mult), from lane
      *     position 0: its groups are owned whole or not at all -- nothing extra.  Positions at or above A.cap, which
-     *     include everything the extension words' fiction touches (A.cap <= segment_capacity), are unowned whole groups;
+     *     include everything the extension words' fiction touches (A.cap <= segment_capacity), are unowned whole groups -- or, with
+     *     riders, a rider piece's, of which the same holds: it owns ten windows from lane position 300, whole groups, or
+     *     finishes its row;
      *   - the lane that finishes its row owns positions 0 .. cnt - 1 with pi * A.cap + cnt = nB: only the group that holds
      *     cnt - 1 is owned in part, and its unowned windows are the row's positions nB .. nB + 3 at most.  Their weight
      *     bytes are among the L - 1 >= 4 zeros behind wt[nB - 1] in the positional table (POSTAB_PAD layout): they add 0;
@@ -200,6 +212,8 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : PK == 4 ? GKM_BS_WAVES : GKM_BS_PAC
     }
     /* (UNIF: word 0 of the lane's piece entry holds its row slot and piece index where the origin word wants them) */
     const uint32_t lane_tag = ((uint32_t)lane << META_LANE_SHIFT) | (UNIF ? A.lane_piece[(size_t)(tile * 64 + lane) * 2] : 0u);
+    /* (RIDERS: word 1 is the tag of the rider piece in the lane's bit rows 30, 31 -- gkm_bitslice.h pack_rider_tag) */
+    if (RIDERS) lpiece[lane] = A.lane_piece[(size_t)(tile * 64 + lane) * 2 + 1];
     const uint32_t lane4 = (uint32_t)lane << 2;
     const int pkw = A.pkw;
     /* dynamic LDS: the column's two packed strands first, interleaved word by word, the weight bytes behind them */
@@ -308,6 +322,10 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : PK == 4 ? GKM_BS_WAVES : GKM_BS_PAC
              * record may well be a lane without a record) */
             uint32_t lm = 0u;
             if (PACKED) lm = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(lane128 >> 5), (int)my_lmask);
+            /* riders: the source lane's rider tag, asked for before the bit row is known -- the read goes out beside the
+             * record's and is back long before the row words are (no further round trip in the chain) */
+            uint32_t rtag = 0u;
+            if (RIDERS) rtag = *(const uint32_t *)((const char *)lpiece + (lane128 >> 5));
             if (!PARTIAL || any) {
                 const uint32_t i0 = __umul24(bit, (uint32_t)W) + (ms & 15u);
                 uint32_t slot4, ia, nv = 5u; /* row slot * 4; LDS address of the row l-mer's weight; owned windows from i0 on */
@@ -324,6 +342,13 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : PK == 4 ? GKM_BS_WAVES : GKM_BS_PAC
                      * piece, whose windows end where the row does: the bytes of the windows behind are masked below */
                     nv = (lp >> 20) - (i0 - __umul24(b0, (uint32_t)W));
                     ia = (i0 - c0b) + s_rowbase;
+                } else if (RIDERS) {
+                    /* bit rows 30 and 31 are the rider's: its tag instead of the resident's fields (31 owns no window) */
+                    const bool rides = bit >= (uint32_t)gkmpack::RIDER_B0;
+                    const uint32_t res4 = (ms >> (META_SLOT_SHIFT - 2)) & 0x1FCu;
+                    const uint32_t res_base = __umul24((ms >> META_PIECE_SHIFT) & 7u, (uint32_t)A.cap);
+                    slot4 = rides ? (rtag & 0x1FCu) : res4;
+                    ia = (rides ? (uint32_t)((int32_t)rtag >> RIDER_TAG_POS_SHIFT) : res_base) + i0 + s_rowbase;
                 } else {
                     slot4 = (ms >> (META_SLOT_SHIFT - 2)) & 0xFCu;
                     ia = __umul24((ms >> META_PIECE_SHIFT) & 7u, (uint32_t)A.cap) + i0 + s_rowbase;
@@ -484,7 +509,7 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : PK == 4 ? GKM_BS_WAVES : GKM_BS_PAC
             for (int m = 0; m <= D; m++) g += A.c[m] * (double)(int32_t)prof[m];
             const int64_t r = A.out.local_rows ? A.tile_out[tile * gkmpack::MAX_ROWS + rs] : row;
             if (A.out.diag && j == row) A.out.diag[row] = g;
-            if (A.S) A.S[(A.tile_soff[tile] + (j - A.tile_cbeg[tile])) * NSLOT + rs] = g;
+            if (A.S) A.S[(A.tile_soff[tile] + (j - A.tile_cbeg[tile])) * SSLOT + rs] = g;
             if (A.out.P) {
 #pragma unroll
                 for (int m = 0; m <= D; m++)
@@ -499,7 +524,10 @@ template <int W, int PACKED>
 static bs_kernel_t pick_bitslice(int L, int d)
 {
 #define GKM_BS(LL, DD) \
-    if (L == LL && d == DD) return k_gram_bitslice<W, LL, DD, PACKED>;
+    if (L == LL && d == DD) { \
+        if constexpr (PACKED != 5 || LL - 1 <= gkmpack::RIDER_NB * W - gkmpack::RIDER_W) return k_gram_bitslice<W, LL, DD, PACKED>; \
+        else return nullptr; /* (no room for a rider piece's overlap: never launched) */ \
+    }
     /* every (L, d) with 5 <= L <= 12, d <= 4 (bin/gkmqc.py:181-185 allows 3 <= L <= 12: L = 3 and 4 take k_gram_direct, the
      * group records need L >= 5), plus the d > 4 pairs where this kernel beats k_gram_direct -- see bitslice_serves()
      * in gkm_gram.hip for where that is. */
@@ -517,6 +545,7 @@ bs_kernel_t gkm_pick_bitslice(int pk, int L, int d)
     case 1: return pick_bitslice<10, 1>(L, d);
     case 2: return pick_bitslice<10, 2>(L, d);
     case 4: return pick_bitslice<10, 4>(L, d);
+    case 5: return pick_bitslice<10, 5>(L, d);
     }
     return nullptr;
 }

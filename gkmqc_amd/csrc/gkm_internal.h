@@ -155,6 +155,7 @@ struct gkmhip_ctx {
     double sampled_hit_share = -1.0; /* share of sampled l-mer pairs of THESE sequences within d mismatches (set_sequences) */
     double last_comparisons = 0;
     const char *last_kernel = "none";
+    int last_riders = 0; /* rows the most recent Gram launch carried as riders (gkm_pack.h RIDER_B0) */
     /* gkmhip_explain_block, gkmhip_ism_block, gkmhip_hyp_block: the row list of the call (upload_rows) and the partial
      * rows of its support-vector chunks.  One buffer each for all three: a call's kernels consume them in stream order
      * before the next call on that stream can overwrite them (growing one is a hipFree, which waits for the device). */

@@ -216,6 +216,9 @@ def load():
     L.gkmhip_last_comparisons.argtypes = (vp,)
     L.gkmhip_last_kernel_name.restype = ctypes.c_char_p
     L.gkmhip_last_kernel_name.argtypes = (vp,)
+    if hasattr(L, "gkmhip_last_riders"):   # (older builds loaded through GKM_LIB_PATH for A/B timing lack it)
+        L.gkmhip_last_riders.restype = i32
+        L.gkmhip_last_riders.argtypes = (vp,)
     _lib = L
     return L
 
@@ -579,6 +582,10 @@ class GramContext:
     def last_kernel_name(self):
         return self.lib.gkmhip_last_kernel_name(self.handle).decode()
 
+    def last_riders(self):
+        """Rows the most recent Gram launch carried as riders (bit rows 30, 31 of the same-length variant's lanes), 0 if none."""
+        return int(self.lib.gkmhip_last_riders(self.handle)) if hasattr(self.lib, "gkmhip_last_riders") else 0
+
 
 def cross_kernel(seqs, rows, kernel_type, L, k, d, M=50, H=50.0, gamma=1.0, device=0, kernel=KERNEL_AUTO):
     """K(rows[i], j) for every sequence j (prediction-style rectangular kernel): torch fp64
@@ -740,10 +747,11 @@ def gram_matrix(seqs, kernel_type, L, k, d, M=50, H=50.0, gamma=1.0, device=0, w
             P = torch.zeros((n, n, d + 1), dtype=torch.int32, device=dev) if want_profiles else None
             sq = torch.zeros(n, dtype=torch.float64, device=dev)
             ctx.gram_rows(np.arange(n), G.data_ptr(), n, P.data_ptr() if want_profiles else None, n, False, stream)
+            riders = ctx.last_riders()
             ctx.normalize(G.data_ptr(), n, sq.data_ptr(), symmetric, stream)
             if not (keep_context and not wait):
                 torch.cuda.current_stream().synchronize()   # (this stream only: others may carry unrelated work)
-            return dict(K=G, P=P, sqnorm=sq, kernel=ctx.last_kernel_name(),
+            return dict(K=G, P=P, sqnorm=sq, kernel=ctx.last_kernel_name(), riders=riders,
                         ms=ctx.last_kernel_ms() if (wait or not keep_context) else None,
                         comparisons=ctx.last_comparisons())
     finally:

@@ -450,6 +450,9 @@ int gkmhip_kernel_timeline_spans(gkmhip_ctx *ctx, double *out, int cap);
 /* number of l-mer comparisons that call evaluated (algorithmic: 2 n_a n_j per pair) */
 double gkmhip_last_comparisons(gkmhip_ctx *ctx);
 const char *gkmhip_last_kernel_name(gkmhip_ctx *ctx);
+/* rows that the most recent Gram launch carried as RIDERS -- in bit rows 30, 31 of lanes whose own row ends below them
+ * (same-length problems) -- 0 if it packed without them or another kernel served it */
+int gkmhip_last_riders(gkmhip_ctx *ctx);
 
 #ifdef __cplusplus
 }
