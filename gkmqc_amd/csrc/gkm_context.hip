@@ -550,6 +550,35 @@ int gkm_launch_events(gkmhip_ctx *ctx, hipEvent_t *e0, hipEvent_t *e1)
     return 0;
 }
 
+int gkm_launch_enter(gkmhip_ctx *ctx)
+{
+    HIPCHK(hipSetDevice(ctx->device));
+    (void)hipGetLastError(); /* the launch checks below must see this call's errors only */
+    return 0;
+}
+
+int gkm_launch_begin(gkmhip_ctx *ctx, hipStream_t stream)
+{
+    hipEvent_t e0, e1;
+    if (gkm_launch_events(ctx, &e0, &e1)) return 4;
+    HIPCHK(hipEventRecord(e0, stream));
+    return 0;
+}
+
+int gkm_launch_stop(gkmhip_ctx *ctx, hipStream_t stream)
+{
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ctx->last_e1, stream));
+    return 0;
+}
+
+void gkm_launch_done(gkmhip_ctx *ctx, const char *kernel, double comparisons)
+{
+    ctx->ev_valid = true;
+    ctx->last_comparisons = comparisons;
+    ctx->last_kernel = kernel;
+}
+
 extern "C" int gkmhip_kernel_timeline(gkmhip_ctx *ctx, int on)
 {
     if (!ctx) return set_err_msg("gkmhip_kernel_timeline: bad arguments", 2);

@@ -26,12 +26,10 @@
  * Every value is one lane's own chain of additions in the order above: no atomics, no cross-lane sums, nothing that
  * depends on the launch geometry.
  */
-#include "gkm_internal.h"
+#include "gkm_lmer_dev.h"
 
 namespace {
 
-constexpr uint32_t DELTA_BAD = 0x80000000u; /* the l-mer covers an invalid base (k_scan_lmers) */
-constexpr uint32_t DELTA_CODE = 0x00FFFFFFu;
 constexpr int DS_THREADS = 256;
 constexpr int DV_THREADS = 256;
 
@@ -49,7 +47,7 @@ __global__ __launch_bounds__(DS_THREADS) void k_delta_sat(const uint32_t *__rest
 #pragma unroll 2
     for (int64_t p = p0; p <= p1; p++, sh += 2) {
         const uint32_t e = lm[p];
-        const uint32_t u = e & DELTA_CODE;
+        const uint32_t u = e & LMER_CODE;
         flags |= e;
         last = u;
         s0 += W[u];
@@ -59,7 +57,7 @@ __global__ __launch_bounds__(DS_THREADS) void k_delta_sat(const uint32_t *__rest
     }
     const uint32_t xt = (last >> (sh - 2)) & 3u; /* (sh - 2: the pair of t in l-mer p1) */
     double2 lo, hi;
-    if (flags & DELTA_BAD) {
+    if (flags & LMER_BAD) {
         const double nan = __builtin_nan("");
         lo = make_double2(nan, nan);
         hi = lo;
@@ -96,7 +94,7 @@ __global__ __launch_bounds__(DV_THREADS) void k_delta_variants(const uint32_t *_
     }
     const int a = max(0, pos - (L - 1)), e = min(nbases, pos + r + (L - 1));
     double ref = 0.0;
-    for (int p = a; p + L <= e; p++) ref += W[lm[p] & DELTA_CODE];
+    for (int p = a; p + L <= e; p++) ref += W[lm[p] & LMER_CODE];
     const uint32_t mask = (uint32_t)((1ull << (2 * L)) - 1ull);
     uint32_t u = 0u;
     int have = 0; /* bases rolled in so far */
@@ -137,18 +135,12 @@ extern "C" int gkmhip_delta_sat(gkmhip_ctx *ctx, const uint32_t *lm, int64_t nlm
     const int64_t blocks = (t_end - t_begin + DS_THREADS - 1) / DS_THREADS;
     if (blocks > 0x7FFFFFFF) return set_err_msg("gkmhip_delta_sat: at most 2^31 - 1 workgroups of positions per launch", 2);
     hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(hipSetDevice(ctx->device));
-    (void)hipGetLastError();
-    hipEvent_t e0, e1;
-    if (gkm_launch_events(ctx, &e0, &e1)) return 4;
-    HIPCHK(hipEventRecord(e0, stream));
+    if (int rc = gkm_launch_enter(ctx)) return rc;
+    if (int rc = gkm_launch_begin(ctx, stream)) return rc;
     hipLaunchKernelGGL(k_delta_sat, dim3((unsigned)blocks), dim3(DS_THREADS), 0, stream, lm, nlm, ctx->L, t_begin, t_end, W,
                        out);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, stream));
-    ctx->ev_valid = true;
-    ctx->last_comparisons = 4.0 * (covered_below(t_end, nlm, ctx->L) - covered_below(t_begin, nlm, ctx->L));
-    ctx->last_kernel = "k_delta_sat";
+    if (int rc = gkm_launch_stop(ctx, stream)) return rc;
+    gkm_launch_done(ctx, "k_delta_sat", 4.0 * (covered_below(t_end, nlm, ctx->L) - covered_below(t_begin, nlm, ctx->L)));
     return 0;
 }
 
@@ -174,22 +166,16 @@ extern "C" int gkmhip_delta_variants(gkmhip_ctx *ctx, const uint32_t *lm, const 
         gathers += (double)std::max<int64_t>(0, e - a - L + 1) + (double)std::max<int64_t>(0, e - a - r + al - L + 1);
     }
     hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(hipSetDevice(ctx->device));
-    (void)hipGetLastError();
+    if (int rc = gkm_launch_enter(ctx)) return rc;
     /* var and alt are the caller's host arrays: on the device before this returns (upload_rows waits) */
     if (ctx->delta_alt.ensure((size_t)nalt, true)) return 4;
     if (nalt) HIPCHK(hipMemcpyAsync(ctx->delta_alt.p, alt, (size_t)nalt, hipMemcpyHostToDevice, stream));
     if (upload_rows(ctx, (const int *)var, 4 * nvar, stream)) return 4;
-    hipEvent_t e0, e1;
-    if (gkm_launch_events(ctx, &e0, &e1)) return 4;
-    HIPCHK(hipEventRecord(e0, stream));
+    if (int rc = gkm_launch_begin(ctx, stream)) return rc;
     hipLaunchKernelGGL(k_delta_variants, dim3((unsigned)((nvar + DV_THREADS - 1) / DV_THREADS)), dim3(DV_THREADS), 0, stream,
                        lm, codes, (int)nbases, L, (const int4 *)ctx->blk_rows.p, nvar, (const uint8_t *)ctx->delta_alt.p,
                        (int)nalt, W, out);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, stream));
-    ctx->ev_valid = true;
-    ctx->last_comparisons = gathers;
-    ctx->last_kernel = "k_delta_variants";
+    if (int rc = gkm_launch_stop(ctx, stream)) return rc;
+    gkm_launch_done(ctx, "k_delta_variants", gathers);
     return 0;
 }

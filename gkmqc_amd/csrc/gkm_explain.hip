@@ -15,7 +15,7 @@
  * Nothing depends on arrival order, so a query's values are bit-identical whatever the block it shares and however often
  * it runs: the chunking is a function of the number of support vectors only.
  */
-#include "gkm_gram_bitslice.h" /* (sgpr_words) */
+#include "gkm_lmer_dev.h"
 
 namespace {
 
@@ -71,8 +71,8 @@ __global__ __launch_bounds__(EX_THREADS) void k_explain(const ExplainArgs A)
     for (int r = 0; r < EX_R; r++) {
         const int p = r * EX_THREADS + tid;
         const uint32_t e = p < nx ? A.lmf[ox + p] : 0u;
-        u[r] = e & 0x00FFFFFFu;
-        wu[r] = e >> 24;
+        u[r] = e & LMER_CODE;
+        wu[r] = e >> LMER_WSHIFT;
         lim[r] = p < nx ? d : -1;
     }
     /* slots in which this wave has any l-mer (wave-uniform) */
@@ -105,14 +105,12 @@ __global__ __launch_bounds__(EX_THREADS) void k_explain(const ExplainArgs A)
 #pragma unroll
                 for (int r = 0; r < EX_R; r++) {
                     if (r >= rn) break;
-                    /* the weight byte of the column entry is masked off by 0x555555 (its top bit 22 folds from bit 23) */
-                    uint32_t tf = u[r] ^ xf[t], tr = u[r] ^ xr[t];
-                    tf = (tf | (tf >> 1)) & 0x00555555u;
-                    tr = (tr | (tr >> 1)) & 0x00555555u;
+                    /* (lmer_mask drops the weight byte of the column entry) */
+                    const uint32_t tf = lmer_mask(u[r], xf[t]), tr = lmer_mask(u[r], xr[t]);
                     const int mf = __builtin_popcount(tf), mr = __builtin_popcount(tr);
                     const int p = r * EX_THREADS + tid;
-                    if (mf <= lim[r]) explain_hit(H, T, mf, p, L, tf, wu[r] * (xf[t] >> 24));
-                    if (mr <= lim[r]) explain_hit(H, T, mr, p, L, tr, wu[r] * (xr[t] >> 24));
+                    if (mf <= lim[r]) explain_hit(H, T, mf, p, L, tf, wu[r] * (xf[t] >> LMER_WSHIFT));
+                    if (mr <= lim[r]) explain_hit(H, T, mr, p, L, tr, wu[r] * (xr[t] >> LMER_WSHIFT));
                 }
             }
         }
@@ -175,8 +173,7 @@ extern "C" int gkmhip_explain_block(gkmhip_ctx *ctx, const int *rows, int nrows,
     scan_range(ctx, col_begin, col_end, &tmax, &bases);
     const double comparisons = 2.0 * row_lmers * (ctx->h_cum_n[(size_t)col_end] - ctx->h_cum_n[(size_t)col_begin]);
     hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(hipSetDevice(ctx->device));
-    (void)hipGetLastError(); /* the launch checks below must see this call's errors only */
+    if (int rc = gkm_launch_enter(ctx)) return rc;
     if (ensure_lmers(ctx, stream, true)) return 4;
     const int chunk = explain_chunk(nrows), nchunks = (nrows + chunk - 1) / chunk;
     if (ctx->blk_part.ensure((size_t)nchunks * (size_t)bases, true)) return 4;
@@ -191,18 +188,13 @@ extern "C" int gkmhip_explain_block(gkmhip_ctx *ctx, const int *rows, int nrows,
     A.part = ctx->blk_part.p; A.part_stride = bases;
     const size_t lds = (size_t)(d + 1) * (size_t)tmax * sizeof(uint32_t); /* at most 13 x 2 047 x 4 = 106 444 bytes */
     HIPCHK(hipFuncSetAttribute((const void *)k_explain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipEvent_t e0, e1;
-    if (gkm_launch_events(ctx, &e0, &e1)) return 4;
-    HIPCHK(hipEventRecord(e0, stream));
+    if (int rc = gkm_launch_begin(ctx, stream)) return rc;
     hipLaunchKernelGGL(k_explain, dim3((unsigned)(col_end - col_begin), (unsigned)nchunks), dim3(EX_THREADS), lds, stream, A);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, stream));
+    if (int rc = gkm_launch_stop(ctx, stream)) return rc; /* (k_explain alone is timed) */
     hipLaunchKernelGGL(k_explain_reduce, dim3((unsigned)(col_end - col_begin)), dim3(256), 0, stream, (const double *)ctx->blk_part.p,
                        (int64_t)bases, nchunks, (const int *)ctx->len.p, (const int64_t *)ctx->off.p, col_begin, xscale, out);
     HIPCHK(hipGetLastError());
-    ctx->ev_valid = true;
-    ctx->last_comparisons = comparisons;
-    ctx->last_kernel = "k_explain";
+    gkm_launch_done(ctx, "k_explain", comparisons);
     if (getenv("GKM_TRACE"))
         fprintf(stderr, "gkmhip: explain %d rows x columns [%d, %d) -> k_explain (%d chunks of %d rows, %zu bytes of LDS, "
                         "%.3g comparisons)\n", nrows, col_begin, col_end, nchunks, chunk, lds, comparisons);

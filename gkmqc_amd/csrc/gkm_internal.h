@@ -10,6 +10,8 @@
  *                          the general kernel k_gram_direct, gkmhip_gram_rows*
  *   gkm_normalize.hip      k_sqnorm, k_normalize, k_assemble_normalize: square roots of the diagonal, division, RBF
  *   gkm_copyout.hip        device matrix -> the caller's host rows: row blocks, staging pieces, the stream prober
+ *   gkm_lmer_dev.h         packed l-mers on the device: scalar-load pointer types, the fields of a packed entry, reverse
+ *                          complement, mismatch mask and count, the coefficient block a table kernel takes by value
  *   gkm_explain.hip        per-base importance of a trained model (k_explain, k_explain_reduce), gkmhip_explain_block
  *   gkm_ism.hip            in-silico mutagenesis of a trained model (k_ism, k_ism_reduce, k_ism_self_base, k_ism_self),
  *                          gkmhip_ism_self_profiles; hypothetical importance (k_ism<true>, k_ism_hyp_reduce);
@@ -168,8 +170,19 @@ struct gkmhip_ctx {
     DevBuf<uint8_t> delta_alt;
 };
 
-/* the pair of events the next Gram kernel is bracketed by (gkm_context.hip) */
+/* the pair of events the next timed kernel is bracketed by (gkm_context.hip; the Gram launches call it themselves) */
 int gkm_launch_events(gkmhip_ctx *ctx, hipEvent_t *e0, hipEvent_t *e1);
+
+/* The bracket of a timed launch (gkm_context.hip), in this order; each but the last returns an error code or 0.
+ *   enter  the context's device; the sticky error discarded
+ *   begin  the launch's pair of events taken (the context's own, or the kernel timeline's next), the first recorded
+ *   stop   the launch error checked, the second event recorded: what lies between begin and stop is what
+ *          gkmhip_last_kernel_ms and the timeline report
+ *   done   once everything has succeeded: the name and the comparisons of the launch, its events valid */
+int gkm_launch_enter(gkmhip_ctx *ctx);
+int gkm_launch_begin(gkmhip_ctx *ctx, hipStream_t stream);
+int gkm_launch_stop(gkmhip_ctx *ctx, hipStream_t stream);
+void gkm_launch_done(gkmhip_ctx *ctx, const char *kernel, double comparisons);
 
 constexpr int WD_LDS = 1024; /* distance weight table entries: >= max |n/2 - p| + 1 for n <= 2047 */
 

@@ -32,7 +32,7 @@
  * Nothing depends on arrival order, so a query's values are bit-identical whatever the block it shares and however often
  * it runs: the chunking is a function of the number of support vectors only, the tiling of (L, d) only.
  */
-#include "gkm_gram_bitslice.h" /* (sgpr_words) */
+#include "gkm_lmer_dev.h"
 
 namespace {
 
@@ -127,9 +127,9 @@ __device__ __forceinline__ void ism_flush(const uint32_t *Q, int qn, int lane, u
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     for (int k = lane; k < qn; k += 64) {
         const uint32_t a = Q[ISM_QWORDS * k], v = Q[ISM_QWORDS * k + 1], c = Q[ISM_QWORDS * k + 2];
-        const uint32_t u = a & 0x00FFFFFFu, t = u ^ v;
-        ism_hit<HYP>(U, B, P, stride, tlen, d, L, (int)(a >> 24), (int)(c & 0xFFFFu) - 16, (t | (t >> 1)) & 0x00555555u,
-                     u, v, c >> 16);
+        const uint32_t u = a & LMER_CODE;
+        /* (the mask is symmetric; with v first the compiler keeps the operand order it has always given the fold) */
+        ism_hit<HYP>(U, B, P, stride, tlen, d, L, (int)(a >> 24), (int)(c & 0xFFFFu) - 16, lmer_mask(v, u), u, v, c >> 16);
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
 }
@@ -165,8 +165,8 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism(const IsmArgs A)
     for (int r = 0; r < ISM_R; r++) {
         const int p = pl0 + r * ISM_THREADS + tid;
         const uint32_t e = p < pl1 ? A.lmf[ox + p] : 0u;
-        u[r] = e & 0x00FFFFFFu;
-        wu[r] = e >> 24;
+        u[r] = e & LMER_CODE;
+        wu[r] = e >> LMER_WSHIFT;
         lim[r] = p < pl1 ? mb : -1;
     }
     const int w0 = (tid >> 6) * 64;
@@ -202,19 +202,16 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism(const IsmArgs A)
 #pragma unroll
                 for (int r = 0; r < ISM_R; r++) {
                     if (r >= rn) break;
-                    uint32_t tf = u[r] ^ xf[t], tr = u[r] ^ xr[t];
-                    tf = (tf | (tf >> 1)) & 0x00555555u;
-                    tr = (tr | (tr >> 1)) & 0x00555555u;
-                    const int mf = __builtin_popcount(tf), mr = __builtin_popcount(tr);
+                    const int mf = lmer_mm(u[r], xf[t]), mr = lmer_mm(u[r], xr[t]);
                     const uint32_t ptw = (uint32_t)(pl0 + r * ISM_THREADS + tid - t0 + 16);
-                    qn = ism_push(Q, qn, mf <= lim[r], u[r] | ((uint32_t)mf << 24), xf[t] & 0x00FFFFFFu,
-                                  ptw | (wu[r] * (xf[t] >> 24)) << 16);
+                    qn = ism_push(Q, qn, mf <= lim[r], u[r] | ((uint32_t)mf << 24), xf[t] & LMER_CODE,
+                                  ptw | (wu[r] * (xf[t] >> LMER_WSHIFT)) << 16);
                     if (qn >= 64) {
                         ism_flush<HYP>(Q, qn, lane, U, B, P, stride, tlen, d, L);
                         qn = 0;
                     }
-                    qn = ism_push(Q, qn, mr <= lim[r], u[r] | ((uint32_t)mr << 24), xr[t] & 0x00FFFFFFu,
-                                  ptw | (wu[r] * (xr[t] >> 24)) << 16);
+                    qn = ism_push(Q, qn, mr <= lim[r], u[r] | ((uint32_t)mr << 24), xr[t] & LMER_CODE,
+                                  ptw | (wu[r] * (xr[t] >> LMER_WSHIFT)) << 16);
                     if (qn >= 64) {
                         ism_flush<HYP>(Q, qn, lane, U, B, P, stride, tlen, d, L);
                         qn = 0;
@@ -359,12 +356,6 @@ __global__ void k_ism_hyp_reduce(const double *__restrict__ part, int64_t part_s
     }
 }
 
-__device__ __forceinline__ int lmer_mismatches(uint32_t a, uint32_t b)
-{
-    uint32_t t = a ^ b;
-    return __builtin_popcount((t | (t >> 1)) & 0x00555555u);
-}
-
 /* P_m(x, x) of each query of the range: pself[jl][m], m = 0..d */
 __global__ __launch_bounds__(ISM_THREADS) void k_ism_self_base(const int *__restrict__ len, const int64_t *__restrict__ lmoff,
                                                               const uint32_t *__restrict__ lmf, const uint32_t *__restrict__ lmr,
@@ -378,11 +369,11 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_self_base(const int *__rest
     __syncthreads();
     for (int p = tid; p < nx; p += ISM_THREADS) {
         const uint32_t ue = lmf[ox + p];
-        const uint32_t uu = ue & 0x00FFFFFFu, wu = ue >> 24;
+        const uint32_t uu = ue & LMER_CODE, wu = ue >> LMER_WSHIFT;
         for (int q = 0; q < 2 * nx; q++) {
             const uint32_t ve = q < nx ? lmf[ox + q] : lmr[ox + q - nx];
-            const int m = lmer_mismatches(uu, ve & 0x00FFFFFFu);
-            if (m <= d) atomicAdd(Pm + m, (unsigned long long)(wu * (ve >> 24)));
+            const int m = lmer_mm(uu, ve & LMER_CODE);
+            if (m <= d) atomicAdd(Pm + m, (unsigned long long)(wu * (ve >> LMER_WSHIFT)));
         }
     }
     __syncthreads();
@@ -394,12 +385,12 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_self_base(const int *__rest
 __device__ __forceinline__ void self_pair(unsigned long long *D, int d, const uint32_t dl[3], uint32_t u, int su,
                                           uint32_t v, int sv, uint32_t w)
 {
-    const int mx = lmer_mismatches(u, v);
+    const int mx = lmer_mm(u, v);
 #pragma unroll
     for (int s = 0; s < 3; s++) {
         const uint32_t uy = su >= 0 ? u ^ (dl[s] << su) : u;
         const uint32_t vy = sv >= 0 ? v ^ (dl[s] << sv) : v;
-        const int my = lmer_mismatches(uy, vy);
+        const int my = lmer_mm(uy, vy);
         if (my == mx) continue;
         if (mx <= d) atomicAdd(D + s * (d + 1) + mx, (unsigned long long)(-(long long)w));
         if (my <= d) atomicAdd(D + s * (d + 1) + my, (unsigned long long)w);
@@ -437,7 +428,7 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_self(const int *__restrict_
             const uint32_t ve = rc ? lmr[ox + q - nx] : lmf[ox + q];
             const int pv = rc ? 2 * nx - 1 - q : q;
             const int sv = pv < a0 || pv > a1 ? -1 : rc ? 2 * (t - pv) : 2 * (L - 1 - (t - pv));
-            self_pair(D, d, dl, ue & 0x00FFFFFFu, su, ve & 0x00FFFFFFu, sv, (ue >> 24) * (ve >> 24));
+            self_pair(D, d, dl, ue & LMER_CODE, su, ve & LMER_CODE, sv, (ue >> LMER_WSHIFT) * (ve >> LMER_WSHIFT));
         }
     }
     /* every pair of an unchanged query-side l-mer with a changed one on the other side */
@@ -449,7 +440,7 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_self(const int *__restrict_
         for (int p = tid; p < nx; p += ISM_THREADS) {
             if (p >= a0 && p <= a1) continue;
             const uint32_t ue = lmf[ox + p];
-            self_pair(D, d, dl, ue & 0x00FFFFFFu, -1, ve & 0x00FFFFFFu, sv, (ue >> 24) * (ve >> 24));
+            self_pair(D, d, dl, ue & LMER_CODE, -1, ve & LMER_CODE, sv, (ue >> LMER_WSHIFT) * (ve >> LMER_WSHIFT));
         }
     }
     __syncthreads();
@@ -488,8 +479,7 @@ int ism_launch(gkmhip_ctx *ctx, IsmArgs &A, const int *rows, int nrows, int col_
     const double comparisons = 2.0 * row_lmers * tile_lmers;
     const int ntiles = (tmax + tile - 1) / tile, stride = std::min(tile, tmax);
     const int ncols = col_end - col_begin;
-    HIPCHK(hipSetDevice(ctx->device));
-    (void)hipGetLastError(); /* the launch checks below must see this call's errors only */
+    if (int rc = gkm_launch_enter(ctx)) return rc;
     if (ensure_lmers(ctx, stream, true)) return 4;
     const int chunk = ism_chunk(nrows), nchunks = (nrows + chunk - 1) / chunk;
     if (ctx->blk_part.ensure((size_t)nchunks * per * (size_t)bases, true) ||
@@ -506,12 +496,9 @@ int ism_launch(gkmhip_ctx *ctx, IsmArgs &A, const int *rows, int nrows, int col_
     /* at most 6 248 + 4 x (13 + 3 x 12) x 804 = 163 832 bytes (L = 12, d = 12); 44 648 at gkmQC's shape */
     const size_t lds = ISM_LDS_FIXED + (size_t)(d + 1 + 3 * mb) * (size_t)stride * sizeof(uint32_t);
     HIPCHK(hipFuncSetAttribute((const void *)k_ism<HYP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipEvent_t e0, e1;
-    if (gkm_launch_events(ctx, &e0, &e1)) return 4;
-    HIPCHK(hipEventRecord(e0, stream));
+    if (int rc = gkm_launch_begin(ctx, stream)) return rc;
     hipLaunchKernelGGL(k_ism<HYP>, dim3((unsigned)ncols, (unsigned)nchunks, (unsigned)ntiles), dim3(ISM_THREADS), lds, stream, A);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, stream));
+    if (int rc = gkm_launch_stop(ctx, stream)) return rc; /* (k_ism<HYP> alone is timed) */
     if constexpr (HYP)
         hipLaunchKernelGGL(k_ism_hyp_reduce, dim3((unsigned)ncols), dim3(256), 0, stream, (const double *)ctx->blk_part.p,
                            (int64_t)per * bases, nchunks, (const int *)ctx->len.p, (const int64_t *)ctx->off.p,
@@ -522,9 +509,7 @@ int ism_launch(gkmhip_ctx *ctx, IsmArgs &A, const int *rows, int nrows, int col_
                            (const int *)ctx->len.p, (const int64_t *)ctx->off.p, (const uint8_t *)ctx->codes.p, col_begin,
                            out, base);
     HIPCHK(hipGetLastError());
-    ctx->ev_valid = true;
-    ctx->last_comparisons = comparisons;
-    ctx->last_kernel = HYP ? "k_ism<true>" : "k_ism";
+    gkm_launch_done(ctx, HYP ? "k_ism<true>" : "k_ism", comparisons);
     if (getenv("GKM_TRACE"))
         fprintf(stderr, "gkmhip: %s %d rows x columns [%d, %d) -> %s (%d chunks of %d rows, %d tiles of %d positions, "
                         "%zu bytes of LDS, %.3g comparisons)\n", HYP ? "hypothetical" : "ism", nrows, col_begin, col_end,
@@ -579,14 +564,11 @@ extern "C" int gkmhip_ism_self_profiles(gkmhip_ctx *ctx, int col_begin, int col_
         }
     }
     hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(hipSetDevice(ctx->device));
-    (void)hipGetLastError();
+    if (int rc = gkm_launch_enter(ctx)) return rc;
     if (ensure_lmers(ctx, stream, true)) return 4;
     if (ctx->ism_pself.ensure((size_t)ncols * (size_t)(d + 1), true)) return 4;
     const uint32_t *lmr = ctx->lmf.p + ctx->lm_stride;
-    hipEvent_t e0, e1;
-    if (gkm_launch_events(ctx, &e0, &e1)) return 4;
-    HIPCHK(hipEventRecord(e0, stream));
+    if (int rc = gkm_launch_begin(ctx, stream)) return rc;
     hipLaunchKernelGGL(k_ism_self_base, dim3((unsigned)ncols), dim3(ISM_THREADS), 0, stream, (const int *)ctx->len.p,
                        (const int64_t *)ctx->lmoff.p, (const uint32_t *)ctx->lmf.p, lmr, L, d, col_begin, ctx->ism_pself.p);
     HIPCHK(hipGetLastError());
@@ -594,11 +576,8 @@ extern "C" int gkmhip_ism_self_profiles(gkmhip_ctx *ctx, int col_begin, int col_
                        (const int *)ctx->len.p, (const int64_t *)ctx->off.p, (const int64_t *)ctx->lmoff.p,
                        (const uint32_t *)ctx->lmf.p, lmr, (const uint8_t *)ctx->codes.p, L, d, col_begin,
                        (const int64_t *)ctx->ism_pself.p, prof);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, stream));
-    ctx->ev_valid = true;
-    ctx->last_comparisons = comparisons;
-    ctx->last_kernel = "k_ism_self";
+    if (int rc = gkm_launch_stop(ctx, stream)) return rc;
+    gkm_launch_done(ctx, "k_ism_self", comparisons);
     if (getenv("GKM_TRACE"))
         fprintf(stderr, "gkmhip: ism self profiles of columns [%d, %d) -> k_ism_self_base + k_ism_self (%d x %d workgroups, "
                         "%.3g comparisons)\n", col_begin, col_end, ncols, tmax, comparisons);
@@ -615,19 +594,13 @@ extern "C" int gkmhip_self_profiles(gkmhip_ctx *ctx, int col_begin, int col_end,
         comparisons += 2.0 * nx * nx;
     }
     hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(hipSetDevice(ctx->device));
-    (void)hipGetLastError();
+    if (int rc = gkm_launch_enter(ctx)) return rc;
     if (ensure_lmers(ctx, stream, true)) return 4;
-    hipEvent_t e0, e1;
-    if (gkm_launch_events(ctx, &e0, &e1)) return 4;
-    HIPCHK(hipEventRecord(e0, stream));
+    if (int rc = gkm_launch_begin(ctx, stream)) return rc;
     hipLaunchKernelGGL(k_ism_self_base, dim3((unsigned)(col_end - col_begin)), dim3(ISM_THREADS), 0, stream,
                        (const int *)ctx->len.p, (const int64_t *)ctx->lmoff.p, (const uint32_t *)ctx->lmf.p,
                        (const uint32_t *)(ctx->lmf.p + ctx->lm_stride), ctx->L, ctx->d, col_begin, pself);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, stream));
-    ctx->ev_valid = true;
-    ctx->last_comparisons = comparisons;
-    ctx->last_kernel = "k_ism_self_base";
+    if (int rc = gkm_launch_stop(ctx, stream)) return rc;
+    gkm_launch_done(ctx, "k_ism_self_base", comparisons);
     return 0;
 }

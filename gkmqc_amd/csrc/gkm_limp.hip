@@ -21,35 +21,14 @@
  * V[rc(u)][L-1-i] is bit for bit V[u][i] (the two strands swap roles; their terms meet in one commutative add before
  * the multiply), and a query's values are functions of the query and V only.
  */
-#include "gkm_gram_bitslice.h" /* (sgpr_words) */
+#include "gkm_lmer_dev.h"
 
 namespace {
 
 constexpr int LI_THREADS = 256;
 constexpr int LI_QB = 8;  /* classes per scalar request */
-constexpr int LI_C = 16;  /* share in LDS, zero beyond d: a mismatch count is at most L <= 12 */
 constexpr int LI_MAXL = 12;
 constexpr int LG_THREADS = 256;
-
-typedef const double __attribute__((address_space(4))) *sgpr_doubles;
-
-struct LimpShare {
-    double s[LI_C];
-};
-
-__device__ __forceinline__ uint32_t limp_rc(uint32_t v, int L)
-{
-    uint32_t x = __builtin_bitreverse32(~v);
-    x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
-    return x >> (32 - 2 * L);
-}
-
-/* bit 2 (L - 1 - i) set where base i differs */
-__device__ __forceinline__ uint32_t limp_mask(uint32_t u, uint32_t v)
-{
-    const uint32_t t = u ^ v;
-    return (t | (t >> 1)) & 0x00555555u;
-}
 
 /* One class against one code.  The miss path is k_lmer_weights': XOR, fold, popcount on both strands and one compare.
  * On a hit the strands' terms are added first and multiplied once (no contraction: the add must stay commutative, so
@@ -58,7 +37,7 @@ template <int L>
 __device__ __forceinline__ void limp_class(uint32_t u, uint32_t x, double w, int d, const double *sh, double (&acc)[L])
 {
 #pragma clang fp contract(off)
-    const uint32_t kf = limp_mask(u, x), kr = limp_mask(u, limp_rc(x, L));
+    const uint32_t kf = lmer_mask(u, x), kr = lmer_mask(u, lmer_rc(x, L));
     const int mf = __builtin_popcount(kf), mr = __builtin_popcount(kr);
     if (min(mf, mr) <= d) {
         const double sf = sh[mf], sr = sh[mr];
@@ -75,10 +54,10 @@ __device__ __forceinline__ void limp_class(uint32_t u, uint32_t x, double w, int
 
 template <int L>
 __global__ __launch_bounds__(LI_THREADS) void k_lmer_importance(const uint32_t *v, const double *cv, int nv, uint32_t u_begin,
-                                                                 uint32_t u_end, const LimpShare S, int d, double *V)
+                                                                 uint32_t u_end, const LmerCoef S, int d, double *V)
 {
-    __shared__ double sh[LI_C];
-    if (threadIdx.x < LI_C) sh[threadIdx.x] = S.s[threadIdx.x];
+    __shared__ double sh[LMER_NC];
+    if (threadIdx.x < LMER_NC) sh[threadIdx.x] = S.c[threadIdx.x];
     __syncthreads();
     /* lanes past the range compare the range's last code and write nothing */
     const uint32_t me = u_begin + blockIdx.x * (uint32_t)LI_THREADS + threadIdx.x;
@@ -119,12 +98,12 @@ __device__ __forceinline__ double limp_gather(const uint32_t *__restrict__ e, in
         const int p = t - i;
         if (p < 0 || p >= n) continue;
         const uint32_t x = e[p]; /* l-mer | weight << 24 (k_pack_lmers) */
-        uint32_t u = x & 0x00FFFFFFu;
+        uint32_t u = x & LMER_CODE;
         if (b >= 0) {
             const int sft = 2 * (L - 1 - i);
             u = (u & ~(3u << sft)) | ((uint32_t)b << sft);
         }
-        const double term = (double)(x >> 24) * V[(size_t)u * L + i];
+        const double term = (double)(x >> LMER_WSHIFT) * V[(size_t)u * L + i];
         acc += term;
     }
     return acc;
@@ -156,7 +135,7 @@ __global__ __launch_bounds__(LG_THREADS) void k_lmer_hyp(const uint32_t *__restr
 
 template <int L>
 void limp_launch(unsigned blocks, hipStream_t stream, const uint32_t *v, const double *cv, int nv, uint32_t u_begin,
-                 uint32_t u_end, const LimpShare &S, int d, double *V)
+                 uint32_t u_end, const LmerCoef &S, int d, double *V)
 {
     hipLaunchKernelGGL(k_lmer_importance<L>, dim3(blocks), dim3(LI_THREADS), 0, stream, v, cv, nv, u_begin, u_end, S, d, V);
 }
@@ -165,8 +144,7 @@ void limp_launch(unsigned blocks, hipStream_t stream, const uint32_t *v, const d
 int limp_gather_prologue(gkmhip_ctx *ctx, int col_begin, int col_end, const char *what, hipStream_t stream, int *tmax)
 {
     if (int rc = check_range(ctx, col_begin, col_end, what)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    (void)hipGetLastError(); /* the launch checks below must see this call's errors only */
+    if (int rc = gkm_launch_enter(ctx)) return rc;
     if (ensure_lmers(ctx, stream, true)) return 4;
     int64_t bases = 0;
     scan_range(ctx, col_begin, col_end, tmax, &bases);
@@ -186,14 +164,10 @@ extern "C" int gkmhip_lmer_importance(gkmhip_ctx *ctx, const double *share, cons
     if (u_begin >= u_end || u_end > codes)
         return set_err_msg("gkmhip_lmer_importance: the code range must satisfy 0 <= u_begin < u_end <= 4^L", 2);
     hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(hipSetDevice(ctx->device));
-    (void)hipGetLastError(); /* the launch checks below must see this call's errors only */
-    LimpShare S;
-    for (int m = 0; m < LI_C; m++) S.s[m] = m <= d ? share[m] : 0.0;
+    if (int rc = gkm_launch_enter(ctx)) return rc;
+    const LmerCoef S = lmer_coef(share, d);
     const unsigned blocks = (unsigned)((u_end - u_begin + LI_THREADS - 1) / LI_THREADS);
-    hipEvent_t e0, e1;
-    if (gkm_launch_events(ctx, &e0, &e1)) return 4;
-    HIPCHK(hipEventRecord(e0, stream));
+    if (int rc = gkm_launch_begin(ctx, stream)) return rc;
     switch (L) {
 #define LIMP_CASE(N) \
     case N: limp_launch<N>(blocks, stream, v, cv, nv, u_begin, u_end, S, d, V); break;
@@ -201,11 +175,8 @@ extern "C" int gkmhip_lmer_importance(gkmhip_ctx *ctx, const double *share, cons
         LIMP_CASE(7) LIMP_CASE(8) LIMP_CASE(9) LIMP_CASE(10) LIMP_CASE(11) LIMP_CASE(12)
 #undef LIMP_CASE
     }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, stream));
-    ctx->ev_valid = true;
-    ctx->last_comparisons = 2.0 * (double)nv * (double)(u_end - u_begin);
-    ctx->last_kernel = "k_lmer_importance";
+    if (int rc = gkm_launch_stop(ctx, stream)) return rc;
+    gkm_launch_done(ctx, "k_lmer_importance", 2.0 * (double)nv * (double)(u_end - u_begin));
     if (getenv("GKM_TRACE"))
         fprintf(stderr, "gkmhip: lmer importance, %d classes x codes [%u, %u) -> k_lmer_importance (%.3g comparisons)\n", nv,
                 u_begin, u_end, ctx->last_comparisons);
@@ -219,18 +190,13 @@ extern "C" int gkmhip_lmer_explain(gkmhip_ctx *ctx, int col_begin, int col_end, 
     hipStream_t stream = (hipStream_t)stream_;
     int tmax = 0;
     if (int rc = limp_gather_prologue(ctx, col_begin, col_end, "gkmhip_lmer_explain", stream, &tmax)) return rc;
-    hipEvent_t e0, e1;
-    if (gkm_launch_events(ctx, &e0, &e1)) return 4;
-    HIPCHK(hipEventRecord(e0, stream));
+    if (int rc = gkm_launch_begin(ctx, stream)) return rc;
     hipLaunchKernelGGL(k_lmer_explain, dim3((unsigned)(col_end - col_begin), (unsigned)((tmax + LG_THREADS - 1) / LG_THREADS)),
                        dim3(LG_THREADS), 0, stream, (const uint32_t *)ctx->lmf.p, (const int64_t *)ctx->lmoff.p,
                        (const int64_t *)ctx->off.p, (const int *)ctx->len.p, ctx->L, col_begin, V, xscale, E);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, stream));
-    ctx->ev_valid = true;
+    if (int rc = gkm_launch_stop(ctx, stream)) return rc;
     /* (gathers: every l-mer is looked up once per base it covers) */
-    ctx->last_comparisons = (double)ctx->L * (ctx->h_cum_n[(size_t)col_end] - ctx->h_cum_n[(size_t)col_begin]);
-    ctx->last_kernel = "k_lmer_explain";
+    gkm_launch_done(ctx, "k_lmer_explain", (double)ctx->L * (ctx->h_cum_n[(size_t)col_end] - ctx->h_cum_n[(size_t)col_begin]));
     return 0;
 }
 
@@ -240,16 +206,11 @@ extern "C" int gkmhip_lmer_hyp(gkmhip_ctx *ctx, int col_begin, int col_end, cons
     hipStream_t stream = (hipStream_t)stream_;
     int tmax = 0;
     if (int rc = limp_gather_prologue(ctx, col_begin, col_end, "gkmhip_lmer_hyp", stream, &tmax)) return rc;
-    hipEvent_t e0, e1;
-    if (gkm_launch_events(ctx, &e0, &e1)) return 4;
-    HIPCHK(hipEventRecord(e0, stream));
+    if (int rc = gkm_launch_begin(ctx, stream)) return rc;
     hipLaunchKernelGGL(k_lmer_hyp, dim3((unsigned)(col_end - col_begin), (unsigned)((4 * tmax + LG_THREADS - 1) / LG_THREADS)),
                        dim3(LG_THREADS), 0, stream, (const uint32_t *)ctx->lmf.p, (const int64_t *)ctx->lmoff.p,
                        (const int64_t *)ctx->off.p, (const int *)ctx->len.p, ctx->L, col_begin, V, R);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, stream));
-    ctx->ev_valid = true;
-    ctx->last_comparisons = 4.0 * (double)ctx->L * (ctx->h_cum_n[(size_t)col_end] - ctx->h_cum_n[(size_t)col_begin]);
-    ctx->last_kernel = "k_lmer_hyp";
+    if (int rc = gkm_launch_stop(ctx, stream)) return rc;
+    gkm_launch_done(ctx, "k_lmer_hyp", 4.0 * (double)ctx->L * (ctx->h_cum_n[(size_t)col_end] - ctx->h_cum_n[(size_t)col_begin]));
     return 0;
 }

@@ -17,43 +17,19 @@
  * Neither uses atomics or depends on the launch geometry: W[u] is a function of u, c and (v, cv) only, and a query's T of
  * the query and W only, bit for bit.
  */
-#include "gkm_gram_bitslice.h" /* (sgpr_words) */
+#include "gkm_lmer_dev.h"
 
 namespace {
 
 constexpr int LW_THREADS = 256;
 constexpr int LW_QB = 8;       /* classes per scalar request */
-constexpr int LW_C = 16;       /* c in LDS, zero beyond d: a mismatch count is at most L <= 12 */
 constexpr int LS_THREADS = 256; /* four queries per workgroup in k_lmer_score */
 
-typedef const double __attribute__((address_space(4))) *sgpr_doubles;
-
-struct LmerC {
-    double c[LW_C];
-};
-
-/* reverse complement of an l-mer code (first base in the highest pair): complement every base, reverse the order of
- * the pairs.  The bit reversal swaps the two bits inside each pair too, which the second line undoes; the complemented
- * bits above 2L land at the bottom and are shifted out. */
-__device__ __forceinline__ uint32_t lmer_rc(uint32_t v, int L)
-{
-    uint32_t x = __builtin_bitreverse32(~v);
-    x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
-    return x >> (32 - 2 * L);
-}
-
-__device__ __forceinline__ int lmer_mm(uint32_t u, uint32_t v)
-{
-    uint32_t t = u ^ v;
-    t = (t | (t >> 1)) & 0x00555555u;
-    return __builtin_popcount(t);
-}
-
 __global__ __launch_bounds__(LW_THREADS) void k_lmer_weights(const uint32_t *v, const double *cv, int nv, uint32_t u_begin,
-                                                              uint32_t u_end, const LmerC C, int L, int d, double *W)
+                                                              uint32_t u_end, const LmerCoef C, int L, int d, double *W)
 {
-    __shared__ double cs[LW_C];
-    if (threadIdx.x < LW_C) cs[threadIdx.x] = C.c[threadIdx.x];
+    __shared__ double cs[LMER_NC];
+    if (threadIdx.x < LMER_NC) cs[threadIdx.x] = C.c[threadIdx.x];
     __syncthreads();
     /* lanes past the range compare the range's last code and write nothing */
     const uint32_t u = min(u_begin + blockIdx.x * (uint32_t)LW_THREADS + threadIdx.x, u_end - 1u);
@@ -97,7 +73,7 @@ __global__ __launch_bounds__(LS_THREADS) void k_lmer_score(const uint32_t *__res
     double acc = 0.0;
     for (int p = lane; p < n; p += 64) {
         const uint32_t x = e[p]; /* l-mer | weight << 24 (k_pack_lmers) */
-        acc += (double)(x >> 24) * W[x & 0x00FFFFFFu];
+        acc += (double)(x >> LMER_WSHIFT) * W[x & LMER_CODE];
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
@@ -115,20 +91,13 @@ extern "C" int gkmhip_lmer_weights(gkmhip_ctx *ctx, const double *c, const uint3
     if (u_begin >= u_end || u_end > codes)
         return set_err_msg("gkmhip_lmer_weights: the code range must satisfy 0 <= u_begin < u_end <= 4^L", 2);
     hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(hipSetDevice(ctx->device));
-    (void)hipGetLastError(); /* the launch checks below must see this call's errors only */
-    LmerC C;
-    for (int m = 0; m < LW_C; m++) C.c[m] = m <= d ? c[m] : 0.0;
+    if (int rc = gkm_launch_enter(ctx)) return rc;
+    const LmerCoef C = lmer_coef(c, d);
     const unsigned blocks = (unsigned)((u_end - u_begin + LW_THREADS - 1) / LW_THREADS);
-    hipEvent_t e0, e1;
-    if (gkm_launch_events(ctx, &e0, &e1)) return 4;
-    HIPCHK(hipEventRecord(e0, stream));
+    if (int rc = gkm_launch_begin(ctx, stream)) return rc;
     hipLaunchKernelGGL(k_lmer_weights, dim3(blocks), dim3(LW_THREADS), 0, stream, v, cv, nv, u_begin, u_end, C, L, d, W);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, stream));
-    ctx->ev_valid = true;
-    ctx->last_comparisons = 2.0 * (double)nv * (double)(u_end - u_begin);
-    ctx->last_kernel = "k_lmer_weights";
+    if (int rc = gkm_launch_stop(ctx, stream)) return rc;
+    gkm_launch_done(ctx, "k_lmer_weights", 2.0 * (double)nv * (double)(u_end - u_begin));
     if (getenv("GKM_TRACE"))
         fprintf(stderr, "gkmhip: lmer weights, %d classes x codes [%u, %u) -> k_lmer_weights (%.3g comparisons)\n", nv,
                 u_begin, u_end, ctx->last_comparisons);
@@ -140,20 +109,14 @@ extern "C" int gkmhip_lmer_score(gkmhip_ctx *ctx, int col_begin, int col_end, co
     if (!ctx || !W || !out) return set_err_msg("gkmhip_lmer_score: bad arguments", 2);
     if (int rc = check_range(ctx, col_begin, col_end, "gkmhip_lmer_score")) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(hipSetDevice(ctx->device));
-    (void)hipGetLastError();
+    if (int rc = gkm_launch_enter(ctx)) return rc;
     if (ensure_lmers(ctx, stream, true)) return 4;
     const int per = LS_THREADS / 64;
-    hipEvent_t e0, e1;
-    if (gkm_launch_events(ctx, &e0, &e1)) return 4;
-    HIPCHK(hipEventRecord(e0, stream));
+    if (int rc = gkm_launch_begin(ctx, stream)) return rc;
     hipLaunchKernelGGL(k_lmer_score, dim3((unsigned)((col_end - col_begin + per - 1) / per)), dim3(LS_THREADS), 0, stream,
                        (const uint32_t *)ctx->lmf.p, (const int64_t *)ctx->lmoff.p, (const int *)ctx->len.p, ctx->L,
                        col_begin, col_end, W, out);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, stream));
-    ctx->ev_valid = true;
-    ctx->last_comparisons = ctx->h_cum_n[(size_t)col_end] - ctx->h_cum_n[(size_t)col_begin]; /* (l-mers looked up) */
-    ctx->last_kernel = "k_lmer_score";
+    if (int rc = gkm_launch_stop(ctx, stream)) return rc;
+    gkm_launch_done(ctx, "k_lmer_score", ctx->h_cum_n[(size_t)col_end] - ctx->h_cum_n[(size_t)col_begin]); /* (l-mers looked up) */
     return 0;
 }

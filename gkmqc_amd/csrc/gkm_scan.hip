@@ -10,7 +10,7 @@
  * kernels take the context for L and d only, and plain device pointers.
  *
  * Kernels
- *   k_scan_lmers     base codes + validity mask -> one word per forward l-mer: the 2L-bit code, SCAN_BAD set when the l-mer
+ *   k_scan_lmers     base codes + validity mask -> one word per forward l-mer: the 2L-bit code, LMER_BAD set when the l-mer
  *                    covers an invalid base
  *   k_scan_profiles  HOT.  One workgroup owns a stretch of g <= 64 consecutive windows and stages their n + (g - 1) s
  *                    l-mer words in LDS.  Both strand terms are symmetric in (p, q), so lane p compares its l-mer (and
@@ -25,12 +25,10 @@
  *
  * A flagged l-mer takes part in no pair: a window that holds one has no profile worth reading, and the caller drops it.
  */
-#include "gkm_internal.h"
+#include "gkm_lmer_dev.h"
 
 namespace {
 
-constexpr uint32_t SCAN_BAD = 0x80000000u; /* the l-mer covers an invalid base */
-constexpr uint32_t SCAN_CODE = 0x00FFFFFFu;
 constexpr int SP_THREADS = 256;
 constexpr int SP_WAVES = SP_THREADS / 64;
 constexpr int SP_GMAX = 64;       /* windows per stretch: one lane each when a hit is resolved */
@@ -51,20 +49,6 @@ inline double stretch_comparisons(int n, int s, int gw)
     return 2.0 * (S * n - 0.5 * (double)n * (n - 1));
 }
 
-__device__ __forceinline__ uint32_t scan_rc(uint32_t v, int L)
-{
-    uint32_t x = __builtin_bitreverse32(~v);
-    x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
-    return x >> (32 - 2 * L);
-}
-
-__device__ __forceinline__ int scan_mm(uint32_t u, uint32_t v)
-{
-    uint32_t t = u ^ v;
-    t = (t | (t >> 1)) & 0x00555555u;
-    return __builtin_popcount(t);
-}
-
 __global__ __launch_bounds__(256) void k_scan_lmers(const uint8_t *__restrict__ codes, const uint8_t *__restrict__ valid,
                                                     int64_t nlm, int L, uint32_t *__restrict__ lm)
 {
@@ -75,7 +59,7 @@ __global__ __launch_bounds__(256) void k_scan_lmers(const uint8_t *__restrict__ 
         v = (v << 2) | (uint32_t)(codes[p + i] & 3);
         ok &= (uint32_t)(valid[p + i] != 0);
     }
-    lm[p] = ok ? v : (v | SCAN_BAD);
+    lm[p] = ok ? v : (v | LMER_BAD);
 }
 
 /* lm: the l-mer words from the first window's first l-mer on; window i of the launch starts at l-mer i * s.
@@ -102,14 +86,14 @@ __global__ __launch_bounds__(SP_THREADS) void k_scan_profiles(const uint32_t *__
     for (int base = wave * 64; base < S; base += SP_THREADS) {
         const int p = base + lane;
         const uint32_t xe = sl[min(p, S - 1)];
-        const bool pok = p < S && !(xe & SCAN_BAD);
-        const uint32_t xf = xe & SCAN_CODE, xr = scan_rc(xf, L);
+        const bool pok = p < S && !(xe & LMER_BAD);
+        const uint32_t xf = xe & LMER_CODE, xr = lmer_rc(xf, L);
         const int dmax = min(n, S - base); /* (wave-uniform) */
         for (int delta = 0; delta < dmax; delta++) {
             const int q = p + delta;
             const uint32_t ye = sl[min(q, S - 1)];
-            const int mf = scan_mm(xf, ye & SCAN_CODE), mr = scan_mm(xr, ye & SCAN_CODE);
-            const bool hit = pok && q < S && !(ye & SCAN_BAD) && min(mf, mr) <= d;
+            const int mf = lmer_mm(xf, ye & LMER_CODE), mr = lmer_mm(xr, ye & LMER_CODE);
+            const bool hit = pok && q < S && !(ye & LMER_BAD) && min(mf, mr) <= d;
             unsigned long long todo = __ballot(hit);
             const int mm = mf | (mr << 8);
             while (todo) {
@@ -147,7 +131,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_scan_score(const uint32_t *__res
     if (i >= nwin) return; /* a whole wave: nothing below waits for the workgroup */
     const uint32_t *e = lm + i * s;
     double acc = 0.0;
-    for (int p = lane; p < n; p += 64) acc += (double)wt[p] * W[e[p] & SCAN_CODE];
+    for (int p = lane; p < n; p += 64) acc += (double)wt[p] * W[e[p] & LMER_CODE];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
     if (lane == 0) out[i] = acc;
@@ -183,8 +167,7 @@ extern "C" int gkmhip_scan_lmers(gkmhip_ctx *ctx, const uint8_t *codes, const ui
     if (nlm < 1 || nlm > ((int64_t)1 << 31) * 256 - 256)
         return set_err_msg("gkmhip_scan_lmers: needs at least L bases (and fewer than 2^39)", 2);
     hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(hipSetDevice(ctx->device));
-    (void)hipGetLastError();
+    if (int rc = gkm_launch_enter(ctx)) return rc;
     hipLaunchKernelGGL(k_scan_lmers, dim3((unsigned)((nlm + 255) / 256)), dim3(256), 0, stream, codes, valid, nlm, ctx->L, lm);
     HIPCHK(hipGetLastError());
     return 0;
@@ -202,18 +185,13 @@ extern "C" int gkmhip_scan_profiles(gkmhip_ctx *ctx, const uint32_t *lm, int64_t
     /* counters, the longest stretch, wt */
     const size_t lds = (size_t)SP_WAVES * (d + 1) * 64 * 8 + ((size_t)n + (size_t)(g - 1) * stride) * 4 + (size_t)n;
     hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(hipSetDevice(ctx->device));
-    (void)hipGetLastError();
-    hipEvent_t e0, e1;
-    if (gkm_launch_events(ctx, &e0, &e1)) return 4;
-    HIPCHK(hipEventRecord(e0, stream));
+    if (int rc = gkm_launch_enter(ctx)) return rc;
+    if (int rc = gkm_launch_begin(ctx, stream)) return rc;
     hipLaunchKernelGGL(k_scan_profiles, dim3((unsigned)blocks), dim3(SP_THREADS), lds, stream, lm, wt, n, stride, g, nwin,
                        ctx->L, d, prof);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, stream));
-    ctx->ev_valid = true;
-    ctx->last_comparisons = (double)(blocks - 1) * stretch_comparisons(n, stride, g) + stretch_comparisons(n, stride, last);
-    ctx->last_kernel = "k_scan_profiles";
+    if (int rc = gkm_launch_stop(ctx, stream)) return rc;
+    gkm_launch_done(ctx, "k_scan_profiles",
+                    (double)(blocks - 1) * stretch_comparisons(n, stride, g) + stretch_comparisons(n, stride, last));
     if (getenv("GKM_TRACE"))
         fprintf(stderr, "gkmhip: scan profiles, %lld windows of %d l-mers at stride %d -> k_scan_profiles (%lld stretches of "
                         "%d windows, %zu bytes of LDS, %.3g comparisons)\n", (long long)nwin, n, stride, (long long)blocks, g,
@@ -228,18 +206,12 @@ extern "C" int gkmhip_scan_score(gkmhip_ctx *ctx, const uint32_t *lm, int64_t nl
     if (n < 0) return -n;
     if (!W) return set_err_msg("gkmhip_scan_score: bad arguments", 2);
     hipStream_t stream = (hipStream_t)stream_;
-    HIPCHK(hipSetDevice(ctx->device));
-    (void)hipGetLastError();
+    if (int rc = gkm_launch_enter(ctx)) return rc;
     const int per = SS_THREADS / 64;
-    hipEvent_t e0, e1;
-    if (gkm_launch_events(ctx, &e0, &e1)) return 4;
-    HIPCHK(hipEventRecord(e0, stream));
+    if (int rc = gkm_launch_begin(ctx, stream)) return rc;
     hipLaunchKernelGGL(k_scan_score, dim3((unsigned)((nwin + per - 1) / per)), dim3(SS_THREADS), 0, stream, lm, wt, n, stride,
                        nwin, W, out);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, stream));
-    ctx->ev_valid = true;
-    ctx->last_comparisons = (double)nwin * n; /* (l-mers looked up) */
-    ctx->last_kernel = "k_scan_score";
+    if (int rc = gkm_launch_stop(ctx, stream)) return rc;
+    gkm_launch_done(ctx, "k_scan_score", (double)nwin * n); /* (l-mers looked up) */
     return 0;
 }

@@ -729,6 +729,17 @@ def default_hyp_block(max_len, d, budget=BLOCK_BYTES):
     return _fit_block(max_len, 8 * (4 * ISM_CHUNKS + 4 * (int(d) + 1) + 28), budget)
 
 
+def _hyp_finish(b, R, prof, c, xscale, dev):
+    """The raw (bases, 4) values R of a block -> its queries' tables: the mutant columns times 1 / sqrt(G(y, y)) (prof:
+    the mutants' self profiles), the own column times explain's xscale."""
+    import torch
+    scale = 1.0 / _mutant_norms_sq(prof[:b.nb], c).sqrt_()
+    own = torch.from_numpy(b.codes.astype(np.int64)).to(dev)
+    per = torch.from_numpy(np.diff(b.qoff)).to(dev)
+    scale.scatter_(1, own[:, None], torch.repeat_interleave(xscale, per)[:, None])
+    return b.split((R[:b.nb] * scale).cpu().numpy())
+
+
 def hypothetical(model, fasta_or_sequences, device=0, block=None, on_block=None):
     """Hypothetical importance of `model` for a FASTA file (or a list / FlatSequences of base codes) -> (names, [float64
     array (T, 4) per query], columns A, C, G, T):
@@ -757,18 +768,13 @@ def hypothetical(model, fasta_or_sequences, device=0, block=None, on_block=None)
         R = torch.empty((most, 4), dtype=torch.float64, device=dev)
         prof = torch.empty((most, 4, d + 1), dtype=torch.int64, device=dev)
         for b in blocks:
-            qb, nb = b.qb, b.nb
+            qb = b.qb
             ctx.ism_self_profiles(S, S + qb, prof.data_ptr(), stream)
             self_ms = ctx.last_kernel_ms() if on_block is not None else None
             coef = dual / sq[:S]
             xscale = 1.0 / sq[S:S + qb]
             ctx.hyp_block(blocks.rows, S, S + qb, share, coef.data_ptr(), R.data_ptr(), stream)
-            # the mutant columns times 1 / sqrt(G(y, y)); the own column times explain's xscale
-            scale = 1.0 / _mutant_norms_sq(prof[:nb], c).sqrt_()
-            own = torch.from_numpy(b.codes.astype(np.int64)).to(dev)
-            per = torch.from_numpy(np.diff(b.qoff)).to(dev)
-            scale.scatter_(1, own[:, None], torch.repeat_interleave(xscale, per)[:, None])
-            out.extend(b.split((R[:nb] * scale).cpu().numpy()))
+            out.extend(_hyp_finish(b, R, prof, c, xscale, dev))
             if on_block is not None:
                 on_block(dict(queries=qb, hyp_kernel_ms=ctx.last_kernel_ms(), comparisons=ctx.last_comparisons(),
                               kernel=ctx.last_kernel_name(), self_kernels_ms=self_ms,
@@ -832,25 +838,34 @@ def lmer_classes(model, sq):
     return v.astype(np.uint32), cv
 
 
-class LmerTable:
+class _FoldedModel:
+    """What the tables a trained model folds into share: the kernel parameters and rho, checked; no support vectors."""
+
+    def _set_params(self, what, kernel_type, L, k, d, M, H, rho, explainable=False):
+        self.kernel_type, self.L, self.k, self.d, self.M = int(kernel_type), int(L), int(k), int(d), int(M)
+        self.H, self.rho = float(H), float(rho)
+        bad = dv.check_parameters(self.kernel_type, self.L, self.k, self.d)
+        if bad:
+            raise ModelError("kernel parameters rejected: %s" % bad)
+        check_table_model(self, what)
+        if explainable:
+            check_explainable(self, what)
+        if not 0 <= self.M <= 255 or not (np.isfinite(self.H) and np.isfinite(self.rho)):
+            raise ModelError("M must lie in 0..255, H and rho must be finite")
+
+    def kernel_params(self):
+        return (self.kernel_type, self.L, self.k, self.d, self.M, self.H, 1.0)
+
+
+class LmerTable(_FoldedModel):
     """A trained model folded into one weight per l-mer: W (float64, 4^L, indexed by code, W[u] ==
     W[rc(u)]) plus what scoring needs -- the kernel parameters and rho; no support vectors."""
 
     def __init__(self, W, kernel_type, L, k, d, M, H, rho):
-        self.kernel_type, self.L, self.k, self.d, self.M = int(kernel_type), int(L), int(k), int(d), int(M)
-        self.H, self.rho = float(H), float(rho)
         self.W = np.ascontiguousarray(W, dtype=np.float64)
-        bad = dv.check_parameters(self.kernel_type, self.L, self.k, self.d)
-        if bad:
-            raise ModelError("kernel parameters rejected: %s" % bad)
-        check_table_model(self, "table")
-        if not 0 <= self.M <= 255 or not (np.isfinite(self.H) and np.isfinite(self.rho)):
-            raise ModelError("M must lie in 0..255, H and rho must be finite")
+        self._set_params("table", kernel_type, L, k, d, M, H, rho)
         if self.W.shape != (4 ** self.L,):
             raise ModelError("a table for L = %d needs 4^L = %d weights" % (self.L, 4 ** self.L))
-
-    def kernel_params(self):
-        return (self.kernel_type, self.L, self.k, self.d, self.M, self.H, 1.0)
 
     def save(self, path):
         """Write the weights file (format: INTEGRATION.md §5b): `# key value` header lines, then LMER<TAB>weight for
@@ -948,17 +963,11 @@ def load_lmer_table(path):
     return LmerTable(W, val["kernel_type"], L, val["k"], val["d"], val["M"], val["H"], val["rho"])
 
 
-def lmer_weights(model, device=0, on_piece=None):
-    """The l-mer weight table of `model` -> LmerTable (DESIGN.md §5g):
-
-        W(u) = sum_s (dual_coef_s / sq_s) sum_q w_s[q] (c[m(u, f_q)] + c[m(u, rc(f_q))])      (c[m] = 0 for m > d)
-
-    so that score(x) = sum_p w_x[p] W(u_p) / sq_x + rho on the no-wrap domain (INTEGRATION.md §5b; sq_s from exact 64-bit
-    self profiles, so beyond it the table holds the exact model where `score` follows the reference's wrap).  Every model `score` serves except RBF (types 3 and 5), k = 0
-    included.  The support vectors' self norms come from one gkmhip_self_profiles launch, the classes (v, cv) from the host
-    (lmer_classes), W from k_lmer_weights over all 4^L codes in pieces of TABLE_PIECE.  on_piece(dict) (measurements):
-    called after every piece with its codes, kernel milliseconds (HIP events) and l-mer comparisons."""
-    check_table_model(model)
+def _fold_table(model, device, on_piece, width, method, coef=None):
+    """The support-vector side of `model` folded over all 4^L codes -> float64 host array (4^L, width): the support
+    vectors uploaded, their exact self norms, the classes (v, cv) of lmer_classes on the device, then the context's
+    `method` (lmer_weights or lmer_importance; coef: its d + 1 coefficients, default c) per piece of TABLE_PIECE codes,
+    on_piece after each."""
     import torch
     S, L, d = model.n_sv, model.L, model.d
     ctx = dv.cached_context(*model.kernel_params(), device=device)
@@ -972,15 +981,30 @@ def lmer_weights(model, device=0, on_piece=None):
         v, cv = lmer_classes(model, sq.cpu().numpy())
         d_v = torch.from_numpy(v.view(np.int32)).to(dev)
         d_cv = torch.from_numpy(cv).to(dev)
-        W = torch.empty(4 ** L, dtype=torch.float64, device=dev)
+        out = torch.empty((4 ** L, width), dtype=torch.float64, device=dev)
         for u0 in range(0, 4 ** L, TABLE_PIECE):
             u1 = min(4 ** L, u0 + TABLE_PIECE)
-            ctx.lmer_weights(c, d_v.data_ptr(), d_cv.data_ptr(), len(v), u0, u1, W.data_ptr() + 8 * u0, stream)
+            getattr(ctx, method)(c if coef is None else coef, d_v.data_ptr(), d_cv.data_ptr(), len(v), u0, u1,
+                                 out.data_ptr() + 8 * width * u0, stream)
             if on_piece is not None:
                 on_piece(dict(codes=u1 - u0, classes=len(v), kernel_ms=ctx.last_kernel_ms(),
                               comparisons=ctx.last_comparisons(), kernel=ctx.last_kernel_name()))
-        Wh = W.cpu().numpy()
-    return LmerTable(Wh, model.kernel_type, L, model.k, d, model.M, model.H, model.rho)
+        return out.cpu().numpy()
+
+
+def lmer_weights(model, device=0, on_piece=None):
+    """The l-mer weight table of `model` -> LmerTable (DESIGN.md §5g):
+
+        W(u) = sum_s (dual_coef_s / sq_s) sum_q w_s[q] (c[m(u, f_q)] + c[m(u, rc(f_q))])      (c[m] = 0 for m > d)
+
+    so that score(x) = sum_p w_x[p] W(u_p) / sq_x + rho on the no-wrap domain (INTEGRATION.md §5b; sq_s from exact 64-bit
+    self profiles, so beyond it the table holds the exact model where `score` follows the reference's wrap).  Every model `score` serves except RBF (types 3 and 5), k = 0
+    included.  The support vectors' self norms come from one gkmhip_self_profiles launch, the classes (v, cv) from the host
+    (lmer_classes), W from k_lmer_weights over all 4^L codes in pieces of TABLE_PIECE.  on_piece(dict) (measurements):
+    called after every piece with its codes, kernel milliseconds (HIP events) and l-mer comparisons."""
+    check_table_model(model)
+    Wh = _fold_table(model, device, on_piece, 1, "lmer_weights").reshape(-1)
+    return LmerTable(Wh, model.kernel_type, model.L, model.k, model.d, model.M, model.H, model.rho)
 
 
 def default_table_block(max_len, budget=BLOCK_BYTES):
@@ -1020,28 +1044,17 @@ _IMPORTANCE_FLOATS = ("H", "rho")
 _IMPORTANCE_KEYS = ("format",) + _IMPORTANCE_INTS + _IMPORTANCE_FLOATS + ("V",)
 
 
-class LmerImportanceTable:
+class LmerImportanceTable(_FoldedModel):
     """A trained model folded into one value per (l-mer, offset): V (float64, (4^L, L), indexed by code
     and by the offset from the l-mer's first base; V[rc(u), L-1-i] == V[u, i] and V.sum(1) is the weight table's W) plus
     what explaining needs -- the kernel parameters and rho; no support vectors."""
 
     def __init__(self, V, kernel_type, L, k, d, M, H, rho):
-        self.kernel_type, self.L, self.k, self.d, self.M = int(kernel_type), int(L), int(k), int(d), int(M)
-        self.H, self.rho = float(H), float(rho)
-        bad = dv.check_parameters(self.kernel_type, self.L, self.k, self.d)
-        if bad:
-            raise ModelError("kernel parameters rejected: %s" % bad)
-        check_table_model(self, "importance table")
-        check_explainable(self, "importance table")
-        if not 0 <= self.M <= 255 or not (np.isfinite(self.H) and np.isfinite(self.rho)):
-            raise ModelError("M must lie in 0..255, H and rho must be finite")
+        self._set_params("importance table", kernel_type, L, k, d, M, H, rho, explainable=True)
         self.V = np.ascontiguousarray(V, dtype=np.float64)
         if self.V.shape != (4 ** self.L, self.L):
             raise ModelError("an importance table for L = %d needs (4^L, L) = (%d, %d) values"
                              % (self.L, 4 ** self.L, self.L))
-
-    def kernel_params(self):
-        return (self.kernel_type, self.L, self.k, self.d, self.M, self.H, 1.0)
 
     def save(self, path):
         """Write the table file (format: INTEGRATION.md §5b) to exactly `path`: an uncompressed .npz with the format
@@ -1109,29 +1122,8 @@ def lmer_importance(model, device=0, on_piece=None):
     from k_lmer_importance over all 4^L codes in pieces of TABLE_PIECE.  on_piece(dict) (measurements): called after
     every piece with its codes, kernel milliseconds (HIP events) and l-mer comparisons."""
     check_explainable(model, "lmer_importance")
-    import torch
-    S, L, d = model.n_sv, model.L, model.d
-    ctx = dv.cached_context(*model.kernel_params(), device=device)
-    dev = torch.device("cuda", device)
-    c = dv.mismatch_weights(model.kernel_type, L, model.k)[:d + 1]
-    share = explain_shares(model)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        ctx.set_sequences(model.flat_seqs(), stream)
-        sq = torch.empty(S, dtype=torch.float64, device=dev)
-        _exact_norms(ctx, S, c, sq, stream)
-        v, cv = lmer_classes(model, sq.cpu().numpy())
-        d_v = torch.from_numpy(v.view(np.int32)).to(dev)
-        d_cv = torch.from_numpy(cv).to(dev)
-        V = torch.empty((4 ** L, L), dtype=torch.float64, device=dev)
-        for u0 in range(0, 4 ** L, TABLE_PIECE):
-            u1 = min(4 ** L, u0 + TABLE_PIECE)
-            ctx.lmer_importance(share, d_v.data_ptr(), d_cv.data_ptr(), len(v), u0, u1, V.data_ptr() + 8 * L * u0, stream)
-            if on_piece is not None:
-                on_piece(dict(codes=u1 - u0, classes=len(v), kernel_ms=ctx.last_kernel_ms(),
-                              comparisons=ctx.last_comparisons(), kernel=ctx.last_kernel_name()))
-        Vh = V.cpu().numpy()
-    return LmerImportanceTable(Vh, model.kernel_type, L, model.k, d, model.M, model.H, model.rho)
+    Vh = _fold_table(model, device, on_piece, model.L, "lmer_importance", explain_shares(model))
+    return LmerImportanceTable(Vh, model.kernel_type, model.L, model.k, model.d, model.M, model.H, model.rho)
 
 
 def default_imptable_block(max_len, d=None, budget=BLOCK_BYTES):
@@ -1189,17 +1181,12 @@ def hypothetical_with_table(itable, fasta_or_sequences, device=0, block=None, on
         R = torch.empty((most, 4), dtype=torch.float64, device=dev)
         prof = torch.empty((most, 4, d + 1), dtype=torch.int64, device=dev)
         for b in blocks:
-            qb, nb = b.qb, b.nb
+            qb = b.qb
             ctx.ism_self_profiles(0, qb, prof.data_ptr(), stream)
             self_ms = ctx.last_kernel_ms() if on_block is not None else None
             xscale = 1.0 / sq[:qb]
             ctx.lmer_hyp(0, qb, V.data_ptr(), R.data_ptr(), stream)
-            # the mutant columns times 1 / sqrt(G(y, y)); the own column times explain's xscale (as `hypothetical`)
-            scale = 1.0 / _mutant_norms_sq(prof[:nb], c).sqrt_()
-            own = torch.from_numpy(b.codes.astype(np.int64)).to(dev)
-            per = torch.from_numpy(np.diff(b.qoff)).to(dev)
-            scale.scatter_(1, own[:, None], torch.repeat_interleave(xscale, per)[:, None])
-            out.extend(b.split((R[:nb] * scale).cpu().numpy()))
+            out.extend(_hyp_finish(b, R, prof, c, xscale, dev))
             if on_block is not None:
                 on_block(dict(queries=qb, hyp_kernel_ms=ctx.last_kernel_ms(), gathers=ctx.last_comparisons(),
                               kernel=ctx.last_kernel_name(), self_kernels_ms=self_ms,
