@@ -6,6 +6,7 @@
  */
 #include <stdint.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <vector>
 
 #include "gkm_bitslice.h"
@@ -188,10 +189,15 @@ extern "C" void bsprobe_piece_valid(int b0, int nb, int cnt, int W, uint32_t *ou
  * Packs the rows with gkmpack::pack_rows, checks the packing invariants, builds every lane's
  * planes from its pieces, runs the lane program and attributes each hit to its piece's row.
  * P_out[i*(d+1)+m] for row i.  Returns 0, or a negative code naming the violated invariant. */
+/* shift_trip > 0: the hits take the way of k_gram_bitslice's SHIFT RECORDS (gkm_bitslice.h shift_record_visit) -- per shift
+ * the two group ORs that the kernel's counting loop computes, one push per shift with a hit, a stack per lane and strand,
+ * trips over the shift_trip records on top as soon as the stack holds that many (visit, re-push what is left), the stack
+ * emptied at the end of the strand; a visit resolves the hits among the five windows of its (bit row, group).
+ * visits_out[0..2]: records pushed, visits made, records put back. */
 template <int W, int L, int D>
 static int run_packed(const uint8_t *codes, const int64_t *off, const int *rows, int nrows, int col,
                       const uint8_t *wd, int32_t *P_out, int *lanes_used, int max_rows = gkmpack::MAX_ROWS, int own_mult = 1,
-                      int rider_w = 0)
+                      int rider_w = 0, int shift_trip = 0, long long *visits_out = nullptr)
 {
     using namespace gkmpack;
     std::vector<int> nwin((size_t)nrows);
@@ -269,16 +275,8 @@ static int run_packed(const uint8_t *codes, const int64_t *off, const int *rows,
                                        piece_bit(seq, len, pc.b0, pc.nb, pc.p0, pc.cnt, b, w, W, 1)) << (2 * (i & 15));
                 }
         }
-        for (int st = 0; st < 2; st++)
-            for (int delta = 0; delta < T; delta++) {
-                uint32_t hit[W];
-                window_hits<W, L, D>(Ahi, Alo, AV, &sb[st][0][(size_t)delta], &sb[st][1][(size_t)delta],
-                                     (const uint32_t *)nullptr, hit);
-                for (int w = 0; w < W; w++) {
-                    uint32_t h = hit[w];
-                    while (h) {
-                        const int bit = __builtin_ctz(h);
-                        h &= h - 1u;
+        /* one hit: bit row `bit` of word w of the shift (delta, st); -20 if a flagged window exceeds D */
+        auto resolve = [&](int bit, int w, int delta, int st) -> int {
                         const Piece &pc = P.pieces[pi + (size_t)piece_of_bitrow(start_mask, bit)];
                         const uint8_t *seq = codes + off[pc.row];
                         const int len = (int)(off[pc.row + 1] - off[pc.row]), nA = len - L + 1;
@@ -292,6 +290,69 @@ static int run_packed(const uint8_t *codes, const int64_t *off, const int *rows,
                         const int i = P.tile_out[(size_t)(pc.lane / LANES) * MAX_ROWS + pc.slot];
                         if (hv.m <= D) acc[(size_t)i * (D + 1) + hv.m] += hv.v;
                         else if (hv.v != 0u) return -20; /* a true hit can never exceed D */
+                        return 0;
+        };
+        if constexpr (W == 2 * SHIFT_GROUP_WORDS) {
+            if (shift_trip > 0) {
+                struct Rec { uint32_t any0, any1, origin; };
+                uint32_t AVg[2] = {0u, 0u};
+                for (int w = 0; w < W; w++) AVg[w / SHIFT_GROUP_WORDS] |= AV[w];
+                for (int st = 0; st < 2; st++) {
+                    std::vector<Rec> stack;
+                    auto trip = [&](size_t c) -> int { /* the c records on top: one visit each, the live ones go back */
+                        std::vector<Rec> top(stack.end() - (long)c, stack.end());
+                        stack.resize(stack.size() - c);
+                        for (Rec r : top) {
+                            const ShiftVisit v = shift_record_visit(r.any0, r.any1);
+                            const int delta = rec_delta(r.origin);
+                            if (rec_w(r.origin) != 0) return -21; /* a shift record's origin carries no word index */
+                            uint32_t hit[W];
+                            window_hits<W, L, D>(Ahi, Alo, AV, &sb[st][0][(size_t)delta], &sb[st][1][(size_t)delta],
+                                                 (const uint32_t *)nullptr, hit);
+                            for (int k = 0; k < SHIFT_GROUP_WORDS; k++)
+                                if ((hit[v.w0 + k] >> v.bit) & 1u)
+                                    if (const int rc = resolve((int)v.bit, (int)v.w0 + k, delta, st)) return rc;
+                            if (visits_out) visits_out[1]++;
+                            if (shift_record_live(r.any0, r.any1)) {
+                                stack.push_back(r);
+                                if (visits_out) visits_out[2]++;
+                            }
+                        }
+                        return 0;
+                    };
+                    for (int delta = 0; delta < T; delta++) {
+                        uint32_t any[2];
+                        if constexpr (top_plane_serves(L, D)) /* (the same-length kernel's entry: a superset per group) */
+                            window_group_any_grouped<W, L, D, SHIFT_GROUP_WORDS>(Ahi, Alo, AVg, &sb[st][0][(size_t)delta],
+                                                                                 &sb[st][1][(size_t)delta], any);
+                        else
+                            window_group_any<W, L, D, SHIFT_GROUP_WORDS>(Ahi, Alo, AV, &sb[st][0][(size_t)delta],
+                                                                         &sb[st][1][(size_t)delta], any);
+                        if (shift_record_live(any[0], any[1])) {
+                            stack.push_back(Rec{any[0], any[1], pack_meta(delta, 0, 0)});
+                            if (visits_out) visits_out[0]++;
+                        }
+                        while (stack.size() >= (size_t)shift_trip)
+                            if (const int rc = trip((size_t)shift_trip)) return rc;
+                    }
+                    while (!stack.empty()) /* the strand's last trips: full ones, then the partial one */
+                        if (const int rc = trip(std::min(stack.size(), (size_t)shift_trip))) return rc;
+                }
+                pi = pj;
+                continue;
+            }
+        }
+        for (int st = 0; st < 2; st++)
+            for (int delta = 0; delta < T; delta++) {
+                uint32_t hit[W];
+                window_hits<W, L, D>(Ahi, Alo, AV, &sb[st][0][(size_t)delta], &sb[st][1][(size_t)delta],
+                                     (const uint32_t *)nullptr, hit);
+                for (int w = 0; w < W; w++) {
+                    uint32_t h = hit[w];
+                    while (h) {
+                        const int bit = __builtin_ctz(h);
+                        h &= h - 1u;
+                        if (const int rc = resolve(bit, w, delta, st)) return rc;
                     }
                 }
             }
@@ -324,6 +385,36 @@ extern "C" int bsprobe_profile_riders(int W, int L, int d, const uint8_t *codes,
     RCASE(10, 11, 3) RCASE(10, 10, 3)
     return 1;
 }
+
+/* The lane program with SHIFT RECORDS between the counting and the hit path (run_packed's shift_trip), over the packing of a
+ * same-length launch: 64 residents per tile, whole groups of five, with riders (riders != 0) or without.  trip = records a
+ * trip takes (the kernel: 64, one per lane; here per lane, so small values exercise the re-push order too). */
+#define SCASE(LL, DD) \
+    if (L == LL && d == DD) \
+        return run_packed<10, LL, DD>(codes, off, rows, nrows, col, wd, P, lanes_used, 64, 5, riders ? gkmpack::RIDER_W : 0, trip, visits);
+extern "C" int bsprobe_profile_shift_records(int L, int d, const uint8_t *codes, const int64_t *off, const int *rows, int nrows,
+                                             int col, const uint8_t *wd, int riders, int trip, int32_t *P, int *lanes_used,
+                                             long long *visits)
+{
+    if (trip <= 0) return 1;
+    SCASE(11, 3) SCASE(10, 3) SCASE(12, 4)
+    return 1;
+}
+
+/* One record through shift_record_visit until it is empty: the (bit row, first word) of every visit, in order; returns the
+ * number of visits (at most 64) */
+extern "C" int bsprobe_shift_record_drain(uint32_t any0, uint32_t any1, int *bits_out, int *w0_out)
+{
+    int n = 0;
+    while (shift_record_live(any0, any1) && n < 64) {
+        const ShiftVisit v = shift_record_visit(any0, any1);
+        bits_out[n] = (int)v.bit;
+        w0_out[n] = (int)v.w0;
+        n++;
+    }
+    return n;
+}
+extern "C" unsigned bsprobe_lowest_bit_or_ones(uint32_t x) { return lowest_bit_or_ones(x); }
 
 /* The packing of a same-length launch as gkm_gram.hip plan_bitslice asks for it (W = 10 words, 64 residents per tile, whole
  * groups of five; rider_w = 0: without riders), for tests/test_rider_packing.py.  pieces_out[k][8] = lane, b0, nb, slot,

@@ -740,5 +740,47 @@ GKM_HD int rec_delta(uint32_t r) { return (int)(r >> 21); }
 GKM_HD int rec_strand(uint32_t r) { return (int)((r >> 4) & 1u); }
 GKM_HD int rec_lane(uint32_t r) { return (int)((r >> META_LANE_SHIFT) & 63u); }
 
+/* ---- SHIFT RECORDS (k_gram_bitslice PK = 6, 7): one record per lane and SHIFT instead of one per lane and group of five
+ * words.  A record is three words: any0 and any1, the group ORs of the shift's two groups of five words (W = 10: which bit
+ * rows of the lane hold a hit somewhere in words 0..4 / 5..9), and the origin word, which then carries no word index (its
+ * bits 0..3 stay 0).  One compaction per shift in the counting loop; the trip that consumes the record finds the group:
+ *   push    a lane with any0 | any1 != 0 appends (any0, any1, origin);
+ *   visit   group g = any0 ? 0 : 1, the lowest bit row b of that group's word, cleared there; the visit resolves the five
+ *           windows at lane positions W b + 5 g .. + 4 exactly as a group record's visit does;
+ *   re-push if any0 | any1 is still non-zero the three words go back to the list.
+ * Every (bit row, group) flagged by the shift is visited exactly once, group 0's bit rows in ascending order first, then
+ * group 1's: popcount(any0) + popcount(any1) visits per record.  The same function runs per lane in the kernel's trip and in
+ * the CPU model (bitslice_cpu_probe.cpp; tests/test_shift_records.py). */
+constexpr int SHIFT_GROUP_WORDS = 5;
+GKM_HD bool shift_record_live(uint32_t any0, uint32_t any1) { return (any0 | any1) != 0u; }
+/* position of the lowest set bit, 0xFFFFFFFF for 0 (v_ffbl_b32's own convention; __builtin_ctz(0) is undefined and the
+ * generic cttz costs a second instruction) */
+GKM_HD uint32_t lowest_bit_or_ones(uint32_t x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t r;
+    asm("v_ffbl_b32 %0, %1" : "=v"(r) : "v"(x));
+    return r;
+#else
+    return x ? (uint32_t)__builtin_ctz(x) : 0xFFFFFFFFu;
+#endif
+}
+struct ShiftVisit {
+    uint32_t bit; /* the bit row visited (0xFFFFFFFF for an empty record: a lane without one in a partial trip) */
+    uint32_t w0;  /* first word of the group visited: 0 or SHIFT_GROUP_WORDS */
+};
+/* one visit: takes the bit row out of (any0, any1) in place; the caller pushes the record again while shift_record_live */
+GKM_HD ShiftVisit shift_record_visit(uint32_t &any0, uint32_t &any1)
+{
+    const bool second = any0 == 0u;
+    ShiftVisit v;
+    v.bit = lowest_bit_or_ones(second ? any1 : any0);
+    v.w0 = second ? (uint32_t)SHIFT_GROUP_WORDS : 0u;
+    const uint32_t rest1 = any1 & (any1 - 1u);
+    any0 &= any0 - 1u; /* (0 stays 0) */
+    any1 = second ? rest1 : any1;
+    return v;
+}
+
 } /* namespace gkmbs */
 #endif

@@ -161,6 +161,7 @@ extern "C" gkmhip_ctx *gkmhip_create(int device, int L, int d, const double *c, 
     if (env) {
         if (!strcmp(env, "direct")) ctx->kernel_pref = GKMHIP_KERNEL_DIRECT;
         else if (!strcmp(env, "bitslice")) ctx->kernel_pref = GKMHIP_KERNEL_BITSLICE;
+        else if (!strcmp(env, "bitslice-groups")) ctx->kernel_pref = GKMHIP_KERNEL_BITSLICE_GROUPS;
     }
     return ctx;
 }
@@ -197,7 +198,7 @@ extern "C" int gkmhip_set_scratch_slot(gkmhip_ctx *ctx, int slot)
 
 extern "C" int gkmhip_set_kernel(gkmhip_ctx *ctx, int which)
 {
-    if (!ctx || which < 0 || which > 2) return set_err_msg("bad kernel selector", 2);
+    if (!ctx || which < 0 || which > GKMHIP_KERNEL_BITSLICE_GROUPS) return set_err_msg("bad kernel selector", 2);
     ctx->kernel_pref = which;
     return 0;
 }
@@ -458,7 +459,7 @@ int ensure_colpk(gkmhip_ctx *ctx, hipStream_t stream, bool wait)
 {
     if (ctx->have_colpk) return 0;
     /* one word more than the bases need: the hit path reads words q/16 and q/16 + 1 */
-    const int pkw = (ctx->maxlen + 15) / 16 + 1;
+    const int pkw = bs_colpk_words(ctx->maxlen);
     if (ctx->colpk.ensure((size_t)ctx->n * 2 * (size_t)pkw)) return 4;
     hipLaunchKernelGGL(k_pack_strands, dim3((unsigned)ctx->n * 2), dim3(64), 0, stream, ctx->codes.p, ctx->off.p, pkw,
                        ctx->colpk.p);
@@ -473,7 +474,7 @@ int ensure_postab(gkmhip_ctx *ctx, hipStream_t stream, bool wait)
 {
     if (ctx->have_postab) return 0;
     /* (+ 8: the same-length variant reads the bytes as aligned pairs of words around index .. index + 4) */
-    const int ptw = ((int)POSTAB_PAD + ctx->L - 1 + ctx->maxlen + (int)POSTAB_PAD + 8 + 3) / 4;
+    const int ptw = bs_postab_words(ctx->maxlen, ctx->L);
     if (ctx->postab.ensure((size_t)ctx->n * (size_t)ptw)) return 4;
     hipLaunchKernelGGL(k_build_postab, dim3((unsigned)ctx->n), dim3(64), 0, stream, ctx->off.p, ctx->L, ctx->wd.p, ptw,
                        ctx->postab.p);

@@ -219,10 +219,15 @@ static double decisive_hit_share(const gkmhip_ctx *ctx)
 }
 static bool auto_takes_bitslice(const gkmhip_ctx *ctx) { return decisive_hit_share(ctx) <= GKM_BITSLICE_MAX_HIT_SHARE; }
 
+static bool forces_bitslice(const gkmhip_ctx *ctx)
+{
+    return ctx->kernel_pref == GKMHIP_KERNEL_BITSLICE || ctx->kernel_pref == GKMHIP_KERNEL_BITSLICE_GROUPS;
+}
+
 bool bitslice_serves(const gkmhip_ctx *ctx)
 {
     if (ctx->kernel_pref == GKMHIP_KERNEL_DIRECT || !gkm_pick_bitslice(2, ctx->L, ctx->d)) return false;
-    return ctx->kernel_pref == GKMHIP_KERNEL_BITSLICE || auto_takes_bitslice(ctx);
+    return forces_bitslice(ctx) || auto_takes_bitslice(ctx);
 }
 
 
@@ -232,6 +237,7 @@ struct BitslicePlan {
     int slots = 64;                   /* row slots per tile: 64 or 128 (the kernel's profiles) */
     int s_slots = 64;                 /* ... of the tile-transposed output: slots, or gkmpack::RIDER_SLOTS with riders */
     bool packed = false, same_length = false, riders = false;
+    bool shift_records = false;       /* same-length variants: one record per lane and shift (PK = 6, 7), not per group */
     bs_kernel_t kernel = nullptr;
     const char *name = "";
     size_t dyn_lds = 0;
@@ -308,6 +314,11 @@ static int plan_bitslice(const gkmhip_ctx *ctx, const int *rows, int nrows, int 
      * wave's trips execute 1.2 % more instructions.  That is accepted: such launches take under 3 ms, and small problems
      * -- the ones a test can check against the oracle -- then run the very path the large ones do.
      * A layout that fails the check is not an error: the launch packs without riders, as before there were any. */
+    /* SHIFT RECORDS (k_gram_bitslice PK = 6, 7; gkm_bitslice.h shift_record_visit): what a same-length launch takes unless
+     * the caller asked for group records by name (GKMHIP_KERNEL_BITSLICE_GROUPS, the cross-check) or the longer hit list
+     * would cost the wave a fifth LDS granule -- and with it the seventh wave per SIMD -- that group records leave it
+     * (gkm_gram_bitslice.h BS_LDS_WAVE_BUDGET; checked below, once the riders are decided). */
+    const bool want_shift_records = ctx->kernel_pref != GKMHIP_KERNEL_BITSLICE_GROUPS && gkm_pick_bitslice(6, L, d) != nullptr;
     if (!packed && gkm_pick_bitslice(5, L, d) != nullptr) {
         gkmpack::Packing withr = pack(64, gkmpack::RIDER_W);
         if (withr.nriders > 0 && withr.ntiles <= P.pk.ntiles && layout_check(withr, gkmpack::RIDER_W, gkmpack::RIDER_SLOTS) == 0) {
@@ -320,7 +331,18 @@ static int plan_bitslice(const gkmhip_ctx *ctx, const int *rows, int nrows, int 
     if (!P.riders) P.s_slots = P.slots;
     const gkmpack::Packing &pk = P.pk;
     const int W = pk.W, ntiles = pk.ntiles, slots = P.slots;
-    P.kernel = gkm_pick_bitslice(P.riders ? 5 : !packed ? 4 : slots == 64 ? 1 : 2, L, d);
+    int variant = P.riders ? 5 : !packed ? 4 : slots == 64 ? 1 : 2; /* k_gram_bitslice's PK */
+    if (!packed && want_shift_records && gkm_pick_bitslice(variant + 2, L, d) != nullptr) {
+        /* (static LDS as the kernel declares it -- it asserts the formula -- plus this launch's dynamic LDS) */
+        const size_t dyn = (size_t)(2 * ctx->pkw + ctx->ptw) * sizeof(uint32_t);
+        const bool fits = (size_t)bs_same_length_static_lds(variant + 2, d) + dyn <= (size_t)BS_LDS_WAVE_BUDGET;
+        const bool groups_fit = (size_t)bs_same_length_static_lds(variant, d) + dyn <= (size_t)BS_LDS_WAVE_BUDGET;
+        if (fits || !groups_fit) { /* (past the budget either way: the list's 512 bytes decide nothing) */
+            variant += 2;
+            P.shift_records = true;
+        }
+    }
+    P.kernel = gkm_pick_bitslice(variant, L, d);
     P.name = !packed ? "k_gram_bitslice<same length>" : slots == 64 ? "k_gram_bitslice<packed>" : "k_gram_bitslice<packed,128>";
     if (!P.kernel) return set_err_msg("bit-sliced kernel not instantiated for this (L, d)", 5);
     if (!packed && !P.riders) { /* (a layout with riders passed the check before it was taken) */
@@ -531,8 +553,9 @@ static int enqueue_bitslice(gkmhip_ctx *ctx, const BitslicePlan &P, int nrows, G
         hipFuncAttributes fa;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)P.kernel, 64, P.dyn_lds) == hipSuccess &&
             hipFuncGetAttributes(&fa, (const void *)P.kernel) == hipSuccess)
-            fprintf(stderr, "gkmhip: hot kernel: %d VGPRs, %zu + %zu bytes of LDS per wave, %d one-wave workgroups per CU\n",
-                    fa.numRegs, (size_t)fa.sharedSizeBytes, P.dyn_lds, per_cu);
+            fprintf(stderr, "gkmhip: hot kernel: %d VGPRs, %zu + %zu bytes of LDS per wave, %d one-wave workgroups per CU%s\n",
+                    fa.numRegs, (size_t)fa.sharedSizeBytes, P.dyn_lds, per_cu,
+                    P.packed ? "" : P.shift_records ? ", shift records" : ", group records");
     }
     ctx->last_kernel = P.name;
     ctx->last_riders = P.riders ? pk.nriders : 0;
@@ -610,7 +633,7 @@ static int gram_launch(gkmhip_ctx *ctx, const int *rows, int nrows, int mode, Gr
     out.col0 = mode == COLS_RANGE ? col_begin : 0;
     /* (W = 10 words per lane; W = 20 was measured too -- config 2: 121 vs 118 ms, 150 bp: 56 vs 31 ms in round 1: the longer
      * per-shift chain does not pay for the registers it costs) */
-    if (ctx->kernel_pref == GKMHIP_KERNEL_BITSLICE && !gkm_pick_bitslice(2, L, d))
+    if (forces_bitslice(ctx) && !gkm_pick_bitslice(2, L, d))
         return set_err_msg("bit-sliced kernel not instantiated for this (L, d)", 5);
     int rc;
     if (bitslice_serves(ctx)) { /* (auto: the general kernel where it is the faster one) */

@@ -75,7 +75,24 @@ constexpr uint32_t POSTAB_PAD = 5;
 
 typedef void (*bs_kernel_t)(const BsArgs);
 /* the instantiation for W = 10 words per lane and packing variant pk (k_gram_bitslice's PK: 4 same length, 5 same length
- * with riders, 1 / 2 several pieces per lane), or nullptr */
+ * with riders, 6 / 7 the same two with shift records, 1 / 2 several pieces per lane), or nullptr */
 bs_kernel_t gkm_pick_bitslice(int pk, int L, int d);
+
+/* LDS of one wave of the same-length variants, for the launch plan: a wave that stays within BS_LDS_WAVE_BUDGET -- four
+ * allocation granules of 1 280 bytes -- leaves room for 7 waves per SIMD (28 per CU of 160 KB), which is what the variants
+ * are compiled for.  Static: the profiles [d + 1][64, or 128 with riders], the hit list of 128 records of two words (group
+ * records) or three (shift records), the rider tags.  Dynamic: the column's two packed strands and its positional weight
+ * table (gkm_context.hip ensure_colpk / ensure_postab). */
+constexpr int BS_LDS_GRANULE = 1280, BS_LDS_WAVE_BUDGET = 4 * BS_LDS_GRANULE;
+constexpr int bs_same_length_static_lds(int pk, int d)
+{
+    return ((d + 1) * ((pk == 5 || pk == 7) ? 128 : 64) + ((pk == 6 || pk == 7) ? 3 : 2) * 128 + ((pk == 5 || pk == 7) ? 64 : 0)) * 4;
+}
+constexpr int bs_colpk_words(int maxlen) { return (maxlen + 15) / 16 + 1; }
+constexpr int bs_postab_words(int maxlen, int L) { return ((int)POSTAB_PAD + L - 1 + maxlen + (int)POSTAB_PAD + 8 + 3) / 4; }
+constexpr int bs_same_length_dyn_lds(int len, int L) { return (2 * bs_colpk_words(len) + bs_postab_words(len, L)) * 4; }
+/* the shapes the shift records were built for keep their seven waves: 300 bp with riders, 600 bp without */
+static_assert(bs_same_length_static_lds(7, 3) + bs_same_length_dyn_lds(300, 11) <= BS_LDS_WAVE_BUDGET, "300 bp, riders, shift records");
+static_assert(bs_same_length_static_lds(6, 3) + bs_same_length_dyn_lds(600, 10) <= BS_LDS_WAVE_BUDGET, "600 bp, shift records");
 
 #endif

@@ -7,15 +7,6 @@
  */
 #include "gkm_gram_bitslice.h"
 
-/* position of the lowest set bit, 0xFFFFFFFF for 0 (v_ffbl_b32's own convention; __builtin_ctz(0) is
- * undefined and the generic cttz costs a second instruction) */
-__device__ __forceinline__ uint32_t ffbl_or_ones(uint32_t x)
-{
-    uint32_t r;
-    asm("v_ffbl_b32 %0, %1" : "=v"(r) : "v"(x));
-    return r;
-}
-
 /* 2 x as an addition: on gfx950 v_lshlrev_b32 issues at HALF the rate of v_add_u32 (tools/valu_ops.hip), and hipcc
  * turns x + x back into a shift */
 __device__ __forceinline__ uint32_t twice(uint32_t x)
@@ -59,7 +50,7 @@ constexpr int BS_CAP = BS_TRIP + 64;
  * control flow besides the push.
  */
 template <int W, int L, int D, int PK>
-__global__ __launch_bounds__(64, D > 4 ? 1 : (PK == 4 || PK == 5) ? GKM_BS_WAVES : GKM_BS_PACKED_WAVES) void k_gram_bitslice(const BsArgs A)
+__global__ __launch_bounds__(64, D > 4 ? 1 : (PK >= 4 && PK <= 7) ? GKM_BS_WAVES : GKM_BS_PACKED_WAVES) void k_gram_bitslice(const BsArgs A)
 {
     /* PK = 4: problems whose sequences all have the same length (gkmQC's own 600-bp subsets, BASELINE configs 1-3): a
      *         RESIDENT row takes k = ceil(windows / 310) lanes from bit row 0, piece pi of it starts at sequence position pi *
@@ -72,19 +63,25 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : (PK == 4 || PK == 5) ? GKM_BS_WAVES
      *         instructions.  The counting loop sees only other bits in planes it sweeps anyway; a trip whose bit row is 30
      *         takes row slot and position base from the source lane's RIDER TAG (an LDS table of 64 words, filled once per
      *         wave) instead of the origin word.  128 profile slots per tile; launches without riders take PK = 4;
+     *      6: PK = 4 with SHIFT RECORDS (gkm_bitslice.h shift_record_visit): the counting loop compacts the lanes once per
+     *         shift, not once per group of five words, and pushes three words -- both groups' ORs and the origin; a trip
+     *         takes the group from the record.  7: the same with riders (PK = 5).  What a same-length launch takes by
+     *         default; PK = 4 and 5 stay as the explicit "group records" kernel code, their bit-for-bit cross-check;
      *      1: everything else -- several pieces per lane (gkm_pack.h), up to 64 rows per tile; 2: up to 128 rows per tile.
      * (Rounds 2-5 also had one-piece variants for ragged lengths, PK = 0 / 3: piece entries in an LDS table / fetched by
      * ds_bpermute_b32, hits resolved one by one.  Once the group records below served ragged data through PK = 1 they were
      * left with L < 5 only, where the general kernel k_gram_direct now serves: git history has them.) */
     constexpr bool PACKED = PK == 1 || PK == 2;
-    constexpr bool UNIF = PK == 4 || PK == 5;
-    constexpr bool RIDERS = PK == 5;
-    static_assert(PACKED || UNIF, "PK = 4, 5, 1 or 2");
+    constexpr bool UNIF = PK >= 4 && PK <= 7;
+    constexpr bool RIDERS = PK == 5 || PK == 7;
+    constexpr bool SHIFTREC = PK == 6 || PK == 7;
+    static_assert(PACKED || UNIF, "PK = 4 .. 7, 1 or 2");
+    static_assert(!SHIFTREC || W == 2 * gkmbs::SHIFT_GROUP_WORDS, "a shift record holds the two groups of a shift");
     static_assert(L >= 5, "the L - 1 zero bytes either side of a weight table cover a group of five windows");
     using namespace gkmbs;
     /* LDS per wave.  STATIC, one array carved by hand:
      *   accl   [(D + 1) * NSLOT]     mismatch profiles [m][row slot]                              1-2.5 KB
-     *   s_list [2][CAP]              the hit list: two-word group records (below)                 1 KB
+     *   s_list [2 | 3][CAP]          the hit list: two-word group records (below) / three-word shift records   1 / 1.5 KB
      *   lpiece [64 * NP | 64 | 0]    piece entries of the several-pieces variants / the lanes' rider tags   0-1 KB
      * DYNAMIC: the column's two 2-bit packed strands, interleaved word by word (2 * pkw words: 0.2 KB at 300 bp, 0.3 KB
      * at 600 bp), then the weight tables: the column's weights by l-mer position (gkm_gram_bitslice.h POSTAB_PAD; ~T + L
@@ -105,19 +102,21 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : (PK == 4 || PK == 5) ? GKM_BS_WAVES
     static_assert(gkmpack::RIDER_SLOTS <= gkmpack::MAX_ROWS, "the riders' row slots have profiles");
     /* GROUP RECORDS: a record of the hit list is TWO words -- the OR of the five hit words of a group of words (which bit
      * rows of the lane hold a hit somewhere in the group) and the origin -- and a trip finds the hits among the five
-     * windows of (bit row, group) itself, from the packed strands it reads anyway (see `trip`). */
-    constexpr int LIST_ARRAYS = 2;
+     * windows of (bit row, group) itself, from the packed strands it reads anyway (see `trip`).  SHIFT RECORDS are three
+     * words: the ORs of both groups of a shift and the origin, which then holds no word index. */
+    constexpr int LIST_ARRAYS = SHIFTREC ? 3 : 2;
     constexpr int ACC_WORDS = (D + 1) * NSLOT, LIST_WORDS = LIST_ARRAYS * BS_CAP;
     /* per piece of the several-pieces variants: row slot | centre offset << 7 | owned windows << 20 */
     constexpr int LPIECE_WORDS = PACKED ? 64 * NP : RIDERS ? 64 : 0;
     constexpr int STATIC_WORDS = ACC_WORDS + LIST_WORDS + LPIECE_WORDS;
+    static_assert(!UNIF || STATIC_WORDS * 4 == bs_same_length_static_lds(PK, D), "gkm_gram_bitslice.h prices this LDS for the plan");
     __shared__ uint32_t s_mem[STATIC_WORDS];
     uint32_t *const accl = s_mem; /* mismatch profiles [m][row slot] */
     /* The hit list.  Word k of record i sits at s_list[k * BS_CAP + i]: k = 0 the OR of the lane's BS_GRP hit words for
      * BS_GRP consecutive words of a shift, k = 1 their origin (first word of the group, shift, row lane); the arrays are
      * a multiple of 64 dwords apart, so that the two stores of a push merge into one ds_write2st64_b32.  Compacting once
      * per group instead of once per word takes 3 VALU instructions per word out of the hot loop (config 2: 111.0 -> 96.2
-     * ms in round 1). */
+     * ms in round 1).  Shift records: k = 0, 1 the two groups' ORs, k = 2 the origin. */
     uint32_t *const s_list = s_mem + ACC_WORDS;
     uint32_t *const lpiece = s_list + LIST_WORDS;
     static_assert((ACC_WORDS * 4) % 256 == 0, "the list's arrays stay 64-dword aligned (ds_write2st64_b32)");
@@ -280,7 +279,11 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : (PK == 4 || PK == 5) ? GKM_BS_WAVES
          * packed positions, the column's strands interleaved word by word, (a & const) | b as one v_bitop3_b32, the strand
          * as wave-uniform scalars.  Same arithmetic as resolve_hit_packed (gkm_bitslice.h), which the CPU tests run
          * against the oracle. */
-        /* One trip over the `c` two-word records on top of the list (PARTIAL: c < BS_TRIP, the last trip of a strand).  A
+        /* One trip over the `c` records on top of the list.  SHIFT RECORDS (PK = 6, 7) differ from what follows in the head and
+         * the tail of a visit only: the record's three words say which bit rows of BOTH groups of one shift hold hits; the
+         * visit takes the lowest bit row of the first non-empty group (w0 = 0 or 5 comes from there, not from the origin
+         * word) and puts all three words back while either group has bit rows left.  Everything from i0 on is shared.
+         * Group records: one trip over the `c` two-word records on top of the list (PARTIAL: c < BS_TRIP, the last trip of a strand).  A
          * record says: some of the five windows (bit row b, words w0 .. w0+4) of source lane r are hits.  Lane positions i0 .. i0+4 (i0 = 10 b + w0) are five
          * CONSECUTIVE l-mers of the row against five consecutive l-mers q .. q+4 of the column strand, and the two 16-base
          * windows that the hit path fetches anyway -- one v_alignbit_b32 per side -- hold all of them (5 + L - 1 <= 16
@@ -312,10 +315,28 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : (PK == 4 || PK == 5) ? GKM_BS_WAVES
             asm("v_add_u32 %0, %1, %2" : "=v"(at_off) : "s"(top4), "v"(lane4));
             const char *const at = (const char *)s_list + at_off;
             uint32_t any = *(const uint32_t *)at;
-            const uint32_t ms = *(const uint32_t *)(at + BS_CAP * 4);
+            /* (shift records: `any` is the first group's OR, any1 the second's, the origin the third word) */
+            uint32_t any1 = SHIFTREC ? *(const uint32_t *)(at + BS_CAP * 4) : 0u;
+            const uint32_t ms = *(const uint32_t *)(at + (LIST_ARRAYS - 1) * BS_CAP * 4);
             if (PARTIAL) any = (lane < c) ? any : 0u;
-            const uint32_t bit = ffbl_or_ones(any);
-            const uint32_t rest = any & (any - 1u); /* the other bit rows of the group with a hit: back to the list */
+            if (PARTIAL && SHIFTREC) any1 = (lane < c) ? any1 : 0u;
+            /* the bit row visited and the first word of its group; what is left of the record goes back to the list: `rest`
+             * (group records), or (rest, any1) with `live` their OR (shift records) */
+            uint32_t bit, rw0, rest, live;
+            if constexpr (SHIFTREC) {
+                /* group = any0 ? 0 : 1, its lowest bit row, cleared in the record (gkm_bitslice.h shift_record_visit) */
+                rest = any;
+                any |= any1; /* (the partial trip's test below: does this lane hold a record at all?) */
+                const ShiftVisit sv = shift_record_visit(rest, any1);
+                bit = sv.bit;
+                rw0 = sv.w0;
+                live = rest | any1;
+            } else {
+                bit = lowest_bit_or_ones(any);
+                rest = any & (any - 1u); /* the other bit rows of the group with a hit: back to the list */
+                rw0 = ms & 15u;
+                live = rest;
+            }
             const uint32_t lane128 = ms & (63u << META_LANE_SHIFT);
             /* several pieces: the source lane's mask of piece-start bit rows, from that lane's register.  EVERY lane takes part
              * (ds_bpermute_b32 reads 0 from lanes that EXEC masks out, and in a partial trip the source lane of a live
@@ -327,7 +348,7 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : (PK == 4 || PK == 5) ? GKM_BS_WAVES
             uint32_t rtag = 0u;
             if (RIDERS) rtag = *(const uint32_t *)((const char *)lpiece + (lane128 >> 5));
             if (!PARTIAL || any) {
-                const uint32_t i0 = __umul24(bit, (uint32_t)W) + (ms & 15u);
+                const uint32_t i0 = __umul24(bit, (uint32_t)W) + rw0;
                 uint32_t slot4, ia, nv = 5u; /* row slot * 4; LDS address of the row l-mer's weight; owned windows from i0 on */
                 if (PACKED) {
                     /* the piece of the source lane that owns bit row `bit`; its entry = slot | centre offset << 7 | owned
@@ -396,14 +417,15 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : (PK == 4 || PK == 5) ? GKM_BS_WAVES
                 }
             }
             s_n -= c;
-            const unsigned long long more = __ballot(rest != 0u);
+            const unsigned long long more = __ballot(live != 0u);
             if (more) {
                 const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(more >> 32),
                                                                 __builtin_amdgcn_mbcnt_lo((uint32_t)more, 0u));
-                if (rest != 0u) {
+                if (live != 0u) {
                     char *const to = (char *)s_list + ((rank + (uint32_t)s_n) << 2);
                     *(uint32_t *)to = rest;
-                    *(uint32_t *)(to + BS_CAP * 4) = ms;
+                    if (SHIFTREC) *(uint32_t *)(to + BS_CAP * 4) = any1;
+                    *(uint32_t *)(to + (LIST_ARRAYS - 1) * BS_CAP * 4) = ms;
                 }
                 s_n += (int)__popcll(more);
             }
@@ -466,6 +488,25 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : (PK == 4 || PK == 5) ? GKM_BS_WAVES
                         uint32_t s_delta = pack_meta(d0 + u, 0, 0);
                         asm("" : "+s"(s_delta));
                         const uint32_t vbase = lane_tag | s_delta;
+                        if constexpr (SHIFTREC) {
+                            /* ONE compaction per shift: the lanes with a hit in either group append (any0, any1, origin) --
+                             * one ballot, one mbcnt pair, one address, three EXEC-masked words; the trip check once per
+                             * shift (a push adds at most 64 records: BS_CAP holds).  The origin carries no word index. */
+                            static_assert(W / BS_GRP == 2 && BS_GRP == gkmbs::SHIFT_GROUP_WORDS, "a shift record is two groups of five");
+                            const uint32_t any0 = grp_any[0], any1 = grp_any[1];
+                            const bool hit = shift_record_live(any0, any1);
+                            const unsigned long long mask = __ballot(hit);
+                            const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
+                                                                            __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+                            if (hit) {
+                                char *const at = (char *)s_list + (((uint32_t)rank + (uint32_t)s_n) << 2);
+                                *(uint32_t *)at = any0;
+                                *(uint32_t *)(at + BS_CAP * 4) = any1;
+                                *(uint32_t *)(at + 2 * BS_CAP * 4) = vbase;
+                            }
+                            s_n += (int)__popcll(mask);
+                            if (s_n >= BS_TRIP) trips(false);
+                        } else {
 #pragma unroll
                         for (int w0 = 0; w0 < W; w0 += BS_GRP) {
                             /* wave-level compaction at the source, once per group of BS_GRP words: the lanes with a hit in the
@@ -484,6 +525,7 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : (PK == 4 || PK == 5) ? GKM_BS_WAVES
                             }
                             s_n += (int)__popcll(mask);
                             if (s_n >= BS_TRIP) trips(false);
+                        }
                         }
                     }
                 }
@@ -525,7 +567,7 @@ static bs_kernel_t pick_bitslice(int L, int d)
 {
 #define GKM_BS(LL, DD) \
     if (L == LL && d == DD) { \
-        if constexpr (PACKED != 5 || LL - 1 <= gkmpack::RIDER_NB * W - gkmpack::RIDER_W) return k_gram_bitslice<W, LL, DD, PACKED>; \
+        if constexpr ((PACKED != 5 && PACKED != 7) || LL - 1 <= gkmpack::RIDER_NB * W - gkmpack::RIDER_W) return k_gram_bitslice<W, LL, DD, PACKED>; \
         else return nullptr; /* (no room for a rider piece's overlap: never launched) */ \
     }
     /* every (L, d) with 5 <= L <= 12, d <= 4 (bin/gkmqc.py:181-185 allows 3 <= L <= 12: L = 3 and 4 take k_gram_direct, the
@@ -546,6 +588,8 @@ bs_kernel_t gkm_pick_bitslice(int pk, int L, int d)
     case 2: return pick_bitslice<10, 2>(L, d);
     case 4: return pick_bitslice<10, 4>(L, d);
     case 5: return pick_bitslice<10, 5>(L, d);
+    case 6: return pick_bitslice<10, 6>(L, d);
+    case 7: return pick_bitslice<10, 7>(L, d);
     }
     return nullptr;
 }

@@ -19,6 +19,8 @@ LIB_DIR = os.path.join(HERE, "bin")
 LIB_NAME = "gkmkern_pylib.so"
 
 KERNEL_AUTO, KERNEL_DIRECT, KERNEL_BITSLICE = 0, 1, 2
+# the bit-sliced kernel with group records where a same-length launch takes shift records by default: the cross-check
+KERNEL_BITSLICE_GROUPS = 3
 
 
 class gkmOpt(ctypes.Structure):

@@ -38,7 +38,10 @@ extern "C" {
 
 typedef struct gkmhip_ctx gkmhip_ctx;
 
-enum { GKMHIP_KERNEL_AUTO = 0, GKMHIP_KERNEL_DIRECT = 1, GKMHIP_KERNEL_BITSLICE = 2 };
+/* (BITSLICE_GROUPS: the bit-sliced kernel with GROUP records -- one hit compaction per group of five words -- where a
+ * same-length launch would take shift records by default: the older variants, kept as the bit-for-bit cross-check of the
+ * newer ones, as DIRECT is of the bit-sliced kernel.  Everywhere else it is BITSLICE.) */
+enum { GKMHIP_KERNEL_AUTO = 0, GKMHIP_KERNEL_DIRECT = 1, GKMHIP_KERNEL_BITSLICE = 2, GKMHIP_KERNEL_BITSLICE_GROUPS = 3 };
 
 const char *gkmhip_last_error(void);
 int gkmhip_device_count(void);
@@ -58,7 +61,7 @@ void gkmhip_set_error_message(const char *msg); /* what gkmhip_last_error() retu
 
 /* choose the kernel family (default AUTO: the bit-sliced kernel where it is instantiated for (L, d) AND the faster one --
  * at most ~7.5 % of the window pairs within d mismatches for iid sequences --, the general kernel elsewhere;
- * BITSLICE fails where the kernel is not instantiated) */
+ * BITSLICE and BITSLICE_GROUPS fail where the kernel is not instantiated) */
 /* Per-launch scratch (row tables of one gkmhip_gram_rows* call) exists twice.  A caller that issues
  * consecutive launches on two different streams, so that one launch fills the CUs the previous one is
  * draining, selects slot 0 / 1 alternately; launches that share a slot must share a stream. */

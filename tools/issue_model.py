@@ -9,7 +9,7 @@ v_cndmask, SDWA / DPP forms, packed 16-bit operations, and any instruction with 
 VALU instruction with those two rates, and splits the kernel into the counting loop (everything outside the trips,
 per shift) and one trip (between the s_setprio that raises the wave's priority and the s_setprio 0 that ends it).
 
-    python3 tools/issue_model.py [--object gkmqc_amd/csrc/build/gkm_gram_bitslice.o] [--kernel 10,11,3,4] [--shifts-per-block 4]
+    python3 tools/issue_model.py [--object gkmqc_amd/csrc/build/gkm_gram_bitslice.o] [--kernel 10,11,3,7] [--shifts-per-block 4]
         [--waves N --T len --trips N --ms measured]
 
 With --waves/--T/--trips it predicts the kernel time as (shifts x counting cost + trips x trip cost) / (1024 SIMDs x
@@ -63,6 +63,24 @@ def disassemble(obj, kernel):
             addrs.append(int(m.group(1), 16) if m else -1)
     disassemble.addrs = addrs
     return sym, lines
+
+
+def resources(obj, kernel):
+    """What the code object's metadata says the instantiation takes: VGPRs, scratch bytes per lane, static LDS bytes."""
+    tmp = tempfile.mkdtemp()
+    elf, fat = os.path.join(tmp, "dev.elf"), os.path.join(tmp, "fatbin")
+    subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", obj, fat])
+    subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
+                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + elf], stderr=subprocess.DEVNULL)
+    sym = "_Z15k_gram_bitsliceILi%dELi%dELi%dELi%dEEv6BsArgs" % tuple(kernel)
+    notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", elf]).decode()
+    for block in notes.split("- .agpr_count:")[1:]:
+        if re.search(r"\.name:\s+%s\s" % re.escape(sym), block):
+            def field(name):
+                return int(re.search(r"\.%s:\s+(\d+)" % name, block).group(1))
+            return {"vgprs": field("vgpr_count"), "vgpr_spills": field("vgpr_spill_count"),
+                    "scratch_bytes": field("private_segment_fixed_size"), "static_lds_bytes": field("group_segment_fixed_size")}
+    raise KeyError(sym)
 
 
 def loops(lines, addrs):
@@ -136,6 +154,9 @@ def analyse(obj, kernel, du):
     rf, (rs, rh), rc = cost(rest)
     t_lds, t_vmem = sum(x.startswith("ds_") for x in trip), sum(x.startswith(("global_", "buffer_")) for x in trip)
     r_lds = sum(x.startswith("ds_") for x in rest) / nshift
+    # hit compactions of the counting loop: one v_mbcnt_lo / v_mbcnt_hi pair each -- two per shift with group records (PK = 4,
+    # 5, 1, 2: one per group of five words), one with shift records (PK = 6, 7)
+    r_comp = sum(x.startswith("v_mbcnt_lo") for x in rest) / nshift
     return {"symbol": sym, "instructions": len(lines), "trip_copies": len(copies),
             "trip": {"full_rate": tf, "sgpr_operand": ts, "half_rate": th, "cycles": tc, "lds": t_lds,
                      "vmem": t_vmem, "salu": sum(x.startswith("s_") for x in trip),
@@ -143,7 +164,7 @@ def analyse(obj, kernel, du):
             "per_shift": {"full_rate": rf / nshift, "sgpr_operand": rs / nshift, "half_rate": rh / nshift, "cycles": rc / nshift,
                           # (the counting loop's LDS instructions are the EXEC-masked pushes of a few lanes: their cost was not
                           # probed and is left out -- pricing them like a trip's full-wave operations over-counts)
-                          "lds": r_lds, "cycles_all": rc / nshift,
+                          "lds": r_lds, "compactions": r_comp, "cycles_all": rc / nshift,
                           "note": "the loop over blocks of %d shifts, trips taken out, / %d" % (nshift, nshift)}}
 
 
@@ -179,6 +200,7 @@ def main():
     ap.add_argument("--clock", type=float, default=2.37e9)
     ap.add_argument("--round", default=None, help="e.g. r3: combine with profiles/<round>_pmc_<workload>.json and "
                     "<round>_kernel_stats_<workload>.csv for c2, peaks, c5 and write profiles/<round>_issue_model.json")
+    ap.add_argument("--groups", action="store_true", help="with --round: the same-length launches took group records (PK = 4, 5)")
     a = ap.parse_args()
     if a.round:
         import csv
@@ -190,8 +212,10 @@ def main():
                "cycles_full_rate": C_FULL, "cycles_sgpr_operand": C_SGPR, "cycles_half_rate": C_HALF,
                "cycles_trip_valu": C_TRIP_VALU, "cycles_lds": C_LDS, "cycles_vmem": C_VMEM, "kernel_source_sha256": bench.kernel_source_hash(),
                "workloads": {}}
-        # (config 2 takes the same-length variant with riders, PK = 5; gkmQC's 600-bp shape has no room for them: PK = 4)
-        for wl, kern, T in (("c2", [10, 11, 3, 5], 300.0), ("peaks", [10, 10, 3, 4], 600.0), ("c5", [10, 12, 4, 1], None)):
+        # (config 2 takes the same-length variant with riders and shift records, PK = 7; gkmQC's 600-bp shape has no room for
+        # riders: PK = 6; --groups: the launches were made with the group-record kernel code, PK = 5 and 4)
+        same = ([10, 11, 3, 5], [10, 10, 3, 4]) if a.groups else ([10, 11, 3, 7], [10, 10, 3, 6])
+        for wl, kern, T in (("c2", same[0], 300.0), ("peaks", same[1], 600.0), ("c5", [10, 12, 4, 1], None)):
             pj = os.path.join(ROOT, "profiles", "%s_pmc_%s.json" % (a.round, wl))
             cs = os.path.join(ROOT, "profiles", "%s_kernel_stats_%s.csv" % (a.round, wl))
             if not (os.path.exists(pj) and os.path.exists(cs)):
@@ -227,8 +251,9 @@ def main():
     print("  %d instructions, %d trip copies" % (m["instructions"], m["trip_copies"]))
     print("  one trip:            %3d full-rate + %3d with an SGPR source + %3d half-rate VALU = %5.0f cycles (%d LDS, %d "
           "vector-memory, %d scalar ALU)" % (t["full_rate"], t["sgpr_operand"], t["half_rate"], t["cycles"], t["lds"], t["vmem"], t["salu"]))
-    print("  counting loop:       %.1f full-rate + %.1f with an SGPR source + %.1f half-rate VALU = %.1f cycles per shift (%s)"
-          % (r["full_rate"], r["sgpr_operand"], r["half_rate"], r["cycles"], r["note"]))
+    print("  counting loop:       %.1f full-rate + %.1f with an SGPR source + %.1f half-rate VALU = %.1f cycles per shift, %.1f hit "
+          "compactions and %.1f LDS instructions (%s)"
+          % (r["full_rate"], r["sgpr_operand"], r["half_rate"], r["cycles"], r["compactions"], r["lds"], r["note"]))
     if a.waves and a.T and a.trips is not None:
         shifts = a.waves * 2 * a.T
         cyc = shifts * r["cycles"] + a.trips * t["cycles"]
