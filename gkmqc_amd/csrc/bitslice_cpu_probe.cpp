@@ -450,6 +450,14 @@ extern "C" int packprobe_same_length(const int *rows, const int *nwin, int nrows
     return (int)P.pieces.size();
 }
 
+/* Tiles of the packing as plan_bitslice asks for it (W = 10, whole groups of five, no riders) with max_rows row slots per
+ * tile: the plan packs with 64 and with MAX_ROWS and takes the wider tiles where they are fewer
+ * (tests/test_same_length_plan_host.py) */
+extern "C" int packprobe_plan_tiles(const int *rows, const int *nwin, int nrows, int L, int max_rows)
+{
+    return gkmpack::pack_rows(rows, nwin, nrows, 10, L, max_rows, 0, 5, 0).ntiles;
+}
+
 /* One lane's image as k_build_rowplanes builds it from the lane's pieces (pieces[k][8] as above): planes_out[3][W] (hi, lo,
  * window ownership) and pk_out[2 W + 2], the 2-bit packed positions. */
 extern "C" void packprobe_lane_image(const uint8_t *codes, const int64_t *off, const int *pieces, int npieces, int W,

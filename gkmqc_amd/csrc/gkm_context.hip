@@ -630,3 +630,4 @@ extern "C" double gkmhip_last_kernel_ms(gkmhip_ctx *ctx)
 extern "C" double gkmhip_last_comparisons(gkmhip_ctx *ctx) { return ctx ? ctx->last_comparisons : 0.0; }
 extern "C" const char *gkmhip_last_kernel_name(gkmhip_ctx *ctx) { return ctx ? ctx->last_kernel : "none"; }
 extern "C" int gkmhip_last_riders(gkmhip_ctx *ctx) { return ctx ? ctx->last_riders : 0; }
+extern "C" int gkmhip_last_variant(gkmhip_ctx *ctx) { return ctx ? ctx->last_variant : 0; }

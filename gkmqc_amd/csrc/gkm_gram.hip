@@ -238,6 +238,7 @@ struct BitslicePlan {
     int s_slots = 64;                 /* ... of the tile-transposed output: slots, or gkmpack::RIDER_SLOTS with riders */
     bool packed = false, same_length = false, riders = false;
     bool shift_records = false;       /* same-length variants: one record per lane and shift (PK = 6, 7), not per group */
+    int variant = 0;                  /* k_gram_bitslice's PK of `kernel` (gkmhip_last_variant) */
     bs_kernel_t kernel = nullptr;
     const char *name = "";
     size_t dyn_lds = 0;
@@ -291,7 +292,6 @@ static int plan_bitslice(const gkmhip_ctx *ctx, const int *rows, int nrows, int 
      * several-pieces variants */
     bool packed = !unif || P.slots != 64;
     for (size_t k = 1; k < P.pk.pieces.size() && !packed; k++) packed = P.pk.pieces[k].lane == P.pk.pieces[k - 1].lane;
-    P.packed = packed;
     /* The same-length variants' contract with the packing -- the three statements of k_gram_bitslice's GROUP_VALID comment
      * for residents and rider pieces, and the lanes: one resident piece, a rider piece only above its last bit row
      * (gkm_pack.h same_length_packing_check; tests/test_rider_packing.py runs the same function).  The counting loop
@@ -305,6 +305,11 @@ static int plan_bitslice(const gkmhip_ctx *ctx, const int *rows, int nrows, int 
         for (size_t k = 0; k < pk.pieces.size(); k++) rw[k] = ctx->h_len[(size_t)pk.pieces[k].row] - L + 1;
         return gkmpack::same_length_packing_check(pk, rw.data(), own_mult, rider_w, max_slots);
     };
+    /* A row's LAST piece may own every window its bit rows hold, one to four more than the lane capacity of whole groups
+     * (L = 10, 320 bp: 311 windows in a lane of capacity 310), which the same-length variants do not allow: such a
+     * problem is served like ragged one-piece data, by the several-pieces variants, whose pieces carry their own count. */
+    if (!packed && layout_check(P.pk, 0, P.slots) != 0) packed = true;
+    P.packed = packed;
     /* RIDERS (gkm_pack.h RIDER_B0): where the residents of a same-length problem leave the lanes' top two bit rows empty,
      * further rows of the tile live there -- 66 rows per tile instead of 64 at 300 bp -- and the launch takes the rider
      * variant of the kernel, with 128 profile slots per tile.  Kept where whole rows fit as riders, the layout passes the
@@ -343,6 +348,7 @@ static int plan_bitslice(const gkmhip_ctx *ctx, const int *rows, int nrows, int 
         }
     }
     P.kernel = gkm_pick_bitslice(variant, L, d);
+    P.variant = variant;
     P.name = !packed ? "k_gram_bitslice<same length>" : slots == 64 ? "k_gram_bitslice<packed>" : "k_gram_bitslice<packed,128>";
     if (!P.kernel) return set_err_msg("bit-sliced kernel not instantiated for this (L, d)", 5);
     if (!packed && !P.riders) { /* (a layout with riders passed the check before it was taken) */
@@ -559,6 +565,7 @@ static int enqueue_bitslice(gkmhip_ctx *ctx, const BitslicePlan &P, int nrows, G
     }
     ctx->last_kernel = P.name;
     ctx->last_riders = P.riders ? pk.nriders : 0;
+    ctx->last_variant = P.variant;
     return 0;
 }
 
@@ -606,6 +613,7 @@ static int enqueue_direct(gkmhip_ctx *ctx, const int *rows, int nrows, int mode,
     HIPCHK(hipEventRecord(e1, stream));
     ctx->last_kernel = "k_gram_direct";
     ctx->last_riders = 0;
+    ctx->last_variant = 0;
     return 0;
 }
 

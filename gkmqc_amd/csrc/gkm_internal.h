@@ -158,6 +158,7 @@ struct gkmhip_ctx {
     double last_comparisons = 0;
     const char *last_kernel = "none";
     int last_riders = 0; /* rows the most recent Gram launch carried as riders (gkm_pack.h RIDER_B0) */
+    int last_variant = 0; /* k_gram_bitslice's PK of the most recent Gram launch (1, 2, 4, 5, 6, 7), 0: k_gram_direct */
     /* gkmhip_explain_block, gkmhip_ism_block, gkmhip_hyp_block: the row list of the call (upload_rows) and the partial
      * rows of its support-vector chunks.  One buffer each for all three: a call's kernels consume them in stream order
      * before the next call on that stream can overwrite them (growing one is a hipFree, which waits for the device). */

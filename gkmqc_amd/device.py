@@ -221,6 +221,9 @@ def load():
     if hasattr(L, "gkmhip_last_riders"):   # (older builds loaded through GKM_LIB_PATH for A/B timing lack it)
         L.gkmhip_last_riders.restype = i32
         L.gkmhip_last_riders.argtypes = (vp,)
+    if hasattr(L, "gkmhip_last_variant"):
+        L.gkmhip_last_variant.restype = i32
+        L.gkmhip_last_variant.argtypes = (vp,)
     _lib = L
     return L
 
@@ -588,6 +591,11 @@ class GramContext:
         """Rows the most recent Gram launch carried as riders (bit rows 30, 31 of the same-length variant's lanes), 0 if none."""
         return int(self.lib.gkmhip_last_riders(self.handle)) if hasattr(self.lib, "gkmhip_last_riders") else 0
 
+    def last_variant(self):
+        """k_gram_bitslice's variant (its PK) of the most recent Gram launch: 1, 2 several pieces per lane, 4 / 5 same length
+        with group records (5: riders), 6 / 7 the same with shift records; 0 for k_gram_direct."""
+        return int(self.lib.gkmhip_last_variant(self.handle)) if hasattr(self.lib, "gkmhip_last_variant") else 0
+
 
 def cross_kernel(seqs, rows, kernel_type, L, k, d, M=50, H=50.0, gamma=1.0, device=0, kernel=KERNEL_AUTO):
     """K(rows[i], j) for every sequence j (prediction-style rectangular kernel): torch fp64
@@ -608,7 +616,7 @@ def cross_kernel(seqs, rows, kernel_type, L, k, d, M=50, H=50.0, gamma=1.0, devi
             ctx.gram_rows_full(rows, G.data_ptr(), n, True, stream)
             ctx.normalize_rows_full(rows, G.data_ptr(), n, sq.data_ptr(), True, stream)
             torch.cuda.synchronize(dev)
-            return dict(K=G, sqnorm=sq, rows=rows, kernel=ctx.last_kernel_name())
+            return dict(K=G, sqnorm=sq, rows=rows, kernel=ctx.last_kernel_name(), variant=ctx.last_variant())
     finally:
         ctx.close()
 
@@ -730,7 +738,8 @@ def gram_matrix(seqs, kernel_type, L, k, d, M=50, H=50.0, gamma=1.0, device=0, w
     """Whole Gram matrix of `seqs` on one GPU (device memory through torch).
 
     Returns dict(K=torch fp64 [n,n] (lower triangle + unit diagonal; upper too if symmetric),
-    P=int32 [n,n,d+1] or None, sqnorm=[n], kernel=name, ms=device ms of the gram kernel).
+    P=int32 [n,n,d+1] or None, sqnorm=[n], kernel=name, riders / variant=GramContext.last_riders() / last_variant() of
+    the launch, ms=device ms of the gram kernel).
     keep_context: use (and keep) the cached context of these parameters, see cached_context().
     wait=False (with keep_context): return as soon as the work is enqueued on torch's current stream -- whatever the
     caller enqueues on that stream next is ordered behind it, and the host is free meanwhile (gkmsvm.init draws the
@@ -749,11 +758,11 @@ def gram_matrix(seqs, kernel_type, L, k, d, M=50, H=50.0, gamma=1.0, device=0, w
             P = torch.zeros((n, n, d + 1), dtype=torch.int32, device=dev) if want_profiles else None
             sq = torch.zeros(n, dtype=torch.float64, device=dev)
             ctx.gram_rows(np.arange(n), G.data_ptr(), n, P.data_ptr() if want_profiles else None, n, False, stream)
-            riders = ctx.last_riders()
+            riders, variant = ctx.last_riders(), ctx.last_variant()
             ctx.normalize(G.data_ptr(), n, sq.data_ptr(), symmetric, stream)
             if not (keep_context and not wait):
                 torch.cuda.current_stream().synchronize()   # (this stream only: others may carry unrelated work)
-            return dict(K=G, P=P, sqnorm=sq, kernel=ctx.last_kernel_name(), riders=riders,
+            return dict(K=G, P=P, sqnorm=sq, kernel=ctx.last_kernel_name(), riders=riders, variant=variant,
                         ms=ctx.last_kernel_ms() if (wait or not keep_context) else None,
                         comparisons=ctx.last_comparisons())
     finally:

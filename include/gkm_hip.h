@@ -456,6 +456,10 @@ const char *gkmhip_last_kernel_name(gkmhip_ctx *ctx);
 /* rows that the most recent Gram launch carried as RIDERS -- in bit rows 30, 31 of lanes whose own row ends below them
  * (same-length problems) -- 0 if it packed without them or another kernel served it */
 int gkmhip_last_riders(gkmhip_ctx *ctx);
+/* which k_gram_bitslice variant the most recent Gram launch ran -- the kernel's PK: 1, 2 several pieces per lane (64, 128
+ * row slots), 4 same length with group records, 5 the same with riders, 6 and 7 those two with shift records (DESIGN.md
+ * section 5) -- or 0 where k_gram_direct served it.  The kernel's name is the same for 4 to 7. */
+int gkmhip_last_variant(gkmhip_ctx *ctx);
 
 #ifdef __cplusplus
 }

@@ -27,9 +27,10 @@ def dev(built):
 _ORACLE = {}
 
 
-def _oracle(seqs, key, t, L, k, d, rows=None):
+def _oracle(seqs, key, t, L, k, d, rows=None, threads=1):
     """Profiles, raw values (sum_m c_m P_m in ascending m from 0.0, libgkm.c:576-582) and K = G / (sq_a sq_j) of the lower
-    triangle (of the given rows only: K then stays unset), computed once per (sequences, parameters) and shared."""
+    triangle (of the given rows only: K then stays unset), computed once per (sequences, parameters) and shared.
+    threads > 1: that many rows at a time."""
     if (key, t, L, k, d) in _ORACLE:
         return _ORACLE[(key, t, L, k, d)]
     from oracle import oracle as O
@@ -37,13 +38,24 @@ def _oracle(seqs, key, t, L, k, d, rows=None):
     opt = O.make_opt(t, L, k, d)
     c = O.mismatch_weights(t, L, k)[: d + 1]
     P = np.zeros((n, n, d + 1), dtype=np.int32)
-    prof = np.zeros(d + 1, dtype=np.int32)
     vp = ctypes.c_void_p
-    for a in (range(n) if rows is None else rows):
+    lib = O.lib()
+
+    def one_row(a):
+        prof = np.zeros(d + 1, dtype=np.int32)
         for j in range(a + 1):
-            O.lib().gkmo_profile(ctypes.byref(opt), seqs[a].ctypes.data_as(vp), len(seqs[a]), seqs[j].ctypes.data_as(vp),
-                                 len(seqs[j]), prof.ctypes.data_as(vp))
+            lib.gkmo_profile(ctypes.byref(opt), seqs[a].ctypes.data_as(vp), len(seqs[a]), seqs[j].ctypes.data_as(vp),
+                             len(seqs[j]), prof.ctypes.data_as(vp))
             P[a, j] = prof
+
+    todo = list(range(n) if rows is None else rows)
+    if threads > 1:      # (gkmo_profile keeps no state between calls, and the call releases the interpreter lock)
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(threads) as pool:
+            list(pool.map(one_row, todo[::-1]))
+    else:
+        for a in todo:
+            one_row(a)
     G = np.zeros((n, n))
     for m in range(d + 1):
         G += c[m] * P[:, :, m].astype(np.float64)

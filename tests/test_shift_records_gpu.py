@@ -30,9 +30,10 @@ def dev(built):
     return device
 
 
-def _launch(dev, seqs, params, kernel, block=None):
-    """One Gram launch with the given kernel code -> (profiles or None, raw values, riders, kernel name).  block = (rows,
-    c0, c1): the column-range launch, raw values [len(rows), c1 - c0] and no profiles."""
+def _launch(dev, seqs, params, kernel, block=None, want_k=False):
+    """One Gram launch with the given kernel code -> (profiles or None, raw values, riders, kernel name, variant: the
+    kernel's PK, 0 for the general kernel).  block = (rows, c0, c1): the column-range launch, raw values [len(rows),
+    c1 - c0] and no profiles.  want_k (triangle only): a sixth value, the normalised matrix of the raw values."""
     import torch
     t, L, k, d = params
     n = len(seqs)
@@ -46,12 +47,18 @@ def _launch(dev, seqs, params, kernel, block=None):
             G = torch.full((len(rows), c1 - c0), -7.25, dtype=torch.float64, device="cuda")
             ctx.gram_block(rows, c0, c1, G.data_ptr(), c1 - c0, stream)
             torch.cuda.synchronize()
-            return None, G.cpu().numpy(), ctx.last_riders(), ctx.last_kernel_name()
+            return None, G.cpu().numpy(), ctx.last_riders(), ctx.last_kernel_name(), ctx.last_variant()
         G = torch.zeros((n, n), dtype=torch.float64, device="cuda")
         P = torch.zeros((n, n, d + 1), dtype=torch.int32, device="cuda")
         ctx.gram_rows(np.arange(n), G.data_ptr(), n, P.data_ptr(), n, False, stream)
         torch.cuda.synchronize()
-        return P.cpu().numpy(), G.cpu().numpy(), ctx.last_riders(), ctx.last_kernel_name()
+        out = (P.cpu().numpy(), G.cpu().numpy(), ctx.last_riders(), ctx.last_kernel_name(), ctx.last_variant())
+        if want_k:
+            sq = torch.zeros(n, dtype=torch.float64, device="cuda")
+            ctx.normalize(G.data_ptr(), n, sq.data_ptr(), False, stream)
+            torch.cuda.synchronize()
+            out += (G.cpu().numpy(),)
+        return out
     finally:
         ctx.close()
 
@@ -61,9 +68,10 @@ def _check(dev, seqs, key, params, riders, name=NAME):
     P, G, _ = _oracle(seqs, key, *params)
     n = len(seqs)
     il = np.tril_indices(n)
-    Ps, Gs, rs, name_s = _launch(dev, seqs, params, dev.KERNEL_BITSLICE)
-    Pg, Gg, rg, name_g = _launch(dev, seqs, params, dev.KERNEL_BITSLICE_GROUPS)
+    Ps, Gs, rs, name_s, pk_s = _launch(dev, seqs, params, dev.KERNEL_BITSLICE)
+    Pg, Gg, rg, name_g, pk_g = _launch(dev, seqs, params, dev.KERNEL_BITSLICE_GROUPS)
     assert name_s == name and name_g == name
+    assert (pk_s, pk_g) == ((1, 1) if name != NAME else (7, 5) if riders else (6, 4))
     assert (rs > 0) == riders and rs == rg
     assert (Ps[il] == P[il]).all() and (Gs[il] == G[il]).all() and (np.triu(Gs, 1) == 0).all()
     assert (Pg[il] == P[il]).all() and (Gg[il] == G[il]).all()
@@ -125,7 +133,7 @@ def test_dense_hits_through_the_column_range_launch(dev, t, L, k, d):
     P, G, _ = _oracle(seqs, ("dense300", L), t, L, k, d)
     full = np.tril(G) + np.tril(G, -1).T
     for rows, c0, c1, riders in ((np.arange(70, dtype=np.int32), 3, 70, True), (np.arange(5, 31, dtype=np.int32), 0, 41, False)):
-        _, Bs, rs, name = _launch(dev, seqs, (t, L, k, d), dev.KERNEL_BITSLICE, (rows, c0, c1))
-        _, Bg, rg, _ = _launch(dev, seqs, (t, L, k, d), dev.KERNEL_BITSLICE_GROUPS, (rows, c0, c1))
-        assert name == NAME and (rs > 0) == riders and rs == rg
+        _, Bs, rs, name, pk_s = _launch(dev, seqs, (t, L, k, d), dev.KERNEL_BITSLICE, (rows, c0, c1))
+        _, Bg, rg, _, pk_g = _launch(dev, seqs, (t, L, k, d), dev.KERNEL_BITSLICE_GROUPS, (rows, c0, c1))
+        assert name == NAME and (rs > 0) == riders and rs == rg and (pk_s, pk_g) == ((7, 5) if riders else (6, 4))
         assert np.array_equal(Bs, full[rows][:, c0:c1]) and np.array_equal(Bs, Bg)

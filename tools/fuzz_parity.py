@@ -13,7 +13,28 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-BITSLICED = [(L, d) for L in range(5, 13) for d in range(0, 5)]   # all have a bit-sliced kernel
+from tests.helpers import ALL_LD as BITSLICED   # noqa: E402  every (L, d) with a bit-sliced kernel
+
+
+def band(L, lanes):
+    """(lo, hi): the lengths at which rows of one length take `lanes` lanes each, one resident piece per lane, and share
+    none -- where a same-length problem runs the one-piece-per-lane variants.  lanes - 1 full lanes
+    of `cap` windows, and a last piece that owns at most `cap` and leaves too few bit rows for the next row to start
+    in (its first piece would own fewer than 30 windows).  tests/test_same_length_plan_host.py holds this against the
+    packing for every length and L."""
+    cap = (320 - (L - 1)) // 5 * 5
+    spare = 1
+    while (spare * 10 - (L - 1)) // 5 * 5 < 30:
+        spare += 1
+    return (lanes - 1) * cap + (32 - spare) * 10 + 1, lanes * cap + L - 1
+
+
+def band_length(rng, L):
+    """A fixed length at which rows of l-mer length L keep one resident piece per lane: one lane half of the time -- with riders up
+    to 300 bp -- two to six lanes otherwise, the band's edges and the first length outside it now and then."""
+    lanes = 1 if rng.random() < 0.5 else int(rng.integers(2, 7))
+    lo, hi = band(L, lanes)
+    return int(rng.choice([int(rng.integers(lo, hi + 1)), int(rng.integers(lo, hi + 1)), lo, hi, lo - 1, hi + 1, 300]))
 
 
 def main():
@@ -44,12 +65,17 @@ def main():
             continue
         M, H = int(rng.integers(1, 256)), float(rng.integers(1, 200))
         gamma = float(rng.choice([0.5, 1.0, 2.0]))
-        n = int(rng.integers(2, 90))
         mode = int(rng.choice([0, 0, 5, 5, 5, 1, 2, 3, 4]))
+        n = int(rng.integers(2, 90))
         if mode == 0:
             lens = np.full(n, int(rng.integers(L, 700)))
-        elif mode == 5:   # fixed lengths that fill one lane piece each: the one-piece-per-lane kernel variant
-            lens = np.full(n, int(rng.choice([int(rng.integers(170, 321)), int(rng.integers(500, 641)), 300, 600])))
+        elif mode == 5:   # fixed lengths inside (or just outside) a band: the one-piece-per-lane kernel variants
+            length = min(band_length(rng, L), 2047)
+            if length <= 320 and rng.random() < 0.3:
+                n = int(rng.integers(130, 200))     # more than one tile with riders
+            elif length > 700:
+                n = int(rng.integers(2, 40))        # (the oracle's time)
+            lens = np.full(n, max(length, L))
         elif mode == 1:
             lens = rng.integers(L, 700, n)
         elif mode == 2:
@@ -69,14 +95,17 @@ def main():
         opt = O.make_opt(t, L, k, d, M, H, gamma, pf, nf)
         ref = O.gram(opt, want_profiles=True, nthreads=16)
         codes = [device.encode(s) for s in seqs]
-        for kern in (device.KERNEL_AUTO, device.KERNEL_DIRECT):
+        kerns = [device.KERNEL_AUTO, device.KERNEL_DIRECT]
+        if (L, d) in BITSLICED:   # whatever `auto` makes of the pair: both record kinds of the bit-sliced kernel
+            kerns += [device.KERNEL_BITSLICE, device.KERNEL_BITSLICE_GROUPS]
+        for kern in kerns:
             res = device.gram_matrix(codes, t, L, k, d, M, H, gamma, want_profiles=True, kernel=kern)
             K = res["K"].cpu().numpy()
             P = res["P"].cpu().numpy()
             il = np.tril_indices(n)
             if not (P[il] == ref["P"][il]).all():
-                raise SystemExit("PROFILE MISMATCH t=%d L=%d k=%d d=%d n=%d mode=%d kernel=%s seed=%d case=%d" %
-                                 (t, L, k, d, n, mode, res["kernel"], a.seed, cases))
+                raise SystemExit("PROFILE MISMATCH t=%d L=%d k=%d d=%d n=%d mode=%d kernel=%s PK %d seed=%d case=%d" %
+                                 (t, L, k, d, n, mode, res["kernel"], res["variant"], a.seed, cases))
             # (a poly-A row with large weights wraps its int32 self profile -- like the reference -- and
             #  its square root is NaN on both sides: NaNs must coincide, the rest must agree)
             kd, kr = K[il], ref["K"][il]
@@ -86,7 +115,8 @@ def main():
             tol = 1e-9 if t in (3, 5) else 1e-12
             if not (same_nan and err < tol):
                 raise SystemExit("K MISMATCH %g t=%d L=%d k=%d d=%d n=%d mode=%d kernel=%s" % (err, t, L, k, d, n, mode, res["kernel"]))
-            kernels[res["kernel"]] = kernels.get(res["kernel"], 0) + 1
+            used = "%s PK %d" % (res["kernel"], res["variant"])
+            kernels[used] = kernels.get(used, 0) + 1
         cases += 1
         if cases % 50 == 0:
             print("%d cases ok %s" % (cases, kernels), flush=True)
