@@ -14,8 +14,9 @@
  *                          complement, mismatch mask and count, the coefficient block a table kernel takes by value
  *   gkm_explain.hip        per-base importance of a trained model (k_explain, k_explain_reduce), gkmhip_explain_block
  *   gkm_ism.hip            in-silico mutagenesis of a trained model (k_ism, k_ism_reduce, k_ism_self_base, k_ism_self),
- *                          gkmhip_ism_self_profiles; hypothetical importance (k_ism<true>, k_ism_hyp_reduce);
- *                          gkmhip_ism_block and gkmhip_hyp_block, both through ism_launch<HYP>
+ *                          gkmhip_ism_self_profiles; hypothetical importance (k_ism<ISM_HYP>, k_ism_hyp_reduce); every
+ *                          mutant's score for RBF models (k_ism<ISM_RBF>); gkmhip_ism_block, gkmhip_hyp_block and
+ *                          gkmhip_ism_rbf_block, all through ism_launch<MODE>
  *   gkm_lmer.hip           l-mer weight tables of a trained model and scores from them (k_lmer_weights, k_lmer_score),
  *                          gkmhip_lmer_weights, gkmhip_lmer_score
  *   gkm_limp.hip           per-base importance tables of a trained model and explanations from them (k_lmer_importance,
@@ -164,7 +165,8 @@ struct gkmhip_ctx {
      * before the next call on that stream can overwrite them (growing one is a hipFree, which waits for the device). */
     DevBuf<int> blk_rows;
     DevBuf<double> blk_part;
-    /* gkmhip_ism_block: the per-tile G of its chunks; gkmhip_ism_self_profiles: the queries' own profiles P_m(x, x) */
+    /* gkmhip_ism_block, gkmhip_ism_rbf_block: the per-tile G (RBF: the query's own decision sum) of its chunks;
+     * gkmhip_ism_self_profiles: the queries' own profiles P_m(x, x) */
     DevBuf<double> ism_gpart;
     DevBuf<int64_t> ism_pself;
     /* gkmhip_delta_variants: the alternate bases of the call (its variant table goes through upload_rows) */

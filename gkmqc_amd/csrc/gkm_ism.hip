@@ -1,7 +1,9 @@
 /*
  * gkm_ism.hip -- in-silico mutagenesis of a trained gkm-SVM: for every query x of a column range, every
  * position t and every base b, the change of the raw kernel values sum_s coef_s G(y, s) when y = x with base t set to b,
- * and the mismatch profiles P_m(y, y) of every such mutant against itself.
+ * and the mismatch profiles P_m(y, y) of every such mutant against itself.  The change dG_s(t, b) of ONE support vector is
+ * complete, as exact integer tallies in LDS, before it is folded; what a model does with it is the fold's business: a
+ * linear model multiplies by a coefficient and adds, an RBF model normalises, exponentiates and adds.
  *
  *   A substitution at t changes only the query l-mers that cover it.  Take every pair (query l-mer u at p, forward or
  *   reverse-complement l-mer v of s) with m <= min(d + 1, L) mismatches and weight w = w_x[p] w_s[q]:
@@ -22,9 +24,14 @@
  *                    list order; one partial row per chunk
  *   k_ism_reduce     the partial rows summed in chunk order into the (T, 4) output (0.0 at the query's own base), and
  *                    base(x) = sum_s coef_s G(x, s) summed over tiles and chunks in order
- *   k_ism<true>      (k_ism is k_ism<false>) the same enumeration, tallies, chunking and tiling with the hypothetical
- *                    fold: 4 doubles per base, no profile
- *   k_ism_hyp_reduce k_ism<true>'s partial rows summed in chunk order into the (T, 4) output, the query's own base included
+ *   k_ism<ISM_HYP>   (k_ism is k_ism<ISM_LIN>; reported as k_ism<true>) the same enumeration, tallies, chunking and
+ *                    tiling with the hypothetical fold: 4 doubles per base, no profile
+ *   k_ism_hyp_reduce k_ism<ISM_HYP>'s partial rows summed in chunk order into the (T, 4) output, the query's own base
+ *                    included
+ *   k_ism<ISM_RBF>   (reported as k_ism_rbf) the same enumeration, tallies, chunking and tiling with the RBF fold of
+ *                    no profile; the raw G(x, s) arrives from a Gram launch, and each support vector adds
+ *                    dual_s exp(gamma (G(y, s) / (sq_s sqrt(G(y, y))) - 1)) per mutant instead of coef_s dG_s; its partial
+ *                    rows and per-tile base go through k_ism_reduce
  *   k_ism_self_base  P_m(x, x), exact uint64 (alone: gkmhip_self_profiles, the exact norms of the interpretation paths)
  *   k_ism_self       P_m(y, y) of the three mutants at one position: P_m(x, x) plus the exact change of every pair in
  *                    which a changed l-mer takes part (about 4 L T comparisons per mutant)
@@ -35,6 +42,10 @@
 #include "gkm_lmer_dev.h"
 
 namespace {
+
+/* what k_ism does with a support vector's tallies: the linear fold of in-silico mutagenesis, the hypothetical fold, or the
+ * RBF fold */
+enum { ISM_LIN = 0, ISM_HYP = 1, ISM_RBF = 2 };
 
 constexpr int ISM_THREADS = 256;
 constexpr int ISM_R = 8;        /* query l-mers per thread: 256 x 8 = 2 048 >= the l-mers of any tile */
@@ -76,16 +87,23 @@ struct IsmArgs {
     double *part;              /* [chunk][3 x bases of the range] (hypothetical mode: 4 x bases) */
     int64_t part_stride;
     double *gpart;             /* [chunk][query][tile] */
+    /* the RBF fold only (there coef holds the dual coefficients, not divided by the norms) */
+    const double *sq;          /* [n]: sqrt(G(i, i)) per uploaded sequence */
+    const double *gx;          /* [nrows][ldg]: raw G(x_j, rows[i]) at column j - col_begin */
+    int64_t ldg;
+    const double *ysq;         /* 4 per base of the range: sqrt(G(y, y)) */
+    const uint8_t *codes;
+    double gamma;
 };
 
 /* A pair (query l-mer at tile position pt, i.e. query position t0 + pt; support-vector l-mer v) with m <= mb mismatches
  * (mm: one bit 2j per mismatched base, j = L - 1 - i for base i of the l-mer).  Base i sits at tile position pt + i.
- * HYP: the hypothetical mode, which keeps no profile. */
-template <bool HYP>
+ * Only the linear mode keeps a profile. */
+template <int MODE>
 __device__ __forceinline__ void ism_hit(uint32_t *U, uint32_t *B, unsigned long long *P, int stride, int tlen, int d,
                                         int L, int m, int pt, uint32_t mm, uint32_t u, uint32_t v, uint32_t w)
 {
-    if constexpr (!HYP) {
+    if constexpr (MODE == ISM_LIN) {
         if (m <= d && pt >= 0) atomicAdd(P + m, (unsigned long long)w); /* (the l-mers of the tile's own positions only) */
     }
     const int top = pt + L - 1;
@@ -120,7 +138,7 @@ __device__ __forceinline__ int ism_push(uint32_t *Q, int qn, bool hit, uint32_t 
     return qn + __popcll(bal);
 }
 
-template <bool HYP>
+template <int MODE>
 __device__ __forceinline__ void ism_flush(const uint32_t *Q, int qn, int lane, uint32_t *U, uint32_t *B,
                                           unsigned long long *P, int stride, int tlen, int d, int L)
 {
@@ -129,17 +147,19 @@ __device__ __forceinline__ void ism_flush(const uint32_t *Q, int qn, int lane, u
         const uint32_t a = Q[ISM_QWORDS * k], v = Q[ISM_QWORDS * k + 1], c = Q[ISM_QWORDS * k + 2];
         const uint32_t u = a & LMER_CODE;
         /* (the mask is symmetric; with v first the compiler keeps the operand order it has always given the fold) */
-        ism_hit<HYP>(U, B, P, stride, tlen, d, L, (int)(a >> 24), (int)(c & 0xFFFFu) - 16, lmer_mask(v, u), u, v, c >> 16);
+        ism_hit<MODE>(U, B, P, stride, tlen, d, L, (int)(a >> 24), (int)(c & 0xFFFFu) - 16, lmer_mask(v, u), u, v, c >> 16);
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
 }
 
-/* HYP = false: in-silico mutagenesis; HYP = true: the hypothetical mode, part rows [slot 0, slot 1, slot 2, own] per base
- * (slot s: the mutant to base (x[t] + 1 + s) mod 4).  The two differ in the fold and what they write only */
-template <bool HYP>
+/* ISM_LIN: in-silico mutagenesis; ISM_HYP: the hypothetical mode, part rows [slot 0, slot 1, slot 2, own] per base
+ * (slot s: the mutant to base (x[t] + 1 + s) mod 4); ISM_RBF: every mutant's RBF decision sum, part rows as ISM_LIN's.
+ * They differ in the fold and what they write only */
+template <int MODE>
 __global__ __launch_bounds__(ISM_THREADS) void k_ism(const IsmArgs A)
 {
     extern __shared__ unsigned long long lds[];
+    constexpr bool HYP = MODE == ISM_HYP;
     constexpr int W = HYP ? 4 : 3; /* doubles per base of a partial row */
     unsigned long long *P = lds;                     /* [d + 1] */
     uint32_t *U = (uint32_t *)(lds + GKM_MAXD1);     /* [d + 1][stride] */
@@ -179,6 +199,19 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism(const IsmArgs A)
         if constexpr (HYP) acc[k][3] = 0.0;
     }
     double gacc = 0.0;
+    /* RBF: the norms of this thread's 3 x ISM_OWN mutants, slot s being base (x[t] + 1 + s) mod 4, stay in registers */
+    double yn[MODE == ISM_RBF ? ISM_OWN : 1][3];
+    if constexpr (MODE == ISM_RBF) {
+        const uint8_t *x = A.codes + A.off[j] + t0;
+        const double *yq = A.ysq + 4 * (A.off[j] - A.off[A.col_begin] + t0);
+#pragma unroll
+        for (int k = 0; k < ISM_OWN; k++) {
+            const int tl = k * ISM_THREADS + tid;
+            const int xb = tl < tlen ? x[tl] & 3 : 0;
+#pragma unroll
+            for (int s = 0; s < 3; s++) yn[k][s] = tl < tlen ? yq[4 * tl + ((xb + 1 + s) & 3)] : 1.0;
+        }
+    }
     for (int e = tid; e < (d + 1 + 3 * mb) * stride; e += ISM_THREADS) U[e] = 0u;
     if (tid <= d) P[tid] = 0ull;
     __syncthreads();
@@ -207,25 +240,31 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism(const IsmArgs A)
                     qn = ism_push(Q, qn, mf <= lim[r], u[r] | ((uint32_t)mf << 24), xf[t] & LMER_CODE,
                                   ptw | (wu[r] * (xf[t] >> LMER_WSHIFT)) << 16);
                     if (qn >= 64) {
-                        ism_flush<HYP>(Q, qn, lane, U, B, P, stride, tlen, d, L);
+                        ism_flush<MODE>(Q, qn, lane, U, B, P, stride, tlen, d, L);
                         qn = 0;
                     }
                     qn = ism_push(Q, qn, mr <= lim[r], u[r] | ((uint32_t)mr << 24), xr[t] & LMER_CODE,
                                   ptw | (wu[r] * (xr[t] >> LMER_WSHIFT)) << 16);
                     if (qn >= 64) {
-                        ism_flush<HYP>(Q, qn, lane, U, B, P, stride, tlen, d, L);
+                        ism_flush<MODE>(Q, qn, lane, U, B, P, stride, tlen, d, L);
                         qn = 0;
                     }
                 }
             }
         }
-        if (qn) ism_flush<HYP>(Q, qn, lane, U, B, P, stride, tlen, d, L);
+        if (qn) ism_flush<MODE>(Q, qn, lane, U, B, P, stride, tlen, d, L);
         __syncthreads();
         /* fold in ascending m: a(t, b) = sum_m fu[m] U[m][t] + fb[m] B[m][t][b], then acc += coef_s a; each thread clears
          * what it has read, so the next support vector starts from zero after one barrier.  Hypothetical mode (fu[m] =
          * share[m], fb[m - 1] = share[m - 1]): the own column takes the U rows only, each mutant column its B rows only,
-         * in k_explain's expression shape */
+         * in k_explain's expression shape.  RBF mode: a is dG_s(t, b) as the linear mode forms it, and acc += dual_s
+         * exp(gamma ((G(x, s) + a) / (sq_s sqrt(G(y, y))) - 1)), k_normalize_full's expression shape */
         const double cs = A.coef[i];
+        double sqs = 0.0, gxs = 0.0;
+        if constexpr (MODE == ISM_RBF) {
+            sqs = A.sq[s];
+            gxs = A.gx[(int64_t)i * A.ldg + jl];
+        }
 #pragma unroll
         for (int k = 0; k < ISM_OWN; k++) {
             const int tl = k * ISM_THREADS + tid;
@@ -268,12 +307,22 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism(const IsmArgs A)
                         b[0] = b[stride] = b[2 * stride] = 0u;
                     }
                 }
-                acc[k][0] += cs * a0;
-                acc[k][1] += cs * a1;
-                acc[k][2] += cs * a2;
+                if constexpr (MODE == ISM_RBF) {
+                    acc[k][0] += cs * exp(A.gamma * ((gxs + a0) / (sqs * yn[k][0]) - 1));
+                    acc[k][1] += cs * exp(A.gamma * ((gxs + a1) / (sqs * yn[k][1]) - 1));
+                    acc[k][2] += cs * exp(A.gamma * ((gxs + a2) / (sqs * yn[k][2]) - 1));
+                } else {
+                    acc[k][0] += cs * a0;
+                    acc[k][1] += cs * a1;
+                    acc[k][2] += cs * a2;
+                }
             }
         }
-        if constexpr (!HYP) {
+        if constexpr (MODE == ISM_RBF) {
+            /* score(x)'s sum, once per query: the first tile keeps it, the others add 0.0 in k_ism_reduce */
+            if (tid == 0 && z == 0) gacc += cs * exp(A.gamma * (gxs / (sqs * A.sq[j]) - 1));
+        }
+        if constexpr (MODE == ISM_LIN) {
             if (tid == 0) {
                 double g = 0.0;
                 for (int m = 0; m <= d; m++) {
@@ -453,15 +502,22 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_self(const int *__restrict_
     }
 }
 
-/* gkmhip_ism_block (HYP = false) and gkmhip_hyp_block (HYP = true) behind their argument checks and fold coefficients
- * (A.fu, A.fb, A.gc): k_ism<HYP> over (rows) x [col_begin, col_end), then its reduce kernel.  3 (ism) or 4 (hypothetical)
- * partial doubles per base; only ism keeps the per-tile G and returns base. */
-template <bool HYP>
+/* gkmhip_ism_block (ISM_LIN), gkmhip_hyp_block (ISM_HYP) and gkmhip_ism_rbf_block (ISM_RBF) behind their argument checks,
+ * fold coefficients (A.fu, A.fb, A.gc) and, for ISM_RBF, A.sq, A.gx, A.ldg and A.ysq: k_ism<MODE> over (rows) x [col_begin,
+ * col_end), then its reduce kernel.  4 (hypothetical) or 3 partial doubles per base; the other two keep a per-tile value
+ * per query and return base. */
+template <int MODE>
 int ism_launch(gkmhip_ctx *ctx, IsmArgs &A, const int *rows, int nrows, int col_begin, int col_end, const double *coef,
                double *out, double *base, hipStream_t stream)
 {
+    constexpr bool HYP = MODE == ISM_HYP;
     constexpr int per = HYP ? 4 : 3;
-    if (int rc = check_range(ctx, col_begin, col_end, HYP ? "gkmhip_hyp_block" : "gkmhip_ism_block")) return rc;
+    constexpr const char *entry[] = {"gkmhip_ism_block", "gkmhip_hyp_block", "gkmhip_ism_rbf_block"};
+    constexpr const char *kernel[] = {"k_ism", "k_ism<true>", "k_ism_rbf"};
+    constexpr const char *what[] = {"ism", "hypothetical", "ism (RBF fold)"};
+    if (int rc = check_range(ctx, col_begin, col_end, entry[MODE])) return rc;
+    if (MODE == ISM_RBF && A.ldg < col_end - col_begin)
+        return set_err_msg("gkmhip_ism_rbf_block: leading dimension too small", 2);
     const int L = ctx->L, d = ctx->d, mb = ism_mb(L, d);
     if (HYP && d >= L)
         return set_err_msg("gkmhip_hyp_block: needs d < L (a pair with m = L has no matched base to credit)", 2);
@@ -493,12 +549,14 @@ int ism_launch(gkmhip_ctx *ctx, IsmArgs &A, const int *rows, int nrows, int col_
     A.L = L; A.d = d; A.mb = mb; A.col_begin = col_begin;
     A.tile = tile; A.stride = stride; A.ntiles = ntiles;
     A.part = ctx->blk_part.p; A.part_stride = per * bases; A.gpart = HYP ? nullptr : ctx->ism_gpart.p;
+    A.codes = ctx->codes.p; A.gamma = ctx->gamma;
     /* at most 6 248 + 4 x (13 + 3 x 12) x 804 = 163 832 bytes (L = 12, d = 12); 44 648 at gkmQC's shape */
     const size_t lds = ISM_LDS_FIXED + (size_t)(d + 1 + 3 * mb) * (size_t)stride * sizeof(uint32_t);
-    HIPCHK(hipFuncSetAttribute((const void *)k_ism<HYP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(hipFuncSetAttribute((const void *)k_ism<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     if (int rc = gkm_launch_begin(ctx, stream)) return rc;
-    hipLaunchKernelGGL(k_ism<HYP>, dim3((unsigned)ncols, (unsigned)nchunks, (unsigned)ntiles), dim3(ISM_THREADS), lds, stream, A);
-    if (int rc = gkm_launch_stop(ctx, stream)) return rc; /* (k_ism<HYP> alone is timed) */
+    hipLaunchKernelGGL(k_ism<MODE>, dim3((unsigned)ncols, (unsigned)nchunks, (unsigned)ntiles), dim3(ISM_THREADS), lds,
+                       stream, A);
+    if (int rc = gkm_launch_stop(ctx, stream)) return rc; /* (k_ism<MODE> alone is timed) */
     if constexpr (HYP)
         hipLaunchKernelGGL(k_ism_hyp_reduce, dim3((unsigned)ncols), dim3(256), 0, stream, (const double *)ctx->blk_part.p,
                            (int64_t)per * bases, nchunks, (const int *)ctx->len.p, (const int64_t *)ctx->off.p,
@@ -509,10 +567,10 @@ int ism_launch(gkmhip_ctx *ctx, IsmArgs &A, const int *rows, int nrows, int col_
                            (const int *)ctx->len.p, (const int64_t *)ctx->off.p, (const uint8_t *)ctx->codes.p, col_begin,
                            out, base);
     HIPCHK(hipGetLastError());
-    gkm_launch_done(ctx, HYP ? "k_ism<true>" : "k_ism", comparisons);
+    gkm_launch_done(ctx, kernel[MODE], comparisons);
     if (getenv("GKM_TRACE"))
         fprintf(stderr, "gkmhip: %s %d rows x columns [%d, %d) -> %s (%d chunks of %d rows, %d tiles of %d positions, "
-                        "%zu bytes of LDS, %.3g comparisons)\n", HYP ? "hypothetical" : "ism", nrows, col_begin, col_end,
+                        "%zu bytes of LDS, %.3g comparisons)\n", what[MODE], nrows, col_begin, col_end,
                 ctx->last_kernel, nchunks, chunk, ntiles, tile, lds, comparisons);
     return 0;
 }
@@ -525,26 +583,45 @@ extern "C" int gkmhip_ism_block(gkmhip_ctx *ctx, const int *rows, int nrows, int
 {
     if (!ctx || !rows || nrows <= 0 || !fold_u || !fold_b || !gcoef || !coef || !out)
         return set_err_msg("gkmhip_ism_block: bad arguments", 2);
-    IsmArgs A;
+    IsmArgs A = {};
     for (int m = 0; m < GKM_MAXD1; m++) {
         A.fu[m] = m <= ctx->d ? fold_u[m] : 0.0;
         A.fb[m] = m < ism_mb(ctx->L, ctx->d) ? fold_b[m] : 0.0;
         A.gc[m] = m <= ctx->d ? gcoef[m] : 0.0;
     }
-    return ism_launch<false>(ctx, A, rows, nrows, col_begin, col_end, coef, out, base, (hipStream_t)stream_);
+    return ism_launch<ISM_LIN>(ctx, A, rows, nrows, col_begin, col_end, coef, out, base, (hipStream_t)stream_);
 }
 
 extern "C" int gkmhip_hyp_block(gkmhip_ctx *ctx, const int *rows, int nrows, int col_begin, int col_end,
                                 const double *share, const double *coef, double *out, void *stream_)
 {
     if (!ctx || !rows || nrows <= 0 || !share || !coef || !out) return set_err_msg("gkmhip_hyp_block: bad arguments", 2);
-    IsmArgs A;
+    IsmArgs A = {};
     for (int m = 0; m < GKM_MAXD1; m++) {
         A.fu[m] = m <= ctx->d ? share[m] : 0.0;                    /* U row m: share[m] */
         A.fb[m] = m < ism_mb(ctx->L, ctx->d) ? share[m] : 0.0;     /* B row m + 1: share[m] */
         A.gc[m] = 0.0;
     }
-    return ism_launch<true>(ctx, A, rows, nrows, col_begin, col_end, coef, out, nullptr, (hipStream_t)stream_);
+    return ism_launch<ISM_HYP>(ctx, A, rows, nrows, col_begin, col_end, coef, out, nullptr, (hipStream_t)stream_);
+}
+
+extern "C" int gkmhip_ism_rbf_block(gkmhip_ctx *ctx, const int *rows, int nrows, int col_begin, int col_end,
+                                    const double *fold_u, const double *fold_b, const double *dual, const double *sq,
+                                    const double *gx, int64_t ld, const double *ysq, double *out, double *base,
+                                    void *stream_)
+{
+    if (!ctx || !rows || nrows <= 0 || !fold_u || !fold_b || !dual || !sq || !gx || !ysq || !out)
+        return set_err_msg("gkmhip_ism_rbf_block: bad arguments", 2);
+    if (!ctx->rbf)
+        return set_err_msg("gkmhip_ism_rbf_block: the context's kernel type is not 3 or 5 (linear types: gkmhip_ism_block)", 2);
+    IsmArgs A = {};
+    for (int m = 0; m < GKM_MAXD1; m++) {
+        A.fu[m] = m <= ctx->d ? fold_u[m] : 0.0;
+        A.fb[m] = m < ism_mb(ctx->L, ctx->d) ? fold_b[m] : 0.0;
+        A.gc[m] = 0.0;
+    }
+    A.sq = sq; A.gx = gx; A.ldg = ld; A.ysq = ysq;
+    return ism_launch<ISM_RBF>(ctx, A, rows, nrows, col_begin, col_end, dual, out, base, (hipStream_t)stream_);
 }
 
 extern "C" int gkmhip_ism_self_profiles(gkmhip_ctx *ctx, int col_begin, int col_end, int64_t *prof, void *stream_)

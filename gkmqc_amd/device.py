@@ -121,6 +121,8 @@ def load():
     L.gkmhip_explain_block.argtypes = (vp, vp, i32, i32, i32, vp, vp, vp, vp, vp)
     L.gkmhip_ism_block.restype = i32
     L.gkmhip_ism_block.argtypes = (vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp)
+    L.gkmhip_ism_rbf_block.restype = i32
+    L.gkmhip_ism_rbf_block.argtypes = (vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp)
     L.gkmhip_hyp_block.restype = i32
     L.gkmhip_hyp_block.argtypes = (vp, vp, i32, i32, i32, vp, vp, vp, vp)
     L.gkmhip_lmer_weights.restype = i32
@@ -443,6 +445,22 @@ class GramContext:
         self._chk(self.lib.gkmhip_ism_block(self.handle, rows.ctypes.data, len(rows), int(col_begin), int(col_end),
                                             fold[0].ctypes.data, fold[1].ctypes.data, fold[2].ctypes.data, coef_ptr,
                                             out_ptr, base_ptr, stream), "gkmhip_ism_block")
+
+    def ism_rbf_block(self, rows, col_begin, col_end, fold_u, fold_b, dual_ptr, sq_ptr, gx_ptr, ld, ysq_ptr, out_ptr,
+                      base_ptr=None, stream=0):
+        """Every single-base mutant's RBF decision sum for the queries [col_begin, col_end) against the support vectors
+        `rows` into out_ptr (4 doubles per base of the range, columns A, C, G, T; 0.0 at the query's own base) and
+        base_ptr (one double per query, or None): fold_u, fold_b = d + 1 host doubles each, dual_ptr = len(rows) device
+        doubles, sq_ptr = the norms of every uploaded sequence, gx_ptr = gram_block's raw values of the same rows and
+        range with leading dimension ld, ysq_ptr = 4 device doubles per base, the mutants' norms (include/gkm_hip.h
+        gkmhip_ism_rbf_block).  Kernel types 3 and 5 only."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        fold = [np.ascontiguousarray(v, dtype=np.float64) for v in (fold_u, fold_b)]
+        if any(len(v) != self.d + 1 for v in fold):
+            raise GkmError("ism_rbf_block: fold_u and fold_b need d + 1 = %d values each" % (self.d + 1))
+        self._chk(self.lib.gkmhip_ism_rbf_block(self.handle, rows.ctypes.data, len(rows), int(col_begin), int(col_end),
+                                                fold[0].ctypes.data, fold[1].ctypes.data, dual_ptr, sq_ptr, gx_ptr,
+                                                int(ld), ysq_ptr, out_ptr, base_ptr, stream), "gkmhip_ism_rbf_block")
 
     def hyp_block(self, rows, col_begin, col_end, share, coef_ptr, out_ptr, stream=0):
         """Raw hypothetical importance of the queries [col_begin, col_end) against the support vectors `rows` into

@@ -16,6 +16,9 @@ The other half of a gkm-SVM next to the cross-validation of `gkmsvm.py` (the cou
   * `ism` scores every single-base substitution of each query (gkmhip_ism_block and
     gkmhip_ism_self_profiles): per block the same upload and exact self norms, one launch that tallies how each l-mer pair's
     mismatch count moves under a substitution, and one that counts every mutant's profile against itself;
+  * `mutant_scores` gives the score of every single-base mutant itself, for every model `score` serves, the RBF types
+    included: a linear model through `ism`'s launches, an RBF model through gkmhip_ism_rbf_block, which
+    takes the raw kernel values of `score`'s Gram launch and folds each support vector's tallies through exp();
   * `hypothetical` gives, for every position and each of the four bases, the importance that base would get there
     (gkmhip_hyp_block): ism's upload, self norms, mutant self profiles and tallies, folded the way
     `explain` folds its own;
@@ -43,6 +46,7 @@ The other half of a gkm-SVM next to the cross-validation of `gkmsvm.py` (the cou
     python -m gkmqc_amd.gkmpredict predict query.fa model.txt out.txt
     python -m gkmqc_amd.gkmpredict explain [--block Qb] query.fa model.txt out.txt
     python -m gkmqc_amd.gkmpredict ism [--block Qb] query.fa model.txt out.txt
+    python -m gkmqc_amd.gkmpredict mutant-scores [--block Qb] query.fa model.txt out.txt
     python -m gkmqc_amd.gkmpredict hypothetical [--block Qb] query.fa model.txt out.txt
     python -m gkmqc_amd.gkmpredict weights model.txt weights.txt
     python -m gkmqc_amd.gkmpredict predict-table [--block Qb] query.fa weights.txt out.txt
@@ -668,7 +672,8 @@ def ism(model, fasta_or_sequences, device=0, block=None, on_block=None):
     with score as `score` computes it, sum_s dual_coef_s G(y, s) / (sq_s sqrt(G(y, y))) - rho, on the
     no-wrap domain (every mismatch profile involved below 2^31: INTEGRATION.md §5b); beyond it `score` follows the
     reference's 32-bit wrap and this is the difference of the exact scores, every norm from 64-bit profiles.  Every
-    model `score` serves except RBF (types 3 and 5), k = 0 included; every query length `score` accepts.
+    model `score` serves except RBF (types 3 and 5), k = 0 included; every query length `score` accepts.  (An RBF model's
+    mutagenesis is `mutant_scores` less its own-base column.)
     block: queries per device block (default_ism_block).  on_block(dict) (measurements): called after every block with
     its size, k_ism's milliseconds (HIP events), its l-mer comparisons, the self-profile kernels' milliseconds and the
     block's wall time."""
@@ -719,6 +724,85 @@ def write_ism(path, names, values):
 def read_ism(path):
     """-> (names, [float64 array (T, 4) per query]) from a file written by write_ism."""
     return _read_values(path, (-1, 4))
+
+
+# ------------------------------------------------------------------ the score of every single-base mutant
+def default_mutscores_block(max_len, d, n_sv, budget=BLOCK_BYTES):
+    """Queries per block: per query, what `ism` takes per base (default_ism_block) plus the mutants' (bases, 4) norms, and
+    the n_sv raw kernel values of an RBF model's Gram launch with that launch's tile-transposed output (about as big),
+    within `budget` bytes of device memory.  n_sv: 0 for a linear model, which runs no Gram launch."""
+    per_query = 8 * (3 * ISM_CHUNKS + 4 * (int(d) + 1) + 28) * max(int(max_len), 64) + 16 * max(int(n_sv), 0)
+    return int(max(1, min(1 << 20, budget // per_query)))
+
+
+def mutant_scores(model, fasta_or_sequences, device=0, block=None, on_block=None):
+    """The score of every single-base mutant of each query of a FASTA file (or a list / FlatSequences of base codes) ->
+    (names, [float64 array (T, 4) per query], columns A, C, G, T):
+
+        ms(x)[t, b] = score(y),   y = x with base t set to b   (so ms(x)[t, x[t]] = score(x), one double at every t)
+
+    with score as `score` computes it, rho included, on the no-wrap domain `ism` documents.
+    In-silico mutagenesis of any model is ms - ms[t, x[t]]; the effect of one SNV (deltaSVM) is one entry of that.  Every
+    model `score` serves, the RBF types 3 and 5 and k = 0 included; every query length `score` accepts.
+
+    Types 0, 1, 2 and 4 take `ism`'s launches and finish: (base + D) / sqrt(G(y, y)) + rho.  Types 3 and 5 (DESIGN.md
+    §5m) take the raw G(x, s) from `score`'s Gram launch and fold every support vector's tallies through
+    dual_s exp(gamma (G(y, s) / (sq_s sqrt(G(y, y))) - 1)) in gkmhip_ism_rbf_block.
+    block: queries per device block (default_mutscores_block).  on_block(dict) (measurements): called after every block
+    with its size, the fold kernel's milliseconds (HIP events), its l-mer comparisons, the self-profile kernels' and (RBF)
+    the Gram kernel's milliseconds and the block's wall time."""
+    import torch
+    seqs, names = _as_queries(fasta_or_sequences)
+    check_queries(model, seqs)
+    d = model.d
+    rbf = model.kernel_type in (3, 5)
+    blocks = _Blocks(model, seqs, device, block,
+                     default_mutscores_block(_longest(seqs), d, model.n_sv if rbf else 0), exact=True)
+    ctx, S, sq, dev, stream = blocks.ctx, blocks.S, blocks.sq, blocks.dev, blocks.stream
+    fold_u, fold_b, c = ism_coefficients(model)
+    # score = sum_s dual_coef_s K(y, s) + rho for both SVM types (Model): what `score` makes of k_decision's sum - rho
+    # with the C-SVC sign, and of the signed sum less LIBSVM's rho = -model.rho for SVR
+    rho = model.rho
+    out = []
+    with torch.cuda.device(dev):
+        dual = torch.from_numpy(model.dual_coef()).to(dev)
+        most = blocks.most_bases()
+        D = torch.empty((most, 4), dtype=torch.float64, device=dev)
+        prof = torch.empty((most, 4, d + 1), dtype=torch.int64, device=dev)
+        base = torch.empty(blocks.qb_max, dtype=torch.float64, device=dev)
+        if rbf:
+            ctx.set_kernel(dv.KERNEL_AUTO)
+            gx = torch.empty((S, blocks.qb_max), dtype=torch.float64, device=dev)
+        for b in blocks:
+            qb, nb = b.qb, b.nb
+            gram_ms = None
+            if rbf:
+                ctx.gram_block(blocks.rows, S, S + qb, gx.data_ptr(), blocks.qb_max, stream)      # raw: not normalised
+                gram_ms = ctx.last_kernel_ms() if on_block is not None else None
+            ctx.ism_self_profiles(S, S + qb, prof.data_ptr(), stream)
+            self_ms = ctx.last_kernel_ms() if on_block is not None else None
+            ysq = _mutant_norms_sq(prof[:nb], c).sqrt_()
+            if rbf:
+                ctx.ism_rbf_block(blocks.rows, S, S + qb, fold_u, fold_b, dual.data_ptr(), sq.data_ptr(), gx.data_ptr(),
+                                  blocks.qb_max, ysq.data_ptr(), D.data_ptr(), base.data_ptr(), stream)
+                res = D[:nb] + rho
+                own = base[:qb] + rho
+            else:
+                coef = dual / sq[:S]
+                ctx.ism_block(blocks.rows, S, S + qb, fold_u, fold_b, c, coef.data_ptr(), D.data_ptr(), base.data_ptr(),
+                              stream)
+                per = torch.from_numpy(np.diff(b.qoff)).to(dev)
+                bx = torch.repeat_interleave(base[:qb], per)
+                res = (bx[:, None] + D[:nb]).div_(ysq).add_(rho)
+                own = base[:qb] / sq[S:S + qb] + rho
+            host = res.cpu().numpy()
+            host[np.arange(nb), b.codes] = np.repeat(own.cpu().numpy(), np.diff(b.qoff))
+            out.extend(b.split(host))
+            if on_block is not None:
+                on_block(dict(queries=qb, ism_kernel_ms=ctx.last_kernel_ms(), comparisons=ctx.last_comparisons(),
+                              kernel=ctx.last_kernel_name(), self_kernels_ms=self_ms, gram_kernel_ms=gram_ms,
+                              wall_ms=(time.perf_counter() - b.t0) * 1e3))
+    return names, out
 
 
 # ------------------------------------------------------------------ hypothetical importance
@@ -1737,6 +1821,10 @@ def build_parser():
     z = sub.add_parser("ism", help="in-silico mutagenesis of the sequences of query.fa: name<TAB>4T values per line, "
                                    "position-major, columns A, C, G, T")
     _add_arguments(z, "query_fa", "model", "output")
+    u = sub.add_parser("mutant-scores", help="the score of every single-base mutant of the sequences of query.fa, RBF "
+                                             "models included: name<TAB>4T values per line, position-major, columns "
+                                             "A, C, G, T (the ism format)")
+    _add_arguments(u, "query_fa", "model", "output")
     h = sub.add_parser("hypothetical", help="hypothetical importance of the sequences of query.fa: name<TAB>4T values per "
                                             "line, position-major, columns A, C, G, T (the ism format)")
     _add_arguments(h, "query_fa", "model", "output")
@@ -1802,6 +1890,7 @@ _QUERY_COMMANDS = {
     "predict": (score, write_scores),
     "explain": (explain, write_explanation),
     "ism": (ism, write_ism),
+    "mutant-scores": (mutant_scores, write_ism),
     "hypothetical": (hypothetical, write_ism),
     "predict-table": (score_with_table, write_scores),
     "explain-table": (explain_with_table, write_explanation),

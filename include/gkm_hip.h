@@ -160,6 +160,29 @@ int gkmhip_ism_block(gkmhip_ctx *ctx, const int *rows, int nrows, int col_begin,
 int gkmhip_hyp_block(gkmhip_ctx *ctx, const int *rows, int nrows, int col_begin, int col_end, const double *share,
                      const double *coef, double *out, void *stream);
 
+/* Every single-base mutant's decision sum for an RBF model (kernel types 3 and 5): rows are support vectors,
+ * the columns [col_begin, col_end) queries.  With gamma the context's and
+ *   term(i, G, n) = dual[i] * exp(gamma * (G / (sq[rows[i]] * n) - 1))   (product first, one division, then exp: the
+ *                                                                         expression gkmhip_normalize_block evaluates),
+ * for query j, each of its bases t and each base b other than x_j[t],
+ *   out[4 (off[j] - off[col_begin] + t) + b] = sum_i term(i, gx[i][j - col_begin] + dG_i(t, b), ysq[4 (.. + t) + b]),
+ * the sum over the rows in list order, where dG_i(t, b) = sum_{m ascending} (fold_u[m] U_m[t] + fold_b[m-1] B_m[t][b]) is
+ * formed from the exact tallies exactly as gkmhip_ism_block forms it; and 0.0 at b = x_j[t], which the caller fills (it
+ * is base's value).  If base is not NULL, base[j - col_begin] = sum_i term(i, gx[i][j - col_begin], sq[j]).
+ *   fold_u, fold_b HOST, d + 1 doubles each, as gkmhip_ism_block's;
+ *   dual           DEVICE, nrows doubles (scoring: dual_coef_i, NOT divided by the norm);
+ *   sq             DEVICE, n doubles: sqrt(G(i, i)) of every uploaded sequence;
+ *   gx             DEVICE, row i at gx + i ld: the raw G(x_j, rows[i]) of gkmhip_gram_block over the same rows and range
+ *                  (not normalised); ld >= col_end - col_begin;
+ *   ysq            DEVICE, 4 doubles per base of the range: sqrt(G(y, y)) of the mutant to base b (at b = x_j[t]: unused);
+ *   out            DEVICE, 4 doubles per base of the range; base DEVICE, col_end - col_begin doubles, or NULL.
+ * rows: host array, strictly ascending.  A context of another kernel type is refused.  Chunking, tiling and bit-identity
+ * as gkmhip_ism_block: no floating-point atomics, the chunks' partial rows are summed in chunk order.  Work is enqueued on
+ * `stream`; last_kernel_ms / last_comparisons / last_kernel_name describe k_ism_rbf. */
+int gkmhip_ism_rbf_block(gkmhip_ctx *ctx, const int *rows, int nrows, int col_begin, int col_end, const double *fold_u,
+                         const double *fold_b, const double *dual, const double *sq, const double *gx, int64_t ld,
+                         const double *ysq, double *out, double *base, void *stream);
+
 /* In-silico mutagenesis, self side: for query j of [col_begin, col_end), each base t and each base b (0..3),
  *   prof[(4 (off[j] - off[col_begin] + t) + b) (d + 1) + m] = P_m(y, y), m = 0..d,
  * the exact integer mismatch profile of y = x_j with base t set to b against itself (b = x_j[t]: P_m(x_j, x_j)), as
