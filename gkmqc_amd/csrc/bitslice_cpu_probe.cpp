@@ -162,6 +162,37 @@ extern "C" int bsprobe_group_any_grouped(int L, int d, const uint32_t *Ahi, cons
     return 1;
 }
 
+/* ---- the crossings entry (tests/test_group_crossings.py) -----------------------------------------
+ * window_group_any_grouped, window_group_any_crossings (from the middle, what the shift-record kernel runs) and its
+ * one-direction form on the planes given; AVg[2] is taken as it comes (any words, not only table-built ones).  Returns 1
+ * for an (L, d) outside the device table, 2 for one whose threshold is not the top plane. */
+template <int W, int L, int D, int GRP>
+static int run_group_any_crossings(const uint32_t *Ahi, const uint32_t *Alo, const uint32_t *AVg, const uint32_t *Bhi,
+                                   const uint32_t *Blo, uint32_t *any_grouped, uint32_t *any_crossings, uint32_t *any_one_way)
+{
+    if constexpr (!top_plane_serves(L, D)) {
+        return 2;
+    } else {
+        window_group_any_grouped<W, L, D, GRP>(Ahi, Alo, AVg, Bhi, Blo, any_grouped);
+        window_group_any_crossings<W, L, D, GRP>(Ahi, Alo, AVg, Bhi, Blo, any_crossings);
+        window_group_any_crossings<W, L, D, GRP, false>(Ahi, Alo, AVg, Bhi, Blo, any_one_way);
+        return 0;
+    }
+}
+
+#define XCASE(LL, DD) \
+    if (L == LL && d == DD) return run_group_any_crossings<10, LL, DD, 5>(Ahi, Alo, AVg, Bhi, Blo, any_grouped, any_crossings, any_one_way);
+#define XCASE_L(LL) XCASE(LL, 0) XCASE(LL, 1) XCASE(LL, 2) XCASE(LL, 3) XCASE(LL, 4)
+
+extern "C" int bsprobe_group_any_crossings(int L, int d, const uint32_t *Ahi, const uint32_t *Alo, const uint32_t *AVg,
+                                           const uint32_t *Bhi, const uint32_t *Blo, uint32_t *any_grouped,
+                                           uint32_t *any_crossings, uint32_t *any_one_way)
+{
+    XCASE_L(5) XCASE_L(6) XCASE_L(7) XCASE_L(8) XCASE_L(9) XCASE_L(10) XCASE_L(11) XCASE_L(12)
+    XCASE(11, 5) XCASE(12, 5) XCASE(12, 6)
+    return 1;
+}
+
 /* the table builders, for the same test: the three planes of a row segment (out[plane * W + w]) ... */
 extern "C" void bsprobe_row_planes(const uint8_t *codes, int len, int s0, int W, int L, uint32_t *out)
 {
@@ -322,9 +353,9 @@ static int run_packed(const uint8_t *codes, const int64_t *off, const int *rows,
                     };
                     for (int delta = 0; delta < T; delta++) {
                         uint32_t any[2];
-                        if constexpr (top_plane_serves(L, D)) /* (the same-length kernel's entry: a superset per group) */
-                            window_group_any_grouped<W, L, D, SHIFT_GROUP_WORDS>(Ahi, Alo, AVg, &sb[st][0][(size_t)delta],
-                                                                                 &sb[st][1][(size_t)delta], any);
+                        if constexpr (top_plane_serves(L, D)) /* (the shift-record kernel's entry: a superset per group) */
+                            window_group_any_crossings<W, L, D, SHIFT_GROUP_WORDS>(Ahi, Alo, AVg, &sb[st][0][(size_t)delta],
+                                                                                   &sb[st][1][(size_t)delta], any);
                         else
                             window_group_any<W, L, D, SHIFT_GROUP_WORDS>(Ahi, Alo, AV, &sb[st][0][(size_t)delta],
                                                                          &sb[st][1][(size_t)delta], any);

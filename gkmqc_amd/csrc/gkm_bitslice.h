@@ -486,6 +486,117 @@ GKM_HD void window_group_any_grouped(const uint32_t *Ahi, const uint32_t *Alo, c
     }
 }
 
+/*
+ * window_group_any_grouped without ever stepping the top count plane: the same any[], bit for bit, on every bit.
+ *
+ * The counter's step of the top plane is b_top[w+1] = b_top[w] ^ t[w+1], with t the carry/borrow into it, which the step of
+ * the planes below computes anyway.  Over any run of consecutive words, then,
+ *     OR_w b_top[w] == b_top[first] | OR of t over the steps inside the run:
+ * if no t fires every b_top of the run is equal; if one fires, b_top differs on its two sides and one of the two is set.  A
+ * Boolean identity on arbitrary words: it does not care what the counter counts or what bit row 31 of the extension words
+ * holds.  So the top plane of the FIRST window is all that is ever kept of it.
+ *
+ * FROM THE MIDDLE (MIDDLE = true): the first window is word GRP's (the adder tree runs over Z[GRP .. GRP+L-1]); one chain of
+ * steps goes up to word W-1, a second one, from a copy of the lower planes, down to word 0 (stepping down, the word that
+ * enters is Z[w-1] and the one that leaves Z[w+L-1]: the same truth tables).  With P = bitlen(L) planes a step is
+ * 2 (P - 1) ops, a chain's last step P - 1 (its plane updates are dead):
+ *     any[1] = (b_top[GRP] | t_up[1] | .. | t_up[GRP-1]) & AVg[1]
+ *     any[0] = ((b_top[GRP] ^ t_dn[0]) | t_dn[1] | .. | t_dn[GRP-1]) & AVg[0]      (b_top[GRP-1] = b_top[GRP] ^ t_dn[0])
+ * three 3-input ops each at GRP = 5.  W = 10, P = 4: 7 steps of 6 + 2 of 3 + 6 = 54 where the stepped top plane took
+ * 8 x 7 + 4 + 6 = 66.
+ * ONE DIRECTION (MIDDLE = false): the first window is word 0's, one chain up to word W-1:
+ *     any[0] = (b_top[0] | t[1] | .. | t[GRP-1]) & AVg[0]
+ *     any[1] = ((b_top[0] ^ t[1] ^ .. ^ t[GRP]) | t[GRP+1] | .. | t[W-1]) & AVg[1]
+ * W = 10, P = 4: 8 x 6 + 3 + 3 + 5 = 59.  It holds one copy of the lower planes; kept as the form to fall back to where the
+ * other does not fit its registers, and as a second route to the same bits for the CPU test.
+ */
+constexpr int TT_AXB_OR_C = 0xBE;  /* (a ^ b) | c */
+constexpr int TT_AB_AND_C = 0xA8;  /* (a | b) & c */
+
+/* one step of the up/down counter's planes below the top one (lo[0 .. P-2]); returns the carry/borrow into the top plane.
+ * `last`: the chain ends here, the planes are not needed again */
+template <int P>
+GKM_HD uint32_t count_step_crossing(uint32_t *lo, uint32_t zin, uint32_t zout, bool last)
+{
+    const uint32_t old0 = lo[0];
+    if (!last) lo[0] = lop3<TT_XOR3>(old0, zin, zout);
+    uint32_t t = lop3<TT_BXC_AND_AXC>(old0, zin, zout);
+#pragma unroll
+    for (int i = 1; i < P - 1; i++) {
+        const uint32_t old = lo[i];
+        if (!last) lo[i] = old ^ t;
+        t = lop3<TT_A_AND_BXC>(t, old, zout);
+    }
+    return t;
+}
+/* (a | t[0] | .. | t[N-1]) & v, three inputs at a time */
+template <int N>
+GKM_HD uint32_t or_terms_and(uint32_t a, const uint32_t *t, uint32_t v)
+{
+#pragma unroll
+    for (int i = 0; i + 1 < N; i += 2) a = lop3<TT_OR3>(a, t[i], t[i + 1]);
+    if constexpr (N % 2 == 1) return lop3<TT_AB_AND_C>(a, t[N - 1], v);
+    else return a & v;
+}
+
+template <int W, int L, int D, int GRP, bool MIDDLE = true>
+GKM_HD void window_group_any_crossings(const uint32_t *Ahi, const uint32_t *Alo, const uint32_t *AVg, const uint32_t *Bhi,
+                                       const uint32_t *Blo, uint32_t *any)
+{
+    static_assert(L >= 2 && L <= 12, "L out of range");
+    static_assert(W == 2 * GRP && GRP >= 3, "a shift is two groups");
+    static_assert(top_plane_serves(L, D), "the crossings form exists for the top-plane (L, D) pairs only");
+    constexpr int P = bitlen(L);
+    static_assert(P >= 2, "a top plane and at least one below it");
+    constexpr int BETA = top_plane_bias(L, D);
+    constexpr int NX = W + L - 1;
+    constexpr int C = MIDDLE ? GRP : 0; /* the word whose window the adder tree sums */
+    uint32_t Z[NX]; /* MATCH bits, as in window_group_any */
+#pragma unroll
+    for (int w = 0; w < W; w++) Z[w] = lop3<TT_NOT_A_OR_BXC>(Ahi[w] ^ Bhi[w], Alo[w], Blo[w]);
+#pragma unroll
+    for (int x = W; x < NX; x++) Z[x] = Z[x - W] >> 1;
+
+    Cnt<P, L + BETA> cnt;
+    static_assert(Cnt<P, L + BETA>::P == P && !Cnt<P, L + BETA>::OV, "the biased count fills exactly its planes");
+    cnt.ovf = 0u;
+    plane_sum_columns_biased<0, P, L + BETA, L, BETA == 1>(Z + C, cnt);
+    const uint32_t top = cnt.b[P - 1];
+    uint32_t up[P - 1];
+#pragma unroll
+    for (int i = 0; i < P - 1; i++) up[i] = cnt.b[i];
+
+    if constexpr (MIDDLE) {
+        uint32_t dn[P - 1];
+#pragma unroll
+        for (int i = 0; i < P - 1; i++) dn[i] = cnt.b[i];
+        uint32_t tu[GRP - 1], td[GRP];
+#pragma unroll
+        for (int s = 0; s < GRP - 1; s++) { /* to word C + 1 + s */
+            const int w = C + 1 + s;
+            tu[s] = count_step_crossing<P>(up, Z[w + L - 1], Z[w - 1], s == GRP - 2);
+        }
+#pragma unroll
+        for (int s = 0; s < GRP; s++) { /* down to word C - 1 - s: Z[w] enters, Z[w + L] leaves */
+            const int w = C - 1 - s;
+            td[s] = count_step_crossing<P>(dn, Z[w], Z[w + L], s == GRP - 1);
+        }
+        any[1] = or_terms_and<GRP - 1>(top, tu, AVg[1]);
+        any[0] = or_terms_and<GRP - 2>(lop3<TT_AXB_OR_C>(top, td[0], td[1]), td + 2, AVg[0]);
+    } else {
+        uint32_t t[W - 1]; /* t[w - 1]: into the top plane on the step to word w */
+#pragma unroll
+        for (int w = 1; w < W; w++) t[w - 1] = count_step_crossing<P>(up, Z[w + L - 1], Z[w - 1], w == W - 1);
+        any[0] = or_terms_and<GRP - 1>(top, t, AVg[0]);
+        /* b_top[GRP] = b_top[0] ^ (the steps to words 1 .. GRP): GRP + 1 terms, three at a time */
+        uint32_t e = top;
+#pragma unroll
+        for (int i = 0; i + 1 < GRP; i += 2) e = lop3<TT_XOR3>(e, t[i], t[i + 1]);
+        if constexpr (GRP % 2 == 0) any[1] = or_terms_and<GRP - 1>(e, t + GRP, AVg[1]);
+        else any[1] = or_terms_and<GRP - 2>(lop3<TT_AXB_OR_C>(e, t[GRP - 1], t[GRP]), t + GRP + 1, AVg[1]);
+    }
+}
+
 /* ------------------------------------------------------------------ tables */
 /* Word w of a ROW SEGMENT plane.  Segment base i = b*W + w is sequence position s0 + i.
  * plane 0/1: hi/lo bit of the base code (0 beyond the end of the sequence);

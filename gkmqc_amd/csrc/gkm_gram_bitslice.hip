@@ -37,6 +37,11 @@ constexpr int BS_CAP = BS_TRIP + 64;
 #ifndef GKM_BS_PACKED_WAVES
 #define GKM_BS_PACKED_WAVES 6 /* the several-pieces variants (ragged lengths): compiled for 6 they come out at 72 VGPRs and run 7 */
 #endif
+#ifndef GKM_BS_CROSSINGS_MIDDLE
+#define GKM_BS_CROSSINGS_MIDDLE 1 /* the shift-record variants' counting loop (gkm_bitslice.h window_group_any_crossings): 1 = the first
+                                     window in the middle of the shift, two chains (106 VALU per shift at L = 11, 69-71 VGPRs); 0 = one
+                                     chain from word 0 (111): profiles/r15_kernel_ab_crossings.txt has both */
+#endif
 #ifndef GKM_TRIP_PRIO
 #define GKM_TRIP_PRIO 3 /* wave priority (s_setprio, 0..3) inside a trip; 0 = as rounds 1-3 */
 #endif
@@ -277,8 +282,12 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : (PK >= 4 && PK <= 7) ? GKM_BS_WAVES
          * costs what three VALU instructions do (profiles/r5_trip_sensitivity.txt).  Hence the layout of the origin word
          * (gkm_bitslice.h pack_meta: fields that are masked in place or shifted out of the top), 128 bytes per lane of
          * packed positions, the column's strands interleaved word by word, (a & const) | b as one v_bitop3_b32, the strand
-         * as wave-uniform scalars.  Same arithmetic as resolve_hit_packed (gkm_bitslice.h), which the CPU tests run
-         * against the oracle. */
+         * as wave-uniform scalars.  NOT the arithmetic of resolve_hit_packed (gkm_bitslice.h), which the CPU model
+         * (bitslice_cpu_probe.cpp) runs hit by hit: a visit evaluates all five windows of a (bit row, group) from one folded
+         * XOR word, reads the zero-guarded positional weight table with its wrap bytes (k_build_postab) and CYCLIC packed
+         * strands (pk_word_cyclic), and relies on groups being owned whole (gkm_pack.h own_mult).  The CPU model shares the
+         * counting loop and shift_record_visit with it; the visit itself is held against the oracle, k_gram_direct and the
+         * group-record kernel code by the GPU tests. */
         /* One trip over the `c` records on top of the list.  SHIFT RECORDS (PK = 6, 7) differ from what follows in the head and
          * the tail of a visit only: the record's three words say which bit rows of BOTH groups of one shift hold hits; the
          * visit takes the lowest bit row of the first non-empty group (w0 = 0 or 5 comes from there, not from the origin
@@ -477,7 +486,9 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : (PK >= 4 && PK <= 7) ? GKM_BS_WAVES
                         /* per group the OR of its words' hits, straight from the count (gkm_bitslice.h: where the bias
                          * allows, the top plane of a count of matches -- one op per word for threshold, validity and OR) */
                         uint32_t grp_any[W / BS_GRP];
-                        if constexpr (GROUP_VALID) /* a superset per group: see AVg above */
+                        if constexpr (GROUP_VALID && SHIFTREC) /* the same words as the next entry, the top plane never stepped */
+                            window_group_any_crossings<W, L, D, BS_GRP, GKM_BS_CROSSINGS_MIDDLE != 0>(Ahi, Alo, AVg, bh + u, bl + u, grp_any);
+                        else if constexpr (GROUP_VALID) /* a superset per group: see AVg above */
                             window_group_any_grouped<W, L, D, BS_GRP>(Ahi, Alo, AVg, bh + u, bl + u, grp_any);
                         else
                             window_group_any<W, L, D, BS_GRP>(Ahi, Alo, AV, bh + u, bl + u, grp_any);
