@@ -193,6 +193,34 @@ extern "C" int bsprobe_group_any_crossings(int L, int d, const uint32_t *Ahi, co
     return 1;
 }
 
+/* ---- the centres entry (tests/test_group_centres.py) ----------------------------------------------
+ * window_group_any_grouped and window_group_any_centres (what the shift-record kernel runs: no counter, each group from its
+ * centre window) on the planes given; AVg[2] is taken as it comes.  Return codes as bsprobe_group_any_crossings. */
+template <int W, int L, int D, int GRP>
+static int run_group_any_centres(const uint32_t *Ahi, const uint32_t *Alo, const uint32_t *AVg, const uint32_t *Bhi,
+                                 const uint32_t *Blo, uint32_t *any_grouped, uint32_t *any_centres)
+{
+    if constexpr (!top_plane_serves(L, D)) {
+        return 2;
+    } else {
+        window_group_any_grouped<W, L, D, GRP>(Ahi, Alo, AVg, Bhi, Blo, any_grouped);
+        window_group_any_centres<W, L, D, GRP>(Ahi, Alo, AVg, Bhi, Blo, any_centres);
+        return 0;
+    }
+}
+
+#define CCASE(LL, DD) \
+    if (L == LL && d == DD) return run_group_any_centres<10, LL, DD, 5>(Ahi, Alo, AVg, Bhi, Blo, any_grouped, any_centres);
+#define CCASE_L(LL) CCASE(LL, 0) CCASE(LL, 1) CCASE(LL, 2) CCASE(LL, 3) CCASE(LL, 4)
+
+extern "C" int bsprobe_group_any_centres(int L, int d, const uint32_t *Ahi, const uint32_t *Alo, const uint32_t *AVg,
+                                         const uint32_t *Bhi, const uint32_t *Blo, uint32_t *any_grouped, uint32_t *any_centres)
+{
+    CCASE_L(5) CCASE_L(6) CCASE_L(7) CCASE_L(8) CCASE_L(9) CCASE_L(10) CCASE_L(11) CCASE_L(12)
+    CCASE(11, 5) CCASE(12, 5) CCASE(12, 6)
+    return 1;
+}
+
 /* the table builders, for the same test: the three planes of a row segment (out[plane * W + w]) ... */
 extern "C" void bsprobe_row_planes(const uint8_t *codes, int len, int s0, int W, int L, uint32_t *out)
 {
@@ -354,8 +382,8 @@ static int run_packed(const uint8_t *codes, const int64_t *off, const int *rows,
                     for (int delta = 0; delta < T; delta++) {
                         uint32_t any[2];
                         if constexpr (top_plane_serves(L, D)) /* (the shift-record kernel's entry: a superset per group) */
-                            window_group_any_crossings<W, L, D, SHIFT_GROUP_WORDS>(Ahi, Alo, AVg, &sb[st][0][(size_t)delta],
-                                                                                   &sb[st][1][(size_t)delta], any);
+                            window_group_any_centres<W, L, D, SHIFT_GROUP_WORDS>(Ahi, Alo, AVg, &sb[st][0][(size_t)delta],
+                                                                                 &sb[st][1][(size_t)delta], any);
                         else
                             window_group_any<W, L, D, SHIFT_GROUP_WORDS>(Ahi, Alo, AV, &sb[st][0][(size_t)delta],
                                                                          &sb[st][1][(size_t)delta], any);

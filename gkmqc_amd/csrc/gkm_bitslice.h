@@ -597,6 +597,77 @@ GKM_HD void window_group_any_crossings(const uint32_t *Ahi, const uint32_t *Alo,
     }
 }
 
+/*
+ * window_group_any_grouped without ANY counter: the same any[], bit for bit, on every bit.
+ *
+ * What a group delivers is the OR over its five windows of "biased count >= 2^(P-1)", i.e. whether the LARGEST of the five
+ * counts reaches the top plane.  The five windows of group w0 .. w0+4 lie at most two steps from the centre window
+ * C = w0 + 2, and a step changes a count by e = zin - zout in {-1, 0, +1}:
+ *     up:    e1 = Z[C+L]  - Z[C],       e2 = Z[C+L+1] - Z[C+1]          B[C+1] = B[C] + e1,  B[C+2] = B[C] + e1 + e2
+ *     down:  f1 = Z[C-1]  - Z[C+L-1],   f2 = Z[C-2]   - Z[C+L-2]        B[C-1] = B[C] + f1,  B[C-2] = B[C] + f1 + f2
+ * so the group's largest count is B[C] + M with M = max(0, e1, e1 + e2, f1, f1 + f2) in {0, 1, 2}.  The centre window is
+ * summed exactly by the adder tree (planes b[0 .. P-1], beta <= B[C] <= L + beta < 2^P: no wrap, as in window_group_any),
+ * and B[C] + M >= 2^(P-1) holds iff B[C] >= 2^(P-1), or B[C] = 2^(P-1) - 1 and M >= 1, or B[C] = 2^(P-1) - 2 and M = 2:
+ *     OR over the group of (B >= 2^(P-1))  ==  b[P-1] | (b[P-2] & .. & b[1] & ((b[0] & [M >= 1]) | [M = 2]))
+ * ([M = 2] implies [M >= 1], so the last term needs no ~b[0]).  An identity on arbitrary words once more: every B it speaks
+ * of is the sum of the same L words of Z that the stepped counter reaches, the extension words' fiction included.
+ * Per side, with (zin1, zout1) the first step's words and (zin2, zout2) the second's, three ops:
+ *     p        = zin2 & ~zout2                                         the second step counts up
+ *     [M >= 1] = (zin1 & ~zout1) | (~(zin1 ^ zout1) & p)               up at once, or level and then up
+ *     [M = 2]  = zin1 & ~zout1 & p
+ * and four to combine: u = ([M>=1]up | [M>=1]dn) & b[0];  v = [M=2]up | [M=2]dn | u;  x = b[P-2] & .. & b[1] & v;
+ * any = (b[P-1] | x) & AVg.  Ten ops per group beside its adder tree where the two chains of the crossings form and their ORs
+ * take 54 per shift beside one tree: W = 10, L = 11: 2 x (16 + 10) = 52 against 16 + 54 = 70, with no chain of dependent steps and no second
+ * copy of the lower planes.  GRP = 5 only: a window further than two steps from the centre would need M up to 3 and a
+ * third plane in the comparison.
+ */
+constexpr int TT_A_ANDN_B = 0x30;      /* a & ~b (c unused) */
+constexpr int TT_UP_OR_LEVEL_C = 0xB2; /* (a & ~b) | (~(a ^ b) & c) */
+constexpr int TT_A_ANDN_B_C = 0x20;    /* a & ~b & c */
+constexpr int TT_AND3 = 0x80;          /* a & b & c */
+
+template <int W, int L, int D, int GRP>
+GKM_HD void window_group_any_centres(const uint32_t *Ahi, const uint32_t *Alo, const uint32_t *AVg, const uint32_t *Bhi,
+                                     const uint32_t *Blo, uint32_t *any)
+{
+    static_assert(L >= 2 && L <= 12, "L out of range");
+    static_assert(W == 2 * GRP && GRP == 5, "a shift is two groups of five: every window within two steps of its group's centre");
+    static_assert(top_plane_serves(L, D), "the centres form exists for the top-plane (L, D) pairs only");
+    constexpr int P = bitlen(L);
+    static_assert(P >= 3, "a top plane, plane 0 and at least one between them");
+    constexpr int BETA = top_plane_bias(L, D);
+    constexpr int NX = W + L - 1;
+    uint32_t Z[NX]; /* MATCH bits, as in window_group_any */
+#pragma unroll
+    for (int w = 0; w < W; w++) Z[w] = lop3<TT_NOT_A_OR_BXC>(Ahi[w] ^ Bhi[w], Alo[w], Blo[w]);
+#pragma unroll
+    for (int x = W; x < NX; x++) Z[x] = Z[x - W] >> 1;
+
+#pragma unroll
+    for (int g = 0; g < W / GRP; g++) {
+        constexpr int HALF = GRP / 2;
+        const int C = g * GRP + HALF; /* the group's centre word: C - 2 >= 0, C + L + 1 <= NX - 1 */
+        Cnt<P, L + BETA> cnt;
+        static_assert(Cnt<P, L + BETA>::P == P && !Cnt<P, L + BETA>::OV, "the biased count fills exactly its planes");
+        cnt.ovf = 0u;
+        plane_sum_columns_biased<0, P, L + BETA, L, BETA == 1>(Z + C, cnt);
+        /* up: Z[C+L], Z[C+L+1] enter, Z[C], Z[C+1] leave; down: Z[C-1], Z[C-2] enter, Z[C+L-1], Z[C+L-2] leave */
+        const uint32_t pu = lop3<TT_A_ANDN_B>(Z[C + L + 1], Z[C + 1], Z[C + 1]);
+        const uint32_t m1u = lop3<TT_UP_OR_LEVEL_C>(Z[C + L], Z[C], pu);
+        const uint32_t m2u = lop3<TT_A_ANDN_B_C>(Z[C + L], Z[C], pu);
+        const uint32_t pd = lop3<TT_A_ANDN_B>(Z[C - 2], Z[C + L - 2], Z[C + L - 2]);
+        const uint32_t m1d = lop3<TT_UP_OR_LEVEL_C>(Z[C - 1], Z[C + L - 1], pd);
+        const uint32_t m2d = lop3<TT_A_ANDN_B_C>(Z[C - 1], Z[C + L - 1], pd);
+        const uint32_t u = lop3<TT_AB_AND_C>(m1u, m1d, cnt.b[0]);
+        uint32_t x = lop3<TT_OR3>(m2u, m2d, u);
+        /* the planes between plane 0 and the top one, two at a time */
+#pragma unroll
+        for (int i = 1; i + 1 <= P - 2; i += 2) x = lop3<TT_AND3>(cnt.b[i], cnt.b[i + 1], x);
+        if constexpr ((P - 2) % 2 == 1) x &= cnt.b[P - 2];
+        any[g] = lop3<TT_AB_AND_C>(cnt.b[P - 1], x, AVg[g]);
+    }
+}
+
 /* ------------------------------------------------------------------ tables */
 /* Word w of a ROW SEGMENT plane.  Segment base i = b*W + w is sequence position s0 + i.
  * plane 0/1: hi/lo bit of the base code (0 beyond the end of the sequence);

@@ -38,9 +38,15 @@ constexpr int BS_CAP = BS_TRIP + 64;
 #define GKM_BS_PACKED_WAVES 6 /* the several-pieces variants (ragged lengths): compiled for 6 they come out at 72 VGPRs and run 7 */
 #endif
 #ifndef GKM_BS_CROSSINGS_MIDDLE
-#define GKM_BS_CROSSINGS_MIDDLE 1 /* the shift-record variants' counting loop (gkm_bitslice.h window_group_any_crossings): 1 = the first
-                                     window in the middle of the shift, two chains (106 VALU per shift at L = 11, 69-71 VGPRs); 0 = one
-                                     chain from word 0 (111): profiles/r15_kernel_ab_crossings.txt has both */
+#define GKM_BS_CROSSINGS_MIDDLE 1 /* the crossings loop (gkm_bitslice.h window_group_any_crossings; round 15's counting loop of the shift-record
+                                     variants, built with -DGKM_BS_CENTRES=0 since): 1 = the first window in the middle of the shift, two
+                                     chains (106 VALU per shift at L = 11, 69-71 VGPRs); 0 = one chain from word 0 (111):
+                                     profiles/r15_kernel_ab_crossings.txt has both */
+#endif
+#ifndef GKM_BS_CENTRES
+#define GKM_BS_CENTRES 1 /* the shift-record variants' counting loop: 1 = no counter at all, each group from its centre window's exact
+                            count and the two steps either side of it (gkm_bitslice.h window_group_any_centres: 88 VALU per shift at
+                            L = 11); 0 = the crossings loop above (106): profiles/r16_kernel_ab_centres.txt has both */
 #endif
 #ifndef GKM_TRIP_PRIO
 #define GKM_TRIP_PRIO 3 /* wave priority (s_setprio, 0..3) inside a trip; 0 = as rounds 1-3 */
@@ -486,7 +492,9 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : (PK >= 4 && PK <= 7) ? GKM_BS_WAVES
                         /* per group the OR of its words' hits, straight from the count (gkm_bitslice.h: where the bias
                          * allows, the top plane of a count of matches -- one op per word for threshold, validity and OR) */
                         uint32_t grp_any[W / BS_GRP];
-                        if constexpr (GROUP_VALID && SHIFTREC) /* the same words as the next entry, the top plane never stepped */
+                        if constexpr (GROUP_VALID && SHIFTREC && GKM_BS_CENTRES != 0) /* the same words as the next two entries, no counter stepped */
+                            window_group_any_centres<W, L, D, BS_GRP>(Ahi, Alo, AVg, bh + u, bl + u, grp_any);
+                        else if constexpr (GROUP_VALID && SHIFTREC) /* the same words as the next entry, the top plane never stepped */
                             window_group_any_crossings<W, L, D, BS_GRP, GKM_BS_CROSSINGS_MIDDLE != 0>(Ahi, Alo, AVg, bh + u, bl + u, grp_any);
                         else if constexpr (GROUP_VALID) /* a superset per group: see AVg above */
                             window_group_any_grouped<W, L, D, BS_GRP>(Ahi, Alo, AVg, bh + u, bl + u, grp_any);

@@ -141,11 +141,15 @@ def analyse(obj, kernel, du):
         in_trip.update(range(j, k + 1))
     trip = lines[copies[0][0]:copies[0][1] + 1] if copies else []
     # the counting loop: the loop over blocks of `du` shifts -- the smallest loop body that holds the scalar loads of the
-    # column words and (trips taken out) more than 80 v_bitop3_b32 per shift
+    # column words and (trips taken out) exactly one block's push sites: a hit compaction (v_mbcnt_lo) per shift with shift
+    # records (PK = 6, 7), one per group of five words -- two per shift -- with group records.  (Until round 15 the test was
+    # "at least 60 v_bitop3_b32 per shift", which the counter-free loop of round 16 no longer has; a sub-loop that the
+    # compiler forms over some of the block's shifts holds fewer push sites and no scalar loads.)
+    pushes = du * (1 if kernel[3] in (6, 7) else 2)
     nshift, rest = None, None
     for b0, b1 in reversed(loops(lines, disassemble.addrs)):          # innermost first
         body = [x for i, x in enumerate(lines[b0:b1 + 1], b0) if i not in in_trip]
-        if sum(x.startswith("v_bitop3_b32") for x in body) >= 60 * du and any(x.startswith("s_load_dwordx") for x in body):
+        if sum(x.startswith("v_mbcnt_lo") for x in body) == pushes and any(x.startswith("s_load_dwordx") for x in body):
             nshift, rest = du, body
             break
     if rest is None:      # no loop found: everything outside the trips, an upper bound
