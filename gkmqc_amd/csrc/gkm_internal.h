@@ -29,6 +29,9 @@
  *                          a stable radix sort of the window starts (k_nullidx_keys, k_nullidx_hist, k_nix_*,
  *                          k_nullidx_digits, k_nullidx_scatter), gkmhip_nullidx_keys, gkmhip_nullidx_cells,
  *                          gkmhip_nullidx_sort, gkmhip_nullidx_tile, gkmhip_nullidx_scratch_bytes; needs no context
+ *   gkm_panel.hip          l-mer weight panels: up to 64 interleaved tables served by one lookup per l-mer, the lanes across
+ *                          models (k_panel_score, k_panel_scan_score, k_panel_delta_variants, k_panel_delta_sat),
+ *                          gkmhip_panel_score, gkmhip_panel_scan_score, gkmhip_panel_delta_variants, gkmhip_panel_delta_sat
  */
 #ifndef GKM_INTERNAL_H
 #define GKM_INTERNAL_H

@@ -147,6 +147,15 @@ def load():
     L.gkmhip_delta_sat.argtypes = (vp, vp, i64, i64, i64, vp, vp, vp)
     L.gkmhip_delta_variants.restype = i32
     L.gkmhip_delta_variants.argtypes = (vp, vp, vp, i64, vp, i32, vp, i64, vp, vp, vp)
+    if hasattr(L, "gkmhip_panel_score"):   # (older builds loaded through GKM_LIB_PATH for A/B timing lack them)
+        L.gkmhip_panel_score.restype = i32
+        L.gkmhip_panel_score.argtypes = (vp, i32, i32, vp, i32, i32, vp, vp)
+        L.gkmhip_panel_scan_score.restype = i32
+        L.gkmhip_panel_scan_score.argtypes = (vp, vp, i64, vp, i32, i32, i64, vp, i32, i32, vp, vp)
+        L.gkmhip_panel_delta_sat.restype = i32
+        L.gkmhip_panel_delta_sat.argtypes = (vp, vp, i64, i64, i64, vp, i32, i32, vp, vp)
+        L.gkmhip_panel_delta_variants.restype = i32
+        L.gkmhip_panel_delta_variants.argtypes = (vp, vp, vp, i64, vp, i32, vp, i64, vp, i32, i32, vp, vp)
     L.gkmhip_nullidx_tile.restype = i32
     L.gkmhip_nullidx_tile.argtypes = ()
     L.gkmhip_nullidx_scratch_bytes.restype = i64
@@ -568,6 +577,31 @@ class GramContext:
         self._chk(self.lib.gkmhip_delta_variants(self.handle, lm_ptr, codes_ptr, int(nbases), var.ctypes.data, len(var),
                                                  alt.ctypes.data if len(alt) else None, len(alt), W_ptr, out_ptr, stream),
                   "gkmhip_delta_variants")
+
+    # l-mer weight panels (include/gkm_hip.h, gkm_panel.hip): P_ptr = 4^L rows of `ms` device doubles, the first `nm` of a
+    # row the models' weights; the model index is the last axis of every output
+    def panel_score(self, col_begin, col_end, P_ptr, nm, ms, out_ptr, stream=0):
+        """lmer_score for every model of a panel -> out_ptr, (col_end - col_begin) x nm doubles (gkmhip_panel_score)."""
+        self._chk(self.lib.gkmhip_panel_score(self.handle, int(col_begin), int(col_end), P_ptr, int(nm), int(ms), out_ptr,
+                                              stream), "gkmhip_panel_score")
+
+    def panel_scan_score(self, lm_ptr, nlm, wt_ptr, width, stride, nwin, P_ptr, nm, ms, out_ptr, stream=0):
+        """scan_score for every model of a panel -> out_ptr, nwin x nm doubles (gkmhip_panel_scan_score)."""
+        self._chk(self.lib.gkmhip_panel_scan_score(self.handle, lm_ptr, int(nlm), wt_ptr, int(width), int(stride), int(nwin),
+                                                   P_ptr, int(nm), int(ms), out_ptr, stream), "gkmhip_panel_scan_score")
+
+    def panel_delta_sat(self, lm_ptr, nlm, t_begin, t_end, P_ptr, nm, ms, out_ptr, stream=0):
+        """delta_sat for every model of a panel -> out_ptr, (t_end - t_begin) x 4 x nm doubles (gkmhip_panel_delta_sat)."""
+        self._chk(self.lib.gkmhip_panel_delta_sat(self.handle, lm_ptr, int(nlm), int(t_begin), int(t_end), P_ptr, int(nm),
+                                                  int(ms), out_ptr, stream), "gkmhip_panel_delta_sat")
+
+    def panel_delta_variants(self, lm_ptr, codes_ptr, nbases, var, alt, P_ptr, nm, ms, out_ptr, stream=0):
+        """delta_variants for every model of a panel -> out_ptr, len(var) x nm doubles (gkmhip_panel_delta_variants)."""
+        var = np.ascontiguousarray(var, dtype=np.int32).reshape(-1, 4)
+        alt = np.ascontiguousarray(alt, dtype=np.uint8)
+        self._chk(self.lib.gkmhip_panel_delta_variants(self.handle, lm_ptr, codes_ptr, int(nbases), var.ctypes.data, len(var),
+                                                       alt.ctypes.data if len(alt) else None, len(alt), P_ptr, int(nm),
+                                                       int(ms), out_ptr, stream), "gkmhip_panel_delta_variants")
 
     def self_norms(self, sq_ptr, stream=0):
         self._chk(self.lib.gkmhip_self_norms(self.handle, sq_ptr, stream), "gkmhip_self_norms")

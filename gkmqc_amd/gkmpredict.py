@@ -1622,21 +1622,29 @@ def delta(table, fasta_or_sequences, variants, device=0, chunk=None, on_chunk=No
     chunk: bases per device chunk (default_delta_chunk).  on_chunk(dict) (measurements): called after every chunk with
     its variants, bases, k_delta_variants' milliseconds (HIP events), its gathers and the chunk's wall time."""
     check_delta(table, chunk=chunk)
+    return _delta_values(table, (), lambda: table.W, lambda ctx, *args: ctx.delta_variants(*args), fasta_or_sequences,
+                         variants, device, chunk, on_chunk)
+
+
+def _delta_values(folded, cols, weights, launch, fasta_or_sequences, variants, device, chunk, on_chunk):
+    """The body `delta` and `delta_with_panel` share: the variants resolved, sorted and checked once, then one launch per
+    chunk -> float64 (len(variants),) + cols.  folded: the table or panel (checked), for L and the context; weights(): the
+    host array the launches read; launch(ctx, lm_ptr, codes_ptr, nbases, var, alt, W_ptr, out_ptr, stream)."""
     variants = list(variants)
     records = _as_scan_records(fasta_or_sequences)
     rec, pos, rlen, alts = _resolve_variants(records, variants)
-    out = np.empty(len(variants))
+    out = np.empty((len(variants),) + cols)
     if not len(variants):
         return out
     import torch
-    L = table.L
+    L = folded.L
     chunk = int(chunk) if chunk else default_delta_chunk()
     alen = np.fromiter((len(a) for a in alts), dtype=np.int64, count=len(alts))
-    ctx = dv.cached_context(*table.kernel_params(), device=device)
+    ctx = dv.cached_context(*folded.kernel_params(), device=device)
     dev = torch.device("cuda", device)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
-        W = torch.from_numpy(table.W).to(dev)
+        W = torch.from_numpy(weights()).to(dev)
         for j in np.unique(rec).tolist():
             _, codes, valid = records[j]
             T = len(codes)
@@ -1654,14 +1662,17 @@ def delta(table, fasta_or_sequences, variants, device=0, chunk=None, on_chunk=No
                 var[:, 0], var[:, 1], var[:, 3] = pos[mine] - b0, rlen[mine], alen[mine]
                 var[:, 2] = np.cumsum(alen[mine]) - alen[mine]
                 alt = np.frombuffer(b"".join([alts[i] for i in mine.tolist()]), dtype=np.uint8)
-                d_out = torch.empty(len(mine), dtype=torch.float64, device=dev)
-                ctx.delta_variants(lm.data_ptr() if lm is not None else None, d_codes.data_ptr(), b1 - b0, var, alt,
-                                   W.data_ptr(), d_out.data_ptr(), stream)
-                out[mine] = np.where(ok[v0:v1], d_out.cpu().numpy(), np.nan)
+                d_out = torch.empty((len(mine),) + cols, dtype=torch.float64, device=dev)
+                launch(ctx, lm.data_ptr() if lm is not None else None, d_codes.data_ptr(), b1 - b0, var, alt,
+                       W.data_ptr(), d_out.data_ptr(), stream)
+                out[mine] = np.where(ok[v0:v1].reshape((-1,) + (1,) * len(cols)), d_out.cpu().numpy(), np.nan)
                 if on_chunk is not None:
-                    on_chunk(dict(variants=len(mine), bases=b1 - b0, kernel_ms=ctx.last_kernel_ms(),
-                                  gathers=ctx.last_comparisons(), kernel=ctx.last_kernel_name(),
-                                  wall_ms=(time.perf_counter() - t0) * 1e3))
+                    info = dict(variants=len(mine), bases=b1 - b0, kernel_ms=ctx.last_kernel_ms(),
+                                gathers=ctx.last_comparisons(), kernel=ctx.last_kernel_name(),
+                                wall_ms=(time.perf_counter() - t0) * 1e3)
+                    if cols:
+                        info["models"] = cols[0]
+                    on_chunk(info)
     return out
 
 
@@ -1779,6 +1790,376 @@ def read_saturation(path):
     return out
 
 
+# ------------------------------------------------------------------ l-mer weight panels
+PANEL_FORMAT = "gkmqc-lmer-panel-1"
+PANEL_MAX_MODELS = 64           # models of a panel (GKMHIP_PANEL_MAX): one wave's lanes across the models of a row
+PANEL_MAX_BYTES = 8 << 30       # the device image 4^L * ms * 8 of a panel, at most: 64 models at L = 12 just fit
+_PANEL_SHARED = ("kernel_type", "L", "k", "d", "M", "H")
+_PANEL_INTS = ("kernel_type", "L", "k", "d", "M")
+_PANEL_KEYS = ("format",) + _PANEL_SHARED + ("names", "rho", "W")
+
+
+def panel_row_stride(n_models):
+    """Doubles per row of a panel's device image: n_models rounded up to a multiple of 8 (rows of whole 64-byte lines)."""
+    return (int(n_models) + 7) // 8 * 8
+
+
+def _check_panel_names(names, n_models):
+    names = list(names)
+    if len(names) != n_models:
+        raise ModelError("panel: %d names for %d members" % (len(names), n_models))
+    for i, name in enumerate(names):
+        if not isinstance(name, str) or not name or "\t" in name or "\n" in name:
+            raise ModelError("panel: the name of member %d must be a non-empty string without tab or newline: %r"
+                             % (i, name))
+        if name in names[:i]:
+            raise ModelError("panel: the name %r is given to members %d and %d" % (name, names.index(name), i))
+    return names
+
+
+def _check_panel_size(L, n_models):
+    """The refusals that precede every allocation of a panel: the number of members and the bytes of the device image."""
+    if not 1 <= n_models <= PANEL_MAX_MODELS:
+        raise ModelError("panel: %d members; a panel holds 1..%d tables" % (n_models, PANEL_MAX_MODELS))
+    size = 4 ** int(L) * panel_row_stride(n_models) * 8
+    if size > PANEL_MAX_BYTES:
+        raise ModelError("panel: %d tables of L = %d take %d bytes on the device, above PANEL_MAX_BYTES = %d"
+                         % (n_models, L, size, PANEL_MAX_BYTES))
+
+
+class LmerPanel(_FoldedModel):
+    """1..64 l-mer weight tables that share (kernel_type, L, k, d, M, H), served together: W (float64,
+    (4^L, n_models), C-contiguous: column m is table m's W), rho (n_models,), names (unique).  n_models is the panel
+    size; M stays the wgkm distance parameter."""
+
+    def __init__(self, tables, names=None):
+        tables = list(tables)
+        for i, t in enumerate(tables):
+            if not isinstance(t, LmerTable):
+                raise ModelError("panel: member %d is no l-mer weight table (gkmpredict weights)" % i)
+        if not tables:
+            raise ModelError("panel: 0 members; a panel holds 1..%d tables" % PANEL_MAX_MODELS)
+        names = _check_panel_names(["table%d" % i for i in range(len(tables))] if names is None else names, len(tables))
+        for i, t in enumerate(tables):
+            check_table_model(t, "panel: member %d (%s)" % (i, names[i]))
+            for key in _PANEL_SHARED:
+                if getattr(t, key) != getattr(tables[0], key):
+                    raise ModelError("panel: member %d (%s) has %s = %r where member 0 (%s) has %r; the members must share %s"
+                                     % (i, names[i], key, getattr(t, key), names[0], getattr(tables[0], key),
+                                        ", ".join(_PANEL_SHARED)))
+        _check_panel_size(tables[0].L, len(tables))
+        self._fill(np.stack([t.W for t in tables], axis=1), names, [t.rho for t in tables],
+                   *(getattr(tables[0], key) for key in _PANEL_SHARED))
+
+    def _fill(self, W, names, rho, kernel_type, L, k, d, M, H):
+        self._set_params("panel", kernel_type, L, k, d, M, H, 0.0)
+        self.names, self.n_models = list(names), len(names)
+        self.rho = np.ascontiguousarray(rho, dtype=np.float64)
+        self.W = np.ascontiguousarray(W, dtype=np.float64)
+        if self.rho.shape != (self.n_models,) or not np.isfinite(self.rho).all():
+            raise ModelError("panel: rho must be %d finite values" % self.n_models)
+        if self.W.shape != (4 ** self.L, self.n_models):
+            raise ModelError("panel: W must be (4^L, n_models) = (%d, %d)" % (4 ** self.L, self.n_models))
+
+    def table(self, m):
+        """Member m as an LmerTable of its own (a copy of its column)."""
+        return LmerTable(self.W[:, m], self.kernel_type, self.L, self.k, self.d, self.M, self.H, float(self.rho[m]))
+
+    def device_rows(self):
+        """The device image: float64 (4^L, ms), ms = panel_row_stride(n_models); columns n_models.. are zero.  W itself
+        (no copy; read only) where n_models is a multiple of 8."""
+        if panel_row_stride(self.n_models) == self.n_models:
+            return self.W
+        P = np.zeros((4 ** self.L, panel_row_stride(self.n_models)), dtype=np.float64)
+        P[:, :self.n_models] = self.W
+        return P
+
+    def save(self, path):
+        """Write the panel file (format: INTEGRATION.md §5b) to exactly `path`: an uncompressed .npz with the format tag,
+        the six shared parameters, names, rho and the rows of the canonical l-mers in ascending order (W[rc(u)] ==
+        W[u] gives the other half)."""
+        head = {key: np.int64(getattr(self, key)) for key in _PANEL_INTS}
+        tmp = path + ".tmp"
+        with open(tmp, "wb") as f:
+            np.savez(f, format=np.array(PANEL_FORMAT), H=np.float64(self.H), names=np.array(self.names, dtype=np.str_),
+                     rho=self.rho, W=self.W[canonical_codes(self.L)], **head)
+        os.replace(tmp, path)
+
+
+def load_lmer_panel(path):
+    """Read a panel file written by LmerPanel.save; anything malformed raises ModelError with the reason."""
+    with open(path, "rb") as f:
+        try:
+            with np.load(f, allow_pickle=False) as z:
+                got = {key: z[key] for key in z.files}
+        except Exception as e:   # (not a zip archive, a truncated member, a pickled object, ...)
+            raise ModelError("%s: not a panel file: %s" % (path, e))
+    missing = [key for key in _PANEL_KEYS if key not in got]
+    if missing:
+        raise ModelError("%s: missing key(s): %s" % (path, ", ".join(missing)))
+    extra = [key for key in got if key not in _PANEL_KEYS]
+    if extra:
+        raise ModelError("%s: key(s) %s do not belong to format %s" % (path, ", ".join(extra), PANEL_FORMAT))
+    fmt = got["format"]
+    if fmt.shape != () or fmt.dtype.kind != "U" or str(fmt) != PANEL_FORMAT:
+        raise ModelError("%s: format %r, expected %r" % (path, fmt.tolist(), PANEL_FORMAT))
+    val = {}
+    for key, kinds in [(key, "iu") for key in _PANEL_INTS] + [("H", "f")]:
+        if got[key].shape != () or got[key].dtype.kind not in kinds:
+            raise ModelError("%s: %s must be one %s" % (path, key, "integer" if kinds == "iu" else "float"))
+        val[key] = got[key].item()
+    L = val["L"]
+    bad = dv.check_parameters(val["kernel_type"], L, val["k"], val["d"])
+    if bad:
+        raise ModelError("%s: kernel parameters rejected: %s" % (path, bad))
+    names, rho, Wc = got["names"], got["rho"], got["W"]
+    if names.ndim != 1 or names.dtype.kind != "U":
+        raise ModelError("%s: names is %s %r, expected one string per member" % (path, names.dtype, names.shape))
+    n = len(names)
+    try:
+        _check_panel_size(L, n)
+        if rho.dtype != np.float64 or rho.shape != (n,):
+            raise ModelError("rho is %s %r, expected float64 (%d,): one per member" % (rho.dtype, rho.shape, n))
+        if not np.isfinite(rho).all():
+            raise ModelError("rho of member %d is not finite" % int(np.flatnonzero(~np.isfinite(rho))[0]))
+        can = canonical_codes(L)
+        if Wc.dtype != np.float64 or Wc.shape != (len(can), n):
+            raise ModelError("W is %s %r, expected float64 (%d, %d): one row per canonical l-mer of L = %d, one column per "
+                             "member" % (Wc.dtype, Wc.shape, len(can), n, L))
+        names = _check_panel_names(names.tolist(), n)
+        W = np.empty((4 ** L, n), dtype=np.float64)
+        W[lmer_rc(can, L)] = Wc
+        W[can] = Wc
+        panel = LmerPanel.__new__(LmerPanel)
+        panel._fill(W, names, rho, val["kernel_type"], L, val["k"], val["d"], val["M"], val["H"])
+    except ModelError as e:
+        raise ModelError("%s: %s" % (path, e))
+    return panel
+
+
+def check_panel(panel, what):
+    """What every panel function refuses first: a table or a model where a panel is needed."""
+    if not isinstance(panel, LmerPanel):
+        raise ModelError("%s: needs an l-mer weight panel (gkmpredict panel), not a table or a model" % what)
+    check_table_model(panel, what)
+
+
+def score_with_panel(panel, fasta_or_sequences, device=0, block=None, on_block=None):
+    """score_with_table for every member of a panel -> (names, scores (Q, n_models)): column m is score_with_table's
+    result for member m, bit for bit, whatever the block size.  Per block the exact self norms once (they depend on the
+    shared parameters only) and one k_panel_score launch: one row read per l-mer for all models.
+    on_block(dict) (measurements): score_with_table's keys and `models`."""
+    import torch
+    check_panel(panel, "predict-panel")
+    seqs, names = _as_queries(fasta_or_sequences)
+    check_queries(panel, seqs)
+    blocks = _Blocks(panel, seqs, device, block, default_table_block(_longest(seqs)), exact=True)
+    ctx, sq, dev = blocks.ctx, blocks.sq, blocks.dev
+    nm, ms = panel.n_models, panel_row_stride(panel.n_models)
+    out = np.empty((len(seqs), nm))
+    with torch.cuda.device(dev):
+        P = torch.from_numpy(panel.device_rows()).to(dev)
+        rho = torch.from_numpy(panel.rho).to(dev)
+        T = torch.empty((blocks.qb_max, nm), dtype=torch.float64, device=dev)
+        for b in blocks:
+            ctx.panel_score(0, b.qb, P.data_ptr(), nm, ms, T.data_ptr(), blocks.stream)
+            out[b.q0:b.q1] = (T[:b.qb] / sq[:b.qb, None] + rho[None, :]).cpu().numpy()
+            if on_block is not None:
+                on_block(dict(queries=b.qb, models=nm, score_kernel_ms=ctx.last_kernel_ms(), lmers=ctx.last_comparisons(),
+                              kernel=ctx.last_kernel_name(), wall_ms=(time.perf_counter() - b.t0) * 1e3))
+    return names, out
+
+
+def default_panel_scan_chunk(d, n_models, budget=BLOCK_BYTES):
+    """Bases per chunk of scan_with_panel: default_scan_chunk's bytes per base and the window's n_models doubles."""
+    return int(budget // (8 * (int(d) + 1) + 64 + 8 * int(n_models)))
+
+
+def check_panel_scan(panel, width, stride, chunk=None):
+    """What `scan_with_panel` refuses before it reads anything or touches the device (check_scan's refusals)."""
+    check_panel(panel, "scan-panel")
+    if int(width) < panel.L:
+        raise ModelError("scan-panel: the width %d is below L = %d" % (width, panel.L))
+    if int(width) > SCAN_MAX_WIDTH:
+        raise ModelError("scan-panel: the width %d is above %d, the longest sequence a score is defined for"
+                         % (width, SCAN_MAX_WIDTH))
+    if int(stride) < 1:
+        raise ModelError("scan-panel: the stride must be at least 1")
+    if chunk is not None and int(chunk) < int(width):
+        raise ModelError("scan-panel: a chunk must hold at least one window (%d bases)" % width)
+
+
+def scan_with_panel(panel, fasta_or_sequences, width, stride=1, device=0, chunk=None, on_chunk=None):
+    """`scan` for every member of a panel -> [(name, starts, scores (windows, n_models))]: column m is scan's result for
+    member m, bit for bit, whatever `chunk` and whatever precedes the record; a window over a character other than A, C,
+    G, T is NaN in every column.  Per chunk the l-mer words and the windows' self profiles once (k_scan_profiles, the
+    hot kernel of a scan, depends on the shared parameters only), then one k_panel_scan_score launch.
+    chunk: bases per device chunk (default_panel_scan_chunk).  on_chunk(dict) (measurements): scan's keys, `models`,
+    `score_kernel` and `score_kernel_ms`."""
+    check_panel_scan(panel, width, stride, chunk)
+    width, stride = int(width), int(stride)
+    records = _as_scan_records(fasta_or_sequences)
+    if not any(len(codes) >= width for _, codes, _ in records):
+        raise ModelError("scan-panel: no record holds a window of %d bases" % width)
+    import torch
+    L, d, nm, ms = panel.L, panel.d, panel.n_models, panel_row_stride(panel.n_models)
+    chunk = int(chunk) if chunk else default_panel_scan_chunk(d, nm)
+    ctx = dv.cached_context(*panel.kernel_params(), device=device)
+    dev = torch.device("cuda", device)
+    c = dv.mismatch_weights(panel.kernel_type, L, panel.k)[:d + 1]
+    wt = dv.position_weights(panel.kernel_type, width - L + 1, panel.M, panel.H)
+    out = []
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        P = torch.from_numpy(panel.device_rows()).to(dev)
+        rho = torch.from_numpy(panel.rho).to(dev)
+        d_wt = torch.from_numpy(wt).to(dev)
+        for name, codes, valid in records:
+            nw = scan_window_count(len(codes), width, stride)
+            scores = np.empty((nw, nm))
+            ok = window_validity(valid, width, stride)
+            for w0, w1, b0, b1 in scan_chunk_plan(len(codes), width, stride, chunk):
+                t0 = time.perf_counter()
+                d_codes = torch.from_numpy(codes[b0:b1]).to(dev)
+                d_valid = torch.from_numpy(valid[b0:b1].view(np.uint8)).to(dev)
+                nlm, nwin = b1 - b0 - L + 1, w1 - w0
+                lm = torch.empty(nlm, dtype=torch.int32, device=dev)
+                ctx.scan_lmers(d_codes.data_ptr(), d_valid.data_ptr(), b1 - b0, lm.data_ptr(), stream)
+                prof = torch.empty((nwin, d + 1), dtype=torch.int64, device=dev)
+                ctx.scan_profiles(lm.data_ptr(), nlm, d_wt.data_ptr(), width, stride, nwin, prof.data_ptr(), stream)
+                if on_chunk is not None:
+                    info = dict(windows=nwin, bases=b1 - b0, models=nm, profile_kernel_ms=ctx.last_kernel_ms(),
+                                comparisons=ctx.last_comparisons(), kernel=ctx.last_kernel_name())
+                T = torch.empty((nwin, nm), dtype=torch.float64, device=dev)
+                ctx.panel_scan_score(lm.data_ptr(), nlm, d_wt.data_ptr(), width, stride, nwin, P.data_ptr(), nm, ms,
+                                     T.data_ptr(), stream)
+                if on_chunk is not None:
+                    info.update(score_kernel=ctx.last_kernel_name(), score_kernel_ms=ctx.last_kernel_ms())
+                sq = _norms_from_profiles(prof, c)
+                scores[w0:w1] = (T / sq[:, None] + rho[None, :]).cpu().numpy()
+                if on_chunk is not None:
+                    info["wall_ms"] = (time.perf_counter() - t0) * 1e3
+                    on_chunk(info)
+            scores[~ok] = np.nan
+            out.append((name, np.arange(nw, dtype=np.int64) * stride, scores))
+    return out
+
+
+def check_panel_delta(panel, variants=None, records=None, chunk=None):
+    """What `delta_with_panel` and `delta_saturation_with_panel` refuse before they touch the device (check_delta's
+    refusals)."""
+    check_panel(panel, "delta-panel")
+    if chunk is not None and int(chunk) < delta_min_chunk(panel.L):
+        raise ModelError("delta-panel: a chunk must hold a variant's context (at least %d bases for L = %d)"
+                         % (delta_min_chunk(panel.L), panel.L))
+    if variants is not None:
+        _resolve_variants(records, list(variants), match=False)
+
+
+def delta_with_panel(panel, fasta_or_sequences, variants, device=0, chunk=None, on_chunk=None):
+    """`delta` for every member of a panel -> float64 (len(variants), n_models): column m is delta's result for member m,
+    bit for bit (NaN in every column where the context holds a character other than A, C, G, T; +0.0 where the alleles
+    are the same).  The variants are resolved, sorted and checked once -- most of delta's time -- and each chunk is one
+    k_panel_delta_variants launch.  on_chunk(dict) (measurements): delta's keys and `models`."""
+    check_panel_delta(panel, chunk=chunk)
+    nm, ms = panel.n_models, panel_row_stride(panel.n_models)
+    return _delta_values(panel, (nm,), panel.device_rows,
+                         lambda ctx, lm, codes, nbases, var, alt, P, out, stream:
+                         ctx.panel_delta_variants(lm, codes, nbases, var, alt, P, nm, ms, out, stream),
+                         fasta_or_sequences, variants, device, chunk, on_chunk)
+
+
+def delta_saturation_with_panel(panel, fasta_or_sequences, device=0, chunk=None, on_chunk=None):
+    """`delta_saturation` for every member of a panel -> [(name, (T, 4, n_models) float64)]: [:, :, m] is
+    delta_saturation's map for member m, bit for bit, and D[t, b, m] is delta_with_panel's value of that SNV.
+    on_chunk(dict) (measurements): delta_saturation's keys and `models`."""
+    check_panel_delta(panel, chunk=chunk)
+    records = _as_scan_records(fasta_or_sequences)
+    L, nm, ms = panel.L, panel.n_models, panel_row_stride(panel.n_models)
+    for name, codes, _ in records:
+        if len(codes) < L:
+            raise ModelError("delta-saturation: record %r has %d bases, fewer than L = %d" % (name, len(codes), L))
+    import torch
+    chunk = int(chunk) if chunk else max(delta_min_chunk(L), int(BLOCK_BYTES // (16 + 32 * nm)))
+    ctx = dv.cached_context(*panel.kernel_params(), device=device)
+    dev = torch.device("cuda", device)
+    out = []
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        P = torch.from_numpy(panel.device_rows()).to(dev)
+        for name, codes, valid in records:
+            T = len(codes)
+            D = np.empty((T, 4, nm))
+            for t0, t1, b0, b1 in delta_saturation_chunk_plan(T, L, chunk):
+                w0 = time.perf_counter()
+                _, lm = _delta_upload(ctx, codes, valid, b0, b1, L, dev, stream)
+                d_out = torch.empty((t1 - t0, 4, nm), dtype=torch.float64, device=dev)
+                ctx.panel_delta_sat(lm.data_ptr(), len(lm), t0 - b0, t1 - b0, P.data_ptr(), nm, ms, d_out.data_ptr(), stream)
+                D[t0:t1] = d_out.cpu().numpy()
+                if on_chunk is not None:
+                    on_chunk(dict(positions=t1 - t0, bases=b1 - b0, models=nm, kernel_ms=ctx.last_kernel_ms(),
+                                  gathers=ctx.last_comparisons(), kernel=ctx.last_kernel_name(),
+                                  wall_ms=(time.perf_counter() - w0) * 1e3))
+            out.append((name, D))
+    return out
+
+
+def _panel_row(lead, values):
+    return "\t".join(lead + ["nan" if x != x else "%.17g" % x for x in values]) + "\n"
+
+
+def write_panel_scores(path, panel_names, names, scores):
+    """The `predict-panel` output: the header #name<TAB>member names, then name<TAB>one score per member at %.17g."""
+    with open(path, "w") as f:
+        f.write("#" + "\t".join(["name"] + list(panel_names)) + "\n")
+        for name, row in zip(names, np.asarray(scores, dtype=np.float64).tolist()):
+            f.write(_panel_row([str(name)], row))
+
+
+def write_panel_scan(path, panel_names, results, width):
+    """The `scan-panel` output: the header #name<TAB>start<TAB>end<TAB>member names, then `scan`'s leading columns and
+    one score per member at %.17g; windows without a score (NaN) are left out.  -> how many were left out."""
+    omitted = 0
+    with open(path, "w") as f:
+        f.write("#" + "\t".join(["name", "start", "end"] + list(panel_names)) + "\n")
+        for name, starts, scores in results:
+            keep = ~np.isnan(scores).any(axis=1)
+            omitted += int((~keep).sum())
+            for i in range(0, len(starts), 1 << 14):
+                k = keep[i:i + (1 << 14)]
+                f.write("".join(_panel_row([name, "%d" % a, "%d" % (a + width)], row) for a, row in
+                                zip(starts[i:i + (1 << 14)][k].tolist(), scores[i:i + (1 << 14)][k].tolist())))
+    return omitted
+
+
+def write_panel_delta(path, panel_names, variants, values):
+    """The `delta-panel` output: the header #name<TAB>pos<TAB>ref<TAB>alt[<TAB>id]<TAB>member names (id when the first
+    variant carries one), then write_delta's leading columns and one delta per member at %.17g, nan where there is none."""
+    with open(path, "w") as f:
+        lead = ["name", "pos", "ref", "alt"] + (["id"] if len(variants) and len(variants[0]) > 4 else [])
+        f.write("#" + "\t".join(lead + list(panel_names)) + "\n")
+        for v, row in zip(variants, np.asarray(values, dtype=np.float64).tolist()):
+            f.write(_panel_row([str(v[0]), "%d" % (int(v[1]) + 1), v[2] or ".", v[3] or "."] + [str(c) for c in v[4:5]],
+                               row))
+
+
+def read_panel_output(path, nlead):
+    """-> (member names, [the nlead leading columns of each row], float64 (rows, n_models)) from a file written by
+    write_panel_scores (nlead = 1), write_panel_scan (3) or write_panel_delta (4, or 5 with ids)."""
+    with open(path) as f:
+        lines = f.read().split("\n")[:-1]
+    if not lines or not lines[0].startswith("#"):
+        raise ModelError("%s: no header line" % path)
+    head = lines[0][1:].split("\t")
+    leads, values = [], []
+    nm = len(head) - int(nlead)
+    for line in lines[1:]:
+        fields = line.split("\t")
+        leads.append(tuple(fields[:-nm]))
+        values.append([float(x) for x in fields[-nm:]])
+    return head[nlead:], leads, np.array(values, dtype=np.float64).reshape(len(values), nm)
+
+
 # ------------------------------------------------------------------ command line
 def _add_train_options(p, svr):
     p.add_argument("-t", "--kernel-type", type=int, default=4, help="kernel type 0..5 (default: 4)")
@@ -1860,7 +2241,33 @@ def build_parser():
                                                 "<TAB>dT per position, positions near a non-ACGT character left out")
     s.add_argument("--chunk", type=int, default=None, help="bases per device chunk (default: from device memory)")
     _add_arguments(s, "weights", "seqs_fa", "output", block=False)
+    pn = sub.add_parser("panel", help="join 1..64 l-mer weight tables that share their kernel parameters into a panel, a "
+                                      "binary .npz file; the members are named after the files")
+    pn.add_argument("--names", default=None, help="comma-separated member names (default: the files' basenames)")
+    pn.add_argument("output")
+    pn.add_argument("weights", nargs="+")
+    pp = sub.add_parser("predict-panel", help="score the sequences of query.fa with every member of a panel: a header, "
+                                              "then name<TAB>one score per member")
+    _add_arguments(pp, "query_fa", "panel", "output")
+    ps = sub.add_parser("scan-panel", help="scan the sequences of seqs.fa with every member of a panel: a header, then "
+                                           "name<TAB>start<TAB>end<TAB>one score per member")
+    ps.add_argument("--width", type=int, required=True, help="bases per window (L..2047)")
+    ps.add_argument("--stride", type=int, default=1, help="bases between window starts (default: 1)")
+    ps.add_argument("--chunk", type=int, default=None, help="bases per device chunk (default: from device memory)")
+    _add_arguments(ps, "seqs_fa", "panel", "output", block=False)
+    pd = sub.add_parser("delta-panel", help="the effect of the variants of variants.tsv on the sequences of seqs.fa for "
+                                            "every member of a panel: a header, then the variant's columns and one delta "
+                                            "per member")
+    pd.add_argument("--chunk", type=int, default=None, help="bases per device chunk (default: from device memory)")
+    _add_arguments(pd, "seqs_fa", "variants", "panel", "output", block=False)
     return p
+
+
+def panel_member_names(paths, names=None):
+    """The member names of `panel`: --names split at commas, or the weight files' basenames."""
+    if names is None:
+        return [os.path.basename(path) for path in paths]
+    return names.split(",")
 
 
 def check_train_args(a):
@@ -1962,6 +2369,41 @@ def main(argv=None):
                 os.replace(tmp, a.output)
                 print("%d positions scored, %d near a non-ACGT character left out -> %s"
                       % (sum(len(r[1]) for r in results) - omitted, omitted, a.output), file=sys.stderr)
+        elif a.cmd == "panel":
+            names = panel_member_names(a.weights, a.names)
+            if len(names) != len(a.weights):
+                raise ModelError("panel: %d names for %d weight files" % (len(names), len(a.weights)))
+            if len(a.weights) > PANEL_MAX_MODELS:
+                raise ModelError("panel: %d weight files; a panel holds 1..%d tables" % (len(a.weights), PANEL_MAX_MODELS))
+            LmerPanel([load_lmer_table(path) for path in a.weights], names).save(a.output)
+        elif a.cmd in ("predict-panel", "scan-panel", "delta-panel"):
+            if a.cmd == "predict-panel" and a.block is not None and a.block < 1:
+                raise ModelError("--block must be at least 1")
+            for path in [getattr(a, key) for key in ("query_fa", "seqs_fa", "variants") if hasattr(a, key)]:
+                if not os.path.isfile(path):
+                    raise ModelError("cannot read %s" % path)
+            panel = load_lmer_panel(a.panel)
+            tmp = a.output + ".tmp"
+            if a.cmd == "predict-panel":
+                names, values = score_with_panel(panel, a.query_fa, a.device, a.block)
+                write_panel_scores(tmp, panel.names, names, values)
+                os.replace(tmp, a.output)
+            elif a.cmd == "scan-panel":
+                check_panel_scan(panel, a.width, a.stride, a.chunk)
+                results = scan_with_panel(panel, a.seqs_fa, a.width, a.stride, a.device, a.chunk)
+                omitted = write_panel_scan(tmp, panel.names, results, a.width)
+                os.replace(tmp, a.output)
+                print("%d windows scored for %d models, %d over a non-ACGT character left out -> %s"
+                      % (sum(len(r[1]) for r in results) - omitted, panel.n_models, omitted, a.output), file=sys.stderr)
+            else:
+                check_panel_delta(panel, chunk=a.chunk)
+                variants = read_variants(a.variants)
+                values = delta_with_panel(panel, a.seqs_fa, variants, a.device, a.chunk)
+                write_panel_delta(tmp, panel.names, variants, values)
+                os.replace(tmp, a.output)
+                bad = int(np.isnan(values).any(axis=1).sum()) if len(values) else 0
+                print("%d variants scored for %d models, %d over a non-ACGT character (nan) -> %s"
+                      % (len(values) - bad, panel.n_models, bad, a.output), file=sys.stderr)
         else:
             compute, write = _QUERY_COMMANDS[a.cmd]
             if a.block is not None and a.block < 1:

@@ -323,6 +323,30 @@ int gkmhip_delta_sat(gkmhip_ctx *ctx, const uint32_t *lm, int64_t nlm, int64_t t
 int gkmhip_delta_variants(gkmhip_ctx *ctx, const uint32_t *lm, const uint8_t *codes, int64_t nbases, const int32_t *var,
                           int nvar, const uint8_t *alt, int64_t nalt, const double *W, double *out, void *stream);
 
+/* ---- l-mer weight panels: many tables per lookup (gkm_panel.hip) ----
+ * nm tables (1 <= nm <= GKMHIP_PANEL_MAX) that share the context's parameters, interleaved: P[u * ms + m] = W_m[u], DEVICE,
+ * 4^L rows of ms doubles, ms >= nm and ms % 8 == 0 (rows of whole 64-byte lines), what lies beyond column nm never
+ * surfaces.  Each call is its single-table counterpart for every model at once -- the same arguments, the same refusals
+ * (error 2; also for a null P, nm outside 1..64, ms < nm, ms % 8 != 0) -- with the model index as the last axis of the
+ * output, and for every m the value written is, bit for bit, what the counterpart writes for the table P[:, m]: the same
+ * order of additions per model, no atomics, nothing that depends on the launch.  last_comparisons: the ROWS looked up
+ * (the counterpart's count, not multiplied by nm); last_kernel_ms / last_kernel_name describe k_panel_score,
+ * k_panel_scan_score, k_panel_delta_sat and k_panel_delta_variants.
+ *   gkmhip_panel_score           out: (col_end - col_begin) x nm doubles   (gkmhip_lmer_score)
+ *   gkmhip_panel_scan_score      out: nwin x nm doubles                    (gkmhip_scan_score)
+ *   gkmhip_panel_delta_sat       out: (t_end - t_begin) x 4 x nm doubles   (gkmhip_delta_sat)
+ *   gkmhip_panel_delta_variants  out: nvar x nm doubles                    (gkmhip_delta_variants) */
+#define GKMHIP_PANEL_MAX 64
+int gkmhip_panel_score(gkmhip_ctx *ctx, int col_begin, int col_end, const double *P, int nm, int ms, double *out,
+                       void *stream);
+int gkmhip_panel_scan_score(gkmhip_ctx *ctx, const uint32_t *lm, int64_t nlm, const uint8_t *wt, int width, int stride,
+                            int64_t nwin, const double *P, int nm, int ms, double *out, void *stream);
+int gkmhip_panel_delta_sat(gkmhip_ctx *ctx, const uint32_t *lm, int64_t nlm, int64_t t_begin, int64_t t_end, const double *P,
+                           int nm, int ms, double *out, void *stream);
+int gkmhip_panel_delta_variants(gkmhip_ctx *ctx, const uint32_t *lm, const uint8_t *codes, int64_t nbases, const int32_t *var,
+                                int nvar, const uint8_t *alt, int64_t nalt, const double *P, int nm, int ms, double *out,
+                                void *stream);
+
 /* ---- the genome window index of null-sequence sampling (gkm_nullidx.hip) ----
  * One chromosome: seq = T raw FASTA bytes, line breaks removed, case kept; t = the window width, 1 <= t <= 2047.  Per byte:
  * na (one of nN), cg (one of cgCG), rp (one of acgt); any other byte sets none.  The windows are the starts i in
