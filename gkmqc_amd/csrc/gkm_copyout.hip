@@ -358,6 +358,7 @@ extern "C" int gkmhip_copy_lower_to_rows(gkmhip_ctx *ctx, const double *K, int64
                                          int nthreads)
 {
     if (!ctx || !K || !rows || n <= 0) return set_err_msg("gkmhip_copy_lower_to_rows: bad arguments", 2);
+    if (ld < n) return set_err_msg("gkmhip_copy_lower_to_rows: leading dimension too small", 2);
     HIPCHK(hipSetDevice(ctx->device));
     const size_t want = (size_t)64 << 20;
     double *stage[2];

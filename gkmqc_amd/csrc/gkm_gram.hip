@@ -668,6 +668,8 @@ extern "C" int gkmhip_gram_rows(gkmhip_ctx *ctx, const int *rows, int nrows, int
 {
     if (!G || !rows || nrows <= 0) return set_err_msg("gkmhip_gram_rows: bad arguments", 2);
     if (ld <= rows[nrows - 1]) return set_err_msg("leading dimension too small", 2);
+    /* (profile (r, j) sits at (r * ldp + j) * (d + 1): a smaller ldp would store rows over each other) */
+    if (P && ldp <= rows[nrows - 1]) return set_err_msg("leading dimension of the profiles too small", 2);
     GramOut out;
     out.G = G; out.ld = ld; out.P = P; out.ldp = ldp; out.local_rows = local_rows; out.write_all = 0; out.diag = nullptr; out.row_off = nullptr; out.col0 = 0;
     return gram_launch(ctx, rows, nrows, COLS_TRIANGLE, out, (hipStream_t)stream_);

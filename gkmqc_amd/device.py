@@ -336,6 +336,15 @@ def encode(seq):
 
 
 # ------------------------------------------------------------------ device layer
+def _row_pointers(host, n):
+    """The row-pointer table of the copy-out calls for a 2-D fp64 numpy array with at least n rows and n columns (rows
+    may be wider: the reference's caller hands in a larger matrix, scripts/gkmsvm.py:67-99)."""
+    if not (isinstance(host, np.ndarray) and host.ndim == 2 and host.dtype == np.float64 and host.flags.writeable
+            and host.strides[1] == 8 and host.strides[0] >= 8 * host.shape[1] and host.shape[0] >= n and host.shape[1] >= n):
+        raise GkmError("the host matrix must be a writeable 2-D fp64 array of at least n x n with unit column stride")
+    return (host.ctypes.data + np.arange(host.shape[0]) * host.strides[0]).astype(np.uintp)
+
+
 class GramContext:
     """Owns one gkmhip_ctx: parameters + uploaded sequences on one GPU."""
 
@@ -621,6 +630,26 @@ class GramContext:
         self._chk(self.lib.gkmhip_assemble_normalize(self.handle, slabs_ptr, lds, slot_ptr, K_ptr, ld, sq_ptr,
                                                      int(symmetric), stream), "gkmhip_assemble_normalize")
 
+    def copy_lower_to_rows(self, K_ptr, ld, n, host, nthreads=1):
+        """host[a, :a + 1] = K[a, :a + 1] for the n rows of a device matrix with leading dimension ld, through the pinned
+        staging pipeline; nothing else of `host` is written (include/gkm_hip.h gkmhip_copy_lower_to_rows).  The copies
+        run on a stream of the call's own: K must be complete."""
+        rows = _row_pointers(host, n)
+        self._chk(self.lib.gkmhip_copy_lower_to_rows(self.handle, K_ptr, int(ld), int(n), rows.ctypes.data, int(nthreads)),
+                  "gkmhip_copy_lower_to_rows")
+
+    def gram_to_host_rows(self, G_ptr, ld, host, nthreads=1, part=0, nparts=1):
+        """The whole normalised matrix of the uploaded sequences into host[a, :a + 1], G_ptr = device scratch of n x ld
+        doubles; nparts > 1: only the row blocks of context `part` of `nparts` (include/gkm_hip.h
+        gkmhip_gram_to_host_rows / gkmhip_gram_part_to_host_rows)."""
+        rows = _row_pointers(host, self.n)
+        if nparts == 1 and part == 0:
+            self._chk(self.lib.gkmhip_gram_to_host_rows(self.handle, G_ptr, int(ld), rows.ctypes.data, int(nthreads)),
+                      "gkmhip_gram_to_host_rows")
+        else:
+            self._chk(self.lib.gkmhip_gram_part_to_host_rows(self.handle, G_ptr, int(ld), rows.ctypes.data, int(nthreads),
+                                                             int(part), int(nparts)), "gkmhip_gram_part_to_host_rows")
+
     def last_kernel_ms(self):
         return self.lib.gkmhip_last_kernel_ms(self.handle)
 
@@ -836,13 +865,15 @@ def allgather_stats():
 
 
 def gram_matrix_multi(seqs, kernel_type, L, k, d, M=50, H=50.0, gamma=1.0, devices=(0,), symmetric=False, chunks=0,
-                      kernel=KERNEL_AUTO):
+                      kernel=KERNEL_AUTO, ld=None, out=None):
     """Whole Gram matrix computed on several GPUs by ONE process (include/gkm_hip.h,
     gkmhip_gram_allgather): rows sharded by folded row blocks, slabs all-gathered over xGMI (RCCL),
     every device ends up with the whole normalised matrix -- bit-identical to gram_matrix().
     `devices` may name a device more than once (rehearsal on a one-GPU box: peer copies instead of RCCL).
+    ld: the leading dimension of every device's matrix (default n); out: the matrices to write, one fp64 [n, ld] tensor
+    per entry of devices on that device (default: zeroed ones) -- columns n..ld-1 are left as they are.
 
-    Returns dict(K=[torch fp64 [n,n] per entry of devices], transport="rccl"|"p2p"|"none", ms=wall)."""
+    Returns dict(K=[torch fp64 [n,ld] per entry of devices], transport="rccl"|"p2p"|"none", ms=wall)."""
     import time
     import torch
     lib = load()
@@ -853,17 +884,23 @@ def gram_matrix_multi(seqs, kernel_type, L, k, d, M=50, H=50.0, gamma=1.0, devic
             c.set_kernel(kernel)
             ctxs.append(c)
         n = len(seqs)
+        ld = n if ld is None else int(ld)
+        if out is not None and (len(out) != len(devices) or any(
+                K.dtype != torch.float64 or tuple(K.shape) != (n, ld) or not K.is_contiguous() or K.device.index != dv
+                for K, dv in zip(out, devices))):
+            raise GkmError("out needs one contiguous fp64 [n, ld] tensor per entry of devices, on that device")
         Ks = []
-        for c, dv in zip(ctxs, devices):
+        for g, (c, dv) in enumerate(zip(ctxs, devices)):
             with torch.cuda.device(dv):
                 c.set_sequences(seqs, torch.cuda.current_stream().cuda_stream)
-                Ks.append(torch.zeros((n, n), dtype=torch.float64, device=torch.device("cuda", dv)))
+                Ks.append(out[g] if out is not None
+                          else torch.zeros((n, max(ld, 0)), dtype=torch.float64, device=torch.device("cuda", dv)))
         for dv in set(devices):
             torch.cuda.synchronize(dv)
         handles = (ctypes.c_void_p * len(ctxs))(*[c.handle for c in ctxs])
         outs = (ctypes.c_void_p * len(ctxs))(*[K.data_ptr() for K in Ks])
         t0 = time.perf_counter()
-        rc = lib.gkmhip_gram_allgather(handles, len(ctxs), outs, n, int(symmetric), int(chunks))
+        rc = lib.gkmhip_gram_allgather(handles, len(ctxs), outs, ld, int(symmetric), int(chunks))
         wall = time.perf_counter() - t0
         if rc:
             raise GkmError("gkmhip_gram_allgather failed (%d): %s" % (rc, lib.gkmhip_last_error().decode()))

@@ -83,7 +83,8 @@ int gkmhip_set_sequences(gkmhip_ctx *ctx, int n, const uint8_t *codes, const int
  * indices): row rows[i] is written to G + i*ld (local_rows != 0) or to
  * G + rows[i]*ld (local_rows == 0).  `G` is a DEVICE pointer.  If P != NULL (device,
  * int32) the integer mismatch profiles are stored as P[(i_or_row*ldp + j)*(d+1) + m]
- * for j <= a.  Work is enqueued on `stream` (a hipStream_t, may be NULL). */
+ * for j <= a.  Both ld and, where P is given, ldp must exceed the largest row index listed (error 2 otherwise, nothing
+ * launched).  Work is enqueued on `stream` (a hipStream_t, may be NULL). */
 int gkmhip_gram_rows(gkmhip_ctx *ctx, const int *rows, int nrows, int local_rows, double *G,
                      int64_t ld, int32_t *P, int64_t ldp, void *stream);
 
@@ -404,7 +405,8 @@ int gkmhip_memcpy_h2d(void *dst, const void *src, size_t bytes);
 int gkmhip_sync(void *stream);
 
 /* Copy the lower triangle (+ diagonal) of a device K (n rows, ld) into caller-owned
- * host row pointers: rows[a][0..a].  Uses pinned staging and `nthreads` host threads. */
+ * host row pointers: rows[a][0..a].  Uses pinned staging and `nthreads` host threads.  ld >= n (error 2 otherwise).
+ * The copies run on a stream of the call's own: K must be complete when the call is made. */
 int gkmhip_copy_lower_to_rows(gkmhip_ctx *ctx, const double *K, int64_t ld, int n,
                               double **rows, int nthreads);
 

@@ -31,13 +31,15 @@ def _rbf_matrix(n, dim, seed, dup=0):
     return np.maximum(K, K.T)
 
 
-def _compare_with_sklearn(K, n_first, trains, tests, C, tol, shrinking=False):
+def _compare_with_sklearn(K, n_first, trains, tests, C, tol, shrinking=False, Kd=None):
+    """Kd: the device matrix handed to the solvers (default: a contiguous copy of K)"""
     import torch
     from sklearn.svm import SVC
     from gkmqc_amd import svmcv
     n = K.shape[0]
     y = np.concatenate((np.repeat(1, n_first), np.repeat(0, n - n_first)))
-    Kd = torch.from_numpy(K).cuda()
+    if Kd is None:
+        Kd = torch.from_numpy(K).cuda()
     sol, handles = svmcv.train_folds(Kd, trains, y, C, tol, shrinking)
     scores = svmcv.decision_values(Kd, handles, tests)
     for f, (train, test) in enumerate(zip(trains, tests)):
@@ -102,6 +104,27 @@ def test_general_solver_with_shrinking_is_bit_identical_to_sklearn(built, n, dim
             a, b = (SVC(kernel="precomputed", C=C, tol=tol, shrinking=sh).fit(K[tr][:, tr], y[tr]) for sh in (True, False))
             differs = differs or int(a.n_iter_[0]) != int(b.n_iter_[0]) or not np.array_equal(a.dual_coef_, b.dual_coef_)
         assert differs
+
+
+@pytest.mark.parametrize("n,dim,general,shrinking", [
+    (600, 10, False, False),       # k_smo
+    (700, 8, True, False),         # the general solver, shrinking off (FAST_FOLD_SAMPLES lowered)
+    (600, 10, False, True),        # the general solver with shrinking
+    (2600, 12, False, False),      # several samples per thread
+])
+def test_padded_kernel_matrix(built, monkeypatch, n, dim, general, shrinking):
+    """K as a view of a wider matrix (row stride n + 11) whose padding is NaN: svmcv passes K.stride(0) through, and
+    k_smo, k_smo_general, k_diag and the decision kernel must index rows by it.  One read of the padding is a NaN in
+    the gradient and ends the bit-identity with scikit-learn."""
+    from tests.abi_cases import nan_padded
+    if general:
+        from gkmqc_amd import svmcv
+        monkeypatch.setattr(svmcv, "FAST_FOLD_SAMPLES", 10)
+    K = _rbf_matrix(n, dim, seed=n + dim)
+    trains, tests = _folds(n, n // 2, 3, seed=1)
+    Kd = nan_padded(K, n + 11)
+    assert Kd.stride(0) == n + 11
+    _compare_with_sklearn(K, n // 2, trains, tests, 1.0, 1e-3, shrinking, Kd=Kd)
 
 
 def test_general_solver_without_shrinking(built, monkeypatch):

@@ -40,11 +40,13 @@ def _folds(n, ncv, seed):
     return list(trains), list(tests)
 
 
-def _compare_with_sklearn(K, z, trains, tests, C, eps, tol, shrinking=False, capped=False):
+def _compare_with_sklearn(K, z, trains, tests, C, eps, tol, shrinking=False, capped=False, Kd=None):
+    """Kd: the device matrix handed to the solvers (default: a contiguous copy of K)"""
     import torch
     from sklearn.svm import SVR
     from gkmqc_amd import svmcv
-    Kd = torch.from_numpy(K).cuda()
+    if Kd is None:
+        Kd = torch.from_numpy(K).cuda()
     sol = svmcv.train_svr_folds(Kd, trains, z, C, eps, tol, shrinking)
     pred = svmcv.svr_predict(Kd, sol, tests)
     for f, (train, test) in enumerate(zip(trains, tests)):
@@ -76,6 +78,28 @@ def test_solver_is_bit_identical_to_sklearn(built, n, dim, C, eps, tol, dup, shr
     z = _targets(X, n)
     trains, tests = _folds(n, 3, seed=1)
     _compare_with_sklearn(K, z, trains, tests, C, eps, tol, shrinking)
+
+
+@pytest.mark.parametrize("n,dim,general,shrinking", [
+    (600, 10, False, False),       # k_smo
+    (700, 8, True, False),         # the general solver, shrinking off (FAST_FOLD_SAMPLES lowered)
+    (600, 10, False, True),        # the general solver with shrinking
+    (2600, 12, False, False),      # several samples per thread
+])
+def test_padded_kernel_matrix(built, monkeypatch, n, dim, general, shrinking):
+    """K as a view of a wider matrix (row stride n + 11) whose padding is NaN: the SVR setup, the solvers and the
+    prediction kernel must index rows by the stride svmcv passes through.  One read of the padding is a NaN and ends
+    the bit-identity with scikit-learn."""
+    from tests.abi_cases import nan_padded
+    if general:
+        from gkmqc_amd import svmcv
+        monkeypatch.setattr(svmcv, "FAST_FOLD_SAMPLES", 10)
+    K, X = _rbf_matrix(n, dim, seed=n + dim)
+    z = _targets(X, n)
+    trains, tests = _folds(n, 3, seed=1)
+    Kd = nan_padded(K, n + 11)
+    assert Kd.stride(0) == n + 11
+    _compare_with_sklearn(K, z, trains, tests, 1.0, 0.1, 1e-3, shrinking, Kd=Kd)
 
 
 @pytest.mark.parametrize("shrinking", [False, True])
