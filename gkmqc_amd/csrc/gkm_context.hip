@@ -350,8 +350,12 @@ extern "C" int gkmhip_set_sequences(gkmhip_ctx *ctx, int n, const uint8_t *codes
         }
         ctx->sampled_hit_share = (double)within / samples;
     }
-    if (weighted && (wdist_len <= (ctx->maxlen - L + 1) / 2 || wdist_len > WD_LDS))
-        return set_err_msg("distance weight table must cover 0..max(n)/2 and hold at most 1024 entries", 3);
+    if (weighted && wdist_len <= (ctx->maxlen - L + 1) / 2)
+        return set_err_msg("distance weight table must cover 0..max(n)/2", 3);
+    /* no l-mer is farther than WD_LDS - 1 from its centre (n <= 2046), so entries past WD_LDS are never read: a caller's
+     * table of max(n) / 2 + 2 entries has 1025 at L = 2 with a 2047-base sequence, and was refused for it */
+    static_assert(WD_LDS > (GKM_MAXLEN - 2 + 1) / 2, "the distance table covers the longest sequence at the shortest L");
+    if (wdist_len > WD_LDS) wdist_len = WD_LDS;
     const size_t total = (size_t)offsets[n];
     if (ctx->codes.ensure(total) || ctx->off.ensure((size_t)n + 1) || ctx->lmoff.ensure((size_t)n + 1) ||
         ctx->len.ensure((size_t)n) || ctx->wd.ensure(WD_LDS))

@@ -73,7 +73,8 @@ int gkmhip_set_kernel(gkmhip_ctx *ctx, int which);
  * wdist: positional weights as a function of the distance to the centre l-mer: the
  * weight of l-mer p of a sequence with n l-mers is wdist[|n/2 - p|] (this is all the
  * reference's exponential-decay weights depend on, src/libgkm.c:912-925); it must cover
- * distances 0..max(n)/2, at most 1024 entries.  wdist == NULL: all weights are 1.
+ * distances 0..max(n)/2; entries past 1024 (no l-mer of a 2047-base sequence is that far from
+ * its centre) are ignored.  wdist == NULL: all weights are 1.
  * The upload runs on `stream` and has completed when the call returns (the arrays may be freed);
  * device tables are built on first use. */
 int gkmhip_set_sequences(gkmhip_ctx *ctx, int n, const uint8_t *codes, const int64_t *offsets,

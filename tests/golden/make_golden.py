@@ -7,6 +7,7 @@ Run in the development container only (needs /root/reference):
     python tests/golden/make_golden.py            # everything except the full C2 run
     python tests/golden/make_golden.py --c2-full  # + full 10 000 x 10 000 reference run (minutes)
     python tests/golden/make_golden.py --only-ragged  # only ragged_expected.npz
+    python tests/golden/make_golden.py --only-region  # only region_*.fa + region_expected.npz (byte for byte)
 
 The reference has no tests or known-answer vectors of its own, so
 every expected value here is an OUTPUT OF THE REFERENCE ITSELF:
@@ -20,6 +21,7 @@ import hashlib
 import json
 import os
 import sys
+import zipfile
 
 import numpy as np
 
@@ -171,6 +173,133 @@ def write_ragged(tmp):
     np.savez_compressed(os.path.join(HERE, "ragged_expected.npz"), **out)
 
 
+# (ix) the whole legal parameter region: 2 <= L <= 12, k <= L, d <= L - k -- k = 0 and d = L included -- on a problem
+# of 20 short sequences of our own.  quirks_expected.npz stops at d = 6 and starts at L = 4.
+REGION_LKD6 = [(12, 4, 8), (12, 1, 11), (11, 2, 9), (10, 3, 7), (9, 2, 7), (8, 1, 7), (2, 1, 1), (3, 1, 2), (3, 2, 1),
+               (4, 1, 3)]
+
+
+def region_params():
+    """(kernel_type, L, k, d, M, H, gamma): d = L - k at k = 0 and 1 for every L (types 0 and 4 in turn), all six kernel
+    types at ten high-d or short-L tuples, two tuples with d < L - k at high d, one with M = 255."""
+    out, turn = [], 0
+    for L in range(2, 13):
+        for k in (0, 1):
+            out.append(((0, 4)[turn % 2], L, k, L - k, 50, 50.0, 1.0))
+            turn += 1
+    for (L, k, d) in REGION_LKD6:
+        for t in range(6):
+            out.append((t, L, k, d, 50, 50.0, 2.0 if t in (3, 5) else 1.0))
+    out += [(2, 12, 2, 7, 50, 50.0, 1.0), (4, 11, 1, 6, 50, 50.0, 1.0), (4, 12, 4, 8, 255, 20.0, 1.0)]
+    return list(dict.fromkeys(out))          # (type 4 at k = 1 of five of the ten tuples is in both lists)
+
+
+def region_weight_tuples():
+    """all 528 (kernel_type, L, k) of the region"""
+    return [(t, L, k) for t in range(6) for L in range(2, 13) for k in range(0, L + 1)]
+
+
+def write_region_fasta():
+    """20 sequences of 12 to 299 bases: exactly 12 and 13 bases (one 12-mer, two), a poly-A and an (AT)n (every window a
+    hit), a duplicate, a reverse-complement pair, two past 290 bases."""
+    rng = np.random.default_rng(20261019)
+
+    def rnd(n):
+        return synth._BASES[rng.integers(0, 4, n)].tobytes()
+
+    pos = [(b"r%d" % i, rnd(ln)) for i, ln in enumerate([12, 13, 30, 64, 100, 150, 291])]
+    pos += [(b"polyA", b"A" * 40), (b"AT", b"AT" * 25), (b"dup_of_r4", pos[4][1])]
+    neg = [(b"rc_of_r3", rc(pos[3][1]))]
+    neg += [(b"s%d" % i, rnd(ln)) for i, ln in enumerate([12, 20, 25, 33, 45, 77, 120, 200, 299])]
+    paths = os.path.join(HERE, "region_pos.fa"), os.path.join(HERE, "region_neg.fa")
+    for path, recs in zip(paths, (pos, neg)):
+        with open(path, "wb") as f:
+            for name, seq in recs:
+                f.write(b">" + name + b"\n" + seq + b"\n")
+    return paths
+
+
+def save_npz_reproducible(path, arrays):
+    """np.savez_compressed with a fixed timestamp on every member, so that a regenerated fixture is the same file."""
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as z:
+        for name, arr in arrays.items():
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            with z.open(info, "w") as f:
+                np.lib.format.write_array(f, np.ascontiguousarray(arr), version=(1, 0), allow_pickle=False)
+
+
+def same_nonfinite_rel_err(a, b):
+    """(NaN and infinity in the same cells, largest relative error of the finite ones)"""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    fin = np.isfinite(b)
+    same = np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(a[~fin & ~np.isnan(b)], b[~fin & ~np.isnan(b)])
+    err = float(np.max(np.abs(a[fin] - b[fin]) / np.maximum(np.abs(b[fin]), 1e-300))) if fin.any() else 0.0
+    return same, err
+
+
+def write_region():
+    """region_expected.npz.  Every stored value is the reference's, and the CPU oracle must reproduce it before it is
+    stored (c_m and integer profiles bit for bit, self norms to 1e-14, K to 1e-12, NaN in the same cells): the GPU tests
+    compare with the oracle on inputs no fixture holds, so the fixture also pins that the oracle may be trusted there.
+
+    At L = 12, k = 0, d = 12 the reference has no defined K or self norm: it keeps a sequence pair's profile in
+    `int mmprofile[MAX_MM]` with MAX_MM = 12 (src/libgkm.c:732, :773; src/libgkm.h:31) and its loops run m <= d, so d = 12
+    writes one int past the array.  The integer profiles (which the k-mer tree's DFS leaves in arrays of d + 1 rows) are
+    stored for that tuple, K and the self norms are not."""
+    pp, pn = write_region_fasta()
+    out = {}
+    tlk = region_weight_tuples()
+    W = np.zeros((len(tlk), 13))
+    for i, (t, L, k) in enumerate(tlk):
+        assert O.lib().gkmo_check_params(t, L, k, L - k) is None, (t, L, k)
+        c = O.ref_weights(t, L, k, L - k)
+        assert O.mismatch_weights(t, L, k)[: L - k + 1].tobytes() == c.tobytes(), ("oracle c_m differ", t, L, k)
+        W[i, : L - k + 1] = c
+    assert len(tlk) == 528
+    out["weights_tlk"] = np.array(tlk, dtype=np.int32)
+    out["weights"] = W
+    params = region_params()
+    Ps, sqs, Ks, wts, hasK = [], [], [], [], []
+    for idx, (t, L, k, d, M, H, g) in enumerate(params):
+        assert O.lib().gkmo_check_params(t, L, k, d) is None, (t, L, k, d)
+        opt = O.make_opt(t, L, k, d, M, H, g, pp, pn, nthreads=4)
+        r = O.ref_profiles(opt)
+        n = r["n"]
+        mine = O.gram(opt, want_profiles=True, nthreads=8)
+        il = np.tril_indices(n)
+        assert mine["n"] == n and mine["n_pos"] == r["n_pos"]
+        assert np.array_equal(mine["P"][il], r["P"][il]), ("oracle profiles differ", params[idx])
+        for a in range(n):
+            nw = int(r["lens"][a]) - L + 1
+            assert np.array_equal(O.position_weights(t, nw, M, H), r["wt"][a, :nw]), ("oracle wt differ", params[idx], a)
+        defined = not (L == 12 and d == 12)
+        if defined:
+            K, npos = ref_K(opt, n)
+            same, err = same_nonfinite_rel_err(mine["sqnorm"], r["sqnorm"])
+            assert same and err < 1e-14, ("oracle self norms differ", params[idx], err)
+            same, err = same_nonfinite_rel_err(tril_pack(mine["K"]), tril_pack(K))
+            assert same and err < 1e-12, ("oracle K differs", params[idx], err)
+        Ps.append(r["P"][il].reshape(-1))
+        sqs.append(r["sqnorm"] if defined else np.zeros(n))
+        Ks.append(tril_pack(K) if defined else np.zeros(n * (n - 1) // 2))
+        wts.append(r["wt"][:, : int(r["lens"].max())])
+        hasK.append(defined)
+        out["lens"] = r["lens"]
+        out["n_pos"] = np.array(r["n_pos"])
+        print("region", (t, L, k, d, M, H, g), "N", n, "K stored" if defined else "profiles only")
+    out["params"] = np.array(params, dtype=np.float64)
+    out["has_K"] = np.array(hasK)
+    out["P"] = np.concatenate(Ps)            # tuple by tuple, the lower triangle with the diagonal row-major, d + 1 each
+    out["sqnorm"] = np.array(sqs)
+    out["K"] = np.array(Ks)                  # strict lower triangle
+    out["wt"] = np.array(wts)
+    path = os.path.join(HERE, "region_expected.npz")
+    save_npz_reproducible(path, out)
+    print("region_expected.npz: %d tuples, %d bytes" % (len(params), os.path.getsize(path)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--c2-full", action="store_true")
@@ -180,6 +309,8 @@ def main():
     ap.add_argument("--only-batch", action="store_true",
                     help="only batch_rows_expected.npz (the reference's batch-vs-set scoring entry)")
     ap.add_argument("--only-ragged", action="store_true", help="only ragged_expected.npz (a small ragged problem)")
+    ap.add_argument("--only-region", action="store_true",
+                    help="only region_pos.fa, region_neg.fa and region_expected.npz (the whole legal (L, k, d) region)")
     ap.add_argument("--threads", type=int, default=os.cpu_count(), help="row threads of the reference for --full")
     args = ap.parse_args()
     if not O.have_ref():
@@ -187,6 +318,9 @@ def main():
 
     tmp = os.path.join(ROOT, "gpurun_out", "golden_tmp")
     os.makedirs(tmp, exist_ok=True)
+    if args.only_region:
+        write_region()
+        return
     if args.only_ragged or not (args.only_full or args.only_batch):
         write_ragged(tmp)
     if args.only_ragged:

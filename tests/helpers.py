@@ -9,6 +9,8 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 QUIRK_POS = os.path.join(GOLDEN, "quirks_pos.fa")
 QUIRK_NEG = os.path.join(GOLDEN, "quirks_neg.fa")
+REGION_POS = os.path.join(GOLDEN, "region_pos.fa")
+REGION_NEG = os.path.join(GOLDEN, "region_neg.fa")
 
 
 def golden_weights():
@@ -28,6 +30,40 @@ def quirks_expected():
                           wt=z["q%d_wt" % i]))
         i += 1
     return cases, z["lens"], int(z["n_pos"])
+
+
+def region_expected():
+    """tests/golden/region_expected.npz: the reference on the 20 sequences of region_pos.fa + region_neg.fa over the whole
+    legal (L, k, d) region (tests/golden/make_golden.py --only-region).  -> (cases, lens, n_pos, weights): cases as
+    quirks_expected() gives them, K and sqnorm None where the reference has no defined value (L = 12, k = 0, d = 12);
+    weights maps each of the 528 (kernel_type, L, k) to the reference's c_0 .. c_{L-k}."""
+    z = np.load(os.path.join(GOLDEN, "region_expected.npz"))
+    lens = z["lens"]
+    n = len(lens)
+    il = np.tril_indices(n)
+    cases, at = [], 0
+    for i, (t, L, k, d, M, H, g) in enumerate(z["params"]):
+        d = int(d)
+        P = np.zeros((n, n, d + 1), dtype=np.int32)
+        P[il] = z["P"][at: at + len(il[0]) * (d + 1)].reshape(-1, d + 1)
+        at += len(il[0]) * (d + 1)
+        has = bool(z["has_K"][i])
+        cases.append(dict(idx=i, kernel_type=int(t), L=int(L), k=int(k), d=d, M=int(M), H=float(H), gamma=float(g), P=P,
+                          sqnorm=z["sqnorm"][i] if has else None, K=z["K"][i] if has else None, wt=z["wt"][i]))
+    assert at == len(z["P"])
+    weights = {tuple(int(x) for x in tlk): w[: tlk[1] - tlk[2] + 1] for tlk, w in zip(z["weights_tlk"], z["weights"])}
+    return cases, lens, int(z["n_pos"].reshape(-1)[0]), weights
+
+
+def same_nonfinite_rel_err(a, b):
+    """(NaN and infinity in the same cells of a and b, the largest per-element relative error of b's finite cells) -- a
+    type with negative c_m can give a negative squared norm, whose root is NaN in the reference too"""
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    fin = np.isfinite(b)
+    inf = ~fin & ~np.isnan(b)
+    same = bool(np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(a[inf], b[inf]))
+    return same, max_rel_err(a[fin], b[fin])
 
 
 def synthetic_expected():

@@ -75,6 +75,31 @@ def test_position_weights(dev):
             assert (got == c["wt"][i, :n]).all(), (c["idx"], i)
 
 
+def test_region_mismatch_weights_bit_identical(dev):
+    """all 528 (kernel type, L, k) with 2 <= L <= 12, 0 <= k <= L: c_0 .. c_{L-k} against the reference's
+    (tests/golden/region_expected.npz)"""
+    weights = helpers.region_expected()[3]
+    assert len(weights) == 528
+    for (t, L, k), ref in weights.items():
+        assert dev.check_parameters(t, L, k, L - k) is None, (t, L, k)
+        assert dev.mismatch_weights(t, L, k)[: L - k + 1].tobytes() == ref.tobytes(), (t, L, k)
+
+
+def test_region_position_weights(dev):
+    cases, lens, _, _ = helpers.region_expected()
+    for c in cases:
+        for i, ln in enumerate(lens):
+            n = int(ln) - c["L"] + 1
+            got = dev.position_weights(c["kernel_type"], n, c["M"], c["H"])
+            assert (got == c["wt"][i, :n]).all(), (c["idx"], i)
+
+
+def test_region_fasta_reader_lengths(dev):
+    seqs, n_pos, n_invalid, n_trunc = dev.read_problem(helpers.REGION_POS, helpers.REGION_NEG)
+    _, lens, npos, _ = helpers.region_expected()
+    assert [len(s) for s in seqs] == list(lens) and n_pos == npos and n_invalid == 0 and n_trunc == 0
+
+
 def test_fasta_reader_matches_oracle_and_reference_lengths(dev):
     from oracle import oracle as O
     seqs, n_pos, n_invalid, n_trunc = dev.read_problem(helpers.QUIRK_POS, helpers.QUIRK_NEG)

@@ -162,3 +162,74 @@ def test_a_cell_depends_on_its_two_sequences_only(O):
         assert G.tobytes() == full["G"][np.ix_(rows, cols)].tobytes(), params
         assert K.tobytes() == full["K"][np.ix_(rows, cols)].tobytes(), params
         assert K[1, 1] == 1.0
+
+
+def test_region_mismatch_weights_bit_identical(O):
+    """c_0 .. c_{L-k} of all 528 (kernel type, L, k) with 2 <= L <= 12 and 0 <= k <= L against the reference's
+    (tests/golden/region_expected.npz, made by make_golden.py --only-region)."""
+    weights = helpers.region_expected()[3]
+    assert len(weights) == 528
+    for (t, L, k), ref in weights.items():
+        assert len(ref) == L - k + 1
+        assert O.mismatch_weights(t, L, k)[: L - k + 1].tobytes() == ref.tobytes(), (t, L, k)
+
+
+@pytest.fixture(scope="module")
+def region_oracle(O):
+    """the oracle on the region problem, one run per tuple of the fixture, shared by the tests below"""
+    cases, lens, npos, _ = helpers.region_expected()
+    runs = []
+    for c in cases:
+        opt = O.make_opt(c["kernel_type"], c["L"], c["k"], c["d"], c["M"], c["H"], c["gamma"],
+                         helpers.REGION_POS, helpers.REGION_NEG)
+        runs.append(O.gram(opt, want_profiles=True, nthreads=8))
+    return cases, lens, npos, runs
+
+
+def test_region_fixture_covers_what_it_claims():
+    """d = L - k at k = 0 and k = 1 for every L, all six types at the ten listed tuples, d >= 7 up to d = L = 12, L = 2
+    and 3, one M = 255; sequences of exactly 12 and 13 bases, two past 290, a duplicate and a reverse-complement pair."""
+    cases, lens, npos, _ = helpers.region_expected()
+    have = {(c["kernel_type"], c["L"], c["k"], c["d"]) for c in cases}
+    lkd = {x[1:] for x in have}
+    for L in range(2, 13):
+        assert (L, 0, L) in lkd and (L, 1, L - 1) in lkd
+    for x in [(12, 4, 8), (12, 1, 11), (11, 2, 9), (10, 3, 7), (9, 2, 7), (8, 1, 7), (2, 1, 1), (3, 1, 2), (3, 2, 1), (4, 1, 3)]:
+        assert all((t,) + x in have for t in range(6)), x
+    assert (2, 12, 2, 7) in have and (4, 11, 1, 6) in have and any(c["M"] == 255 for c in cases)
+    assert [c["K"] is None for c in cases].count(True) == 1        # L = 12, k = 0, d = 12 alone
+    assert all((c["L"], c["k"], c["d"]) == (12, 0, 12) for c in cases if c["K"] is None)
+    assert sorted(lens)[:2] == [12, 12] and 13 in lens and (np.asarray(lens) > 290).sum() == 2 and len(lens) == 20
+
+
+def test_region_profiles_bit_identical(region_oracle):
+    cases, lens, npos, runs = region_oracle
+    il = np.tril_indices(len(lens))
+    for c, r in zip(cases, runs):
+        assert r["n"] == len(lens) and r["n_pos"] == npos
+        assert np.array_equal(r["P"][il], c["P"][il]), (c["kernel_type"], c["L"], c["k"], c["d"])
+
+
+def test_region_self_norms_and_kernel(region_oracle):
+    """1e-14 on the self norms and 1e-12 on K as for the quirks fixture, per element, NaN in the same cells (a type with
+    negative c_m, or an int32 profile that wrapped at M = 255, has a negative squared norm)."""
+    cases, lens, npos, runs = region_oracle
+    seen_nan = 0
+    for c, r in zip(cases, runs):
+        if c["K"] is None:
+            continue
+        key = (c["kernel_type"], c["L"], c["k"], c["d"])
+        same, err = helpers.same_nonfinite_rel_err(r["sqnorm"], c["sqnorm"])
+        assert same and err < 1e-14, (key, err)
+        same, err = helpers.same_nonfinite_rel_err(helpers.tril_pack(r["K"]), c["K"])
+        assert same and err < 1e-12, (key, err)
+        seen_nan += int(np.isnan(c["K"]).any())
+    assert seen_nan > 0
+
+
+def test_region_position_weights(O):
+    cases, lens, _, _ = helpers.region_expected()
+    for c in cases:
+        for i, ln in enumerate(lens):
+            n = int(ln) - c["L"] + 1
+            assert (O.position_weights(c["kernel_type"], n, c["M"], c["H"]) == c["wt"][i, :n]).all(), (c["idx"], i)

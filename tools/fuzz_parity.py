@@ -1,7 +1,11 @@
 """Randomised parity sweep on the GPU box: random (kernel type, L, k, d, M, H), random length
 distributions (fixed, ragged, minimal, duplicates, poly-A), random row subsets -- integer
 mismatch profiles and K of the device layer against the CPU oracle (test infrastructure).
-python tools/fuzz_parity.py [--seconds 240] [--seed 1]"""
+python tools/fuzz_parity.py [--seconds 240] [--seed 1] [--region whole]
+
+--region whole: outside the bit-sliced table the draw covers every legal tuple -- L in 2..12, k in 0..L, d in 0..L-k, so
+d up to L -- where the default stops at d <= 4, L >= 3, k >= 1.  The last line counts the cases with d >= 5 outside the
+bit-sliced table: the ones only k_gram_direct serves."""
 import argparse
 import os
 import sys
@@ -41,6 +45,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=240)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--region", choices=("default", "whole"), default="default")
     a = ap.parse_args()
     import torch  # noqa: F401
     from gkmqc_amd import device, synth
@@ -51,12 +56,17 @@ def main():
     letters = np.frombuffer(b"ACGT", dtype=np.uint8)
     t_end = time.time() + a.seconds
     cases = 0
+    high_d = 0        # cases with d >= 5 and no bit-sliced kernel
     kernels = {}
     while time.time() < t_end:
         t = int(rng.integers(0, 6))
         if rng.random() < 0.75:   # (L, d) pairs with a bit-sliced instantiation
             L, d = BITSLICED[int(rng.integers(len(BITSLICED)))]
             k = int(rng.integers(1, L - d + 1))
+        elif a.region == "whole":
+            L = int(rng.integers(2, 13))
+            k = int(rng.integers(0, L + 1))
+            d = int(rng.integers(0, L - k + 1))
         else:
             L = int(rng.integers(3, 13))
             k = int(rng.integers(1, L + 1))
@@ -118,9 +128,10 @@ def main():
             used = "%s PK %d" % (res["kernel"], res["variant"])
             kernels[used] = kernels.get(used, 0) + 1
         cases += 1
+        high_d += int(d >= 5 and (L, d) not in BITSLICED)
         if cases % 50 == 0:
             print("%d cases ok %s" % (cases, kernels), flush=True)
-    print("fuzz ok: %d cases, kernels used: %s" % (cases, kernels))
+    print("fuzz ok: %d cases, %d with d >= 5 outside the bit-sliced table, kernels used: %s" % (cases, high_d, kernels))
 
 
 if __name__ == "__main__":
