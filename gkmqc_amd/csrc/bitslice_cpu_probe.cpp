@@ -221,6 +221,37 @@ extern "C" int bsprobe_group_any_centres(int L, int d, const uint32_t *Ahi, cons
     return 1;
 }
 
+/* ---- the centres entry's two forms (tests/test_shared_trees.py) ------------------------------------
+ * window_group_any_grouped, window_group_any_centres as the shift-record kernel runs it (the two centre trees share their
+ * overlap, the top half adder folded into the threshold) and its private-trees form (SHARED = false: the build with
+ * -DGKM_BS_CENTRES=1) on the planes given; AVg[2] is taken as it comes.  Return codes as bsprobe_group_any_crossings. */
+template <int W, int L, int D, int GRP>
+static int run_group_any_centres_forms(const uint32_t *Ahi, const uint32_t *Alo, const uint32_t *AVg, const uint32_t *Bhi,
+                                       const uint32_t *Blo, uint32_t *any_grouped, uint32_t *any_shared, uint32_t *any_private)
+{
+    if constexpr (!top_plane_serves(L, D)) {
+        return 2;
+    } else {
+        window_group_any_grouped<W, L, D, GRP>(Ahi, Alo, AVg, Bhi, Blo, any_grouped);
+        window_group_any_centres<W, L, D, GRP>(Ahi, Alo, AVg, Bhi, Blo, any_shared);
+        window_group_any_centres<W, L, D, GRP, false>(Ahi, Alo, AVg, Bhi, Blo, any_private);
+        return 0;
+    }
+}
+
+#define FCASE(LL, DD) \
+    if (L == LL && d == DD) return run_group_any_centres_forms<10, LL, DD, 5>(Ahi, Alo, AVg, Bhi, Blo, any_grouped, any_shared, any_private);
+#define FCASE_L(LL) FCASE(LL, 0) FCASE(LL, 1) FCASE(LL, 2) FCASE(LL, 3) FCASE(LL, 4)
+
+extern "C" int bsprobe_group_any_centres_forms(int L, int d, const uint32_t *Ahi, const uint32_t *Alo, const uint32_t *AVg,
+                                               const uint32_t *Bhi, const uint32_t *Blo, uint32_t *any_grouped,
+                                               uint32_t *any_shared, uint32_t *any_private)
+{
+    FCASE_L(5) FCASE_L(6) FCASE_L(7) FCASE_L(8) FCASE_L(9) FCASE_L(10) FCASE_L(11) FCASE_L(12)
+    FCASE(11, 5) FCASE(12, 5) FCASE(12, 6)
+    return 1;
+}
+
 /* the table builders, for the same test: the three planes of a row segment (out[plane * W + w]) ... */
 extern "C" void bsprobe_row_planes(const uint8_t *codes, int len, int s0, int W, int L, uint32_t *out)
 {

@@ -626,7 +626,47 @@ constexpr int TT_UP_OR_LEVEL_C = 0xB2; /* (a & ~b) | (~(a ^ b) & c) */
 constexpr int TT_A_ANDN_B_C = 0x20;    /* a & ~b & c */
 constexpr int TT_AND3 = 0x80;          /* a & b & c */
 
-template <int W, int L, int D, int GRP>
+/*
+ * SHARED TREES (SHARED = true, what the kernel runs): the two centre windows Z[C0 .. C0+L-1] and Z[C1 .. C1+L-1], C1 = C0 + GRP,
+ * have the n = L - GRP words Z[C1 .. C0+L-1] in common, and a column sum does not care in which order its planes are folded.  So
+ * the overlap's words are folded three at a time ONCE, by floor(n / 3) full adders; each centre's column 0 then takes its GRP
+ * exclusive words, the shared sums and the overlap's leftover words, and its column 1 takes that column's carries and the shared
+ * carries.  A bias of one is common to both centres as well: where the overlap leaves a word over it rides there (two leftover
+ * words: their half adder with a third input of one, as in ColumnSumBiased; one: w + 1 = (~w, carry w)), else in each centre's
+ * column 0 as before.  L = 11: FA(Z7, Z8, Z9), FA(Z10, Z11, Z12), then per centre 3 full adders in column 0 (5 + 2 planes) and 2
+ * in column 1 (3 + 2 carries): 4 + 2 x 10 ops where two private trees take 2 x 14 below their top half adder.  L = 10, bias 1:
+ * FA(Z7, Z8, Z9) and the biased half adder of Z10, Z11: the same 4 + 2 x 10.
+ * THE TOP HALF ADDER FOLDED INTO THE THRESHOLD: where the column of plane P-2 holds exactly two planes p and q (L = 10, 11 and
+ * others: top_pair_folds), b[P-2] = p ^ q and b[P-1] = p & q, and with y = b[P-3] & .. & b[1] & v the group's word is
+ *     b[P-1] | (b[P-2] & y)  =  (p & q) | ((p ^ q) & y)  =  maj(p, q, y)
+ * so neither plane is ever formed: y, maj, & AVg -- three ops where the half adder, x and the last op took four.  Other shapes
+ * (L = 12, d = 4: three planes in that column, a full adder) keep their last stage.
+ * Per shift at W = 10, L = 11: 20 + 10 + 4 + 2 x (10 + 6 + 2 + 3) + 6 = 82 where the private trees come to 88.  Both are the
+ * same function of Z, bit for bit on arbitrary words (tests/test_shared_trees.py); SHARED = false is the private form, kept
+ * for the A/B build (-DGKM_BS_CENTRES=1) and as the second route of that test.
+ */
+constexpr bool top_pair_folds(int I, int P, int N) /* column I holds N planes: does column P-2 come to hold exactly two? */
+{
+    return I > P - 2 ? false : I == P - 2 ? N == 2 : top_pair_folds(I + 1, P, N / 2);
+}
+/* planes I .. of a count from the N planes of column I, column compression as in ColumnSum; with FOLD the pair of column P-2 is
+ * handed back in pq instead of being added */
+template <int I, int P, int N, bool FOLD>
+GKM_HD void centre_planes(const uint32_t *x, uint32_t *b, uint32_t *pq)
+{
+    if constexpr (FOLD && I == P - 2) {
+        static_assert(N == 2, "the fold is for a column of exactly two planes");
+        pq[0] = x[0];
+        pq[1] = x[1];
+    } else if constexpr (I < P) {
+        static_assert(N >= 1, "a plane of the count has at least one input");
+        uint32_t carry[ColumnSum<N>::NC > 0 ? ColumnSum<N>::NC : 1];
+        b[I] = ColumnSum<N>::run(x, carry);
+        centre_planes<I + 1, P, ColumnSum<N>::NC, FOLD>(carry, b, pq);
+    }
+}
+
+template <int W, int L, int D, int GRP, bool SHARED = true>
 GKM_HD void window_group_any_centres(const uint32_t *Ahi, const uint32_t *Alo, const uint32_t *AVg, const uint32_t *Bhi,
                                      const uint32_t *Blo, uint32_t *any)
 {
@@ -637,20 +677,70 @@ GKM_HD void window_group_any_centres(const uint32_t *Ahi, const uint32_t *Alo, c
     static_assert(P >= 3, "a top plane, plane 0 and at least one between them");
     constexpr int BETA = top_plane_bias(L, D);
     constexpr int NX = W + L - 1;
+    constexpr int HALF = GRP / 2;
     uint32_t Z[NX]; /* MATCH bits, as in window_group_any */
 #pragma unroll
     for (int w = 0; w < W; w++) Z[w] = lop3<TT_NOT_A_OR_BXC>(Ahi[w] ^ Bhi[w], Alo[w], Blo[w]);
 #pragma unroll
     for (int x = W; x < NX; x++) Z[x] = Z[x - W] >> 1;
 
+    /* the overlap of the two centre windows, folded once (SHARED): NS planes for each centre's column 0, NY for its column 1 */
+    constexpr bool SH = SHARED && L >= GRP;
+    constexpr int OV0 = GRP + HALF;                      /* the overlap's first word: the second centre */
+    constexpr int NOV = SH ? L - GRP : 0;                /* its words Z[OV0 .. HALF+L-1] */
+    constexpr int NF = NOV / 3, REST = NOV - 3 * NF;     /* full adders, words left over */
+    constexpr bool BIAS_SH = SH && BETA == 1 && REST > 0; /* the one rides in the overlap's leftover */
+    constexpr int NS = NF + (BIAS_SH ? 1 : REST), NY = NF + (BIAS_SH ? 1 : 0);
+    constexpr int N0 = GRP + NS;                         /* planes of a centre's column 0: its own words and the shared sums */
+    constexpr bool CIN0 = BETA == 1 && !BIAS_SH;         /* ... and the one, where the overlap could not take it */
+    using CS0 = ColumnSumBiased<N0, CIN0>;
+    constexpr int N1 = CS0::NC + NY;                     /* planes of its column 1 */
+    constexpr bool FOLD = SH && top_pair_folds(1, P, N1);
+    uint32_t ss[NS > 0 ? NS : 1], sy[NY > 0 ? NY : 1];
+    if constexpr (SH) {
+#pragma unroll
+        for (int i = 0; i < NF; i++) {
+            const uint32_t a = Z[OV0 + 3 * i], b = Z[OV0 + 3 * i + 1], c = Z[OV0 + 3 * i + 2];
+            ss[i] = lop3<TT_XOR3>(a, b, c);
+            sy[i] = lop3<TT_MAJ>(a, b, c);
+        }
+        if constexpr (BIAS_SH && REST == 2) { /* a + b + 1 */
+            const uint32_t a = Z[OV0 + 3 * NF], b = Z[OV0 + 3 * NF + 1];
+            ss[NF] = lop3<TT_XNOR_AB>(a, b, b);
+            sy[NF] = a | b;
+        } else if constexpr (BIAS_SH) { /* a + 1 */
+            ss[NF] = ~Z[OV0 + 3 * NF];
+            sy[NF] = Z[OV0 + 3 * NF];
+        } else {
+#pragma unroll
+            for (int i = 0; i < REST; i++) ss[NF + i] = Z[OV0 + 3 * NF + i];
+        }
+    }
+
 #pragma unroll
     for (int g = 0; g < W / GRP; g++) {
-        constexpr int HALF = GRP / 2;
         const int C = g * GRP + HALF; /* the group's centre word: C - 2 >= 0, C + L + 1 <= NX - 1 */
-        Cnt<P, L + BETA> cnt;
-        static_assert(Cnt<P, L + BETA>::P == P && !Cnt<P, L + BETA>::OV, "the biased count fills exactly its planes");
-        cnt.ovf = 0u;
-        plane_sum_columns_biased<0, P, L + BETA, L, BETA == 1>(Z + C, cnt);
+        uint32_t b[P], pq[2] = {0u, 0u};
+        if constexpr (SH) {
+            /* column 0: the centre's own GRP words (group 0: below the overlap, group 1: above it) and the shared sums */
+            const int X0 = g == 0 ? HALF : HALF + L;
+            uint32_t c0[N0], c1[N1];
+#pragma unroll
+            for (int i = 0; i < GRP; i++) c0[i] = Z[X0 + i];
+#pragma unroll
+            for (int i = 0; i < NS; i++) c0[GRP + i] = ss[i];
+            b[0] = CS0::run(c0, c1);
+#pragma unroll
+            for (int i = 0; i < NY; i++) c1[CS0::NC + i] = sy[i];
+            centre_planes<1, P, N1, FOLD>(c1, b, pq);
+        } else {
+            Cnt<P, L + BETA> cnt;
+            static_assert(Cnt<P, L + BETA>::P == P && !Cnt<P, L + BETA>::OV, "the biased count fills exactly its planes");
+            cnt.ovf = 0u;
+            plane_sum_columns_biased<0, P, L + BETA, L, BETA == 1>(Z + C, cnt);
+#pragma unroll
+            for (int i = 0; i < P; i++) b[i] = cnt.b[i];
+        }
         /* up: Z[C+L], Z[C+L+1] enter, Z[C], Z[C+1] leave; down: Z[C-1], Z[C-2] enter, Z[C+L-1], Z[C+L-2] leave */
         const uint32_t pu = lop3<TT_A_ANDN_B>(Z[C + L + 1], Z[C + 1], Z[C + 1]);
         const uint32_t m1u = lop3<TT_UP_OR_LEVEL_C>(Z[C + L], Z[C], pu);
@@ -658,13 +748,15 @@ GKM_HD void window_group_any_centres(const uint32_t *Ahi, const uint32_t *Alo, c
         const uint32_t pd = lop3<TT_A_ANDN_B>(Z[C - 2], Z[C + L - 2], Z[C + L - 2]);
         const uint32_t m1d = lop3<TT_UP_OR_LEVEL_C>(Z[C - 1], Z[C + L - 1], pd);
         const uint32_t m2d = lop3<TT_A_ANDN_B_C>(Z[C - 1], Z[C + L - 1], pd);
-        const uint32_t u = lop3<TT_AB_AND_C>(m1u, m1d, cnt.b[0]);
+        const uint32_t u = lop3<TT_AB_AND_C>(m1u, m1d, b[0]);
         uint32_t x = lop3<TT_OR3>(m2u, m2d, u);
-        /* the planes between plane 0 and the top one, two at a time */
+        /* the planes between plane 0 and the top one (with the fold: below the pair's), two at a time */
+        constexpr int TOPMID = FOLD ? P - 3 : P - 2;
 #pragma unroll
-        for (int i = 1; i + 1 <= P - 2; i += 2) x = lop3<TT_AND3>(cnt.b[i], cnt.b[i + 1], x);
-        if constexpr ((P - 2) % 2 == 1) x &= cnt.b[P - 2];
-        any[g] = lop3<TT_AB_AND_C>(cnt.b[P - 1], x, AVg[g]);
+        for (int i = 1; i + 1 <= TOPMID; i += 2) x = lop3<TT_AND3>(b[i], b[i + 1], x);
+        if constexpr (TOPMID >= 1 && TOPMID % 2 == 1) x &= b[TOPMID];
+        if constexpr (FOLD) any[g] = lop3<TT_MAJ>(pq[0], pq[1], x) & AVg[g];
+        else any[g] = lop3<TT_AB_AND_C>(b[P - 1], x, AVg[g]);
     }
 }
 
