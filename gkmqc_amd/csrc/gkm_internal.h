@@ -23,15 +23,17 @@
  *                          k_lmer_explain, k_lmer_hyp), gkmhip_lmer_importance, gkmhip_lmer_explain, gkmhip_lmer_hyp
  *   gkm_scan.hip           every window of a long sequence scored from an l-mer weight table (k_scan_lmers, k_scan_profiles,
  *                          k_scan_score), gkmhip_scan_lmers, gkmhip_scan_profiles, gkmhip_scan_score, gkmhip_scan_group
- *   gkm_delta.hip          variant effects from an l-mer weight table: every SNV of every position and a list of variants
- *                          (k_delta_sat, k_delta_variants), gkmhip_delta_sat, gkmhip_delta_variants
+ *   gkm_delta.hip          variant effects from an l-mer weight table or panel: every SNV of every position and a list of
+ *                          variants, one body each over a weight accessor (k_delta_sat, k_delta_variants,
+ *                          k_panel_delta_sat, k_panel_delta_variants), gkmhip_delta_sat, gkmhip_delta_variants,
+ *                          gkmhip_panel_delta_sat, gkmhip_panel_delta_variants
  *   gkm_nullidx.hip        the genome window index of null-sequence sampling: window keys and flag planes, cell counts,
  *                          a stable radix sort of the window starts (k_nullidx_keys, k_nullidx_hist, k_nix_*,
  *                          k_nullidx_digits, k_nullidx_scatter), gkmhip_nullidx_keys, gkmhip_nullidx_cells,
  *                          gkmhip_nullidx_sort, gkmhip_nullidx_tile, gkmhip_nullidx_scratch_bytes; needs no context
  *   gkm_panel.hip          l-mer weight panels: up to 64 interleaved tables served by one lookup per l-mer, the lanes across
- *                          models (k_panel_score, k_panel_scan_score, k_panel_delta_variants, k_panel_delta_sat),
- *                          gkmhip_panel_score, gkmhip_panel_scan_score, gkmhip_panel_delta_variants, gkmhip_panel_delta_sat
+ *                          models: the two tree kernels (k_panel_score, k_panel_scan_score), gkmhip_panel_score,
+ *                          gkmhip_panel_scan_score, and what every panel entry checks (panel_check, panel_shift)
  */
 #ifndef GKM_INTERNAL_H
 #define GKM_INTERNAL_H
@@ -210,6 +212,14 @@ int check_rows(const gkmhip_ctx *ctx, const int *rows, int nrows, double *row_lm
 void scan_range(const gkmhip_ctx *ctx, int col_begin, int col_end, int *tmax, int64_t *bases);
 /* rows -> ctx->blk_rows, complete on return */
 int upload_rows(gkmhip_ctx *ctx, const int *rows, int nrows, hipStream_t stream);
+
+/* what the launches over l-mer words share across files; `what`: the entry point, in front of every message */
+/* the windows of a scan launch (gkm_scan.hip): width - L + 1, or a negative value after set_err_msg */
+int scan_check(const gkmhip_ctx *ctx, const void *lm, int64_t nlm, const void *wt, int width, int stride, int64_t nwin,
+               const void *out, const char *what);
+/* a panel's pointer, models and row stride (gkm_panel.hip): 0 or error 2; log2 of nm rounded up to 8, 16, 32 or 64 */
+int panel_check(const void *P, int nm, int ms, const char *what);
+int panel_shift(int nm);
 
 /* ------------------------------------------------------------ what a Gram launch writes */
 struct GramOut {

@@ -137,7 +137,9 @@ __global__ __launch_bounds__(SS_THREADS) void k_scan_score(const uint32_t *__res
     if (lane == 0) out[i] = acc;
 }
 
-/* the checks the window launches share: n, or a negative value after set_err_msg */
+} /* namespace */
+
+/* the checks the window launches share, gkm_panel.hip's included: n, or a negative value after set_err_msg */
 int scan_check(const gkmhip_ctx *ctx, const void *lm, int64_t nlm, const void *wt, int width, int stride, int64_t nwin,
                const void *out, const char *what)
 {
@@ -150,8 +152,6 @@ int scan_check(const gkmhip_ctx *ctx, const void *lm, int64_t nlm, const void *w
         return -set_err_msg(std::string(what) + ": the windows must lie inside the l-mer words given", 2);
     return n;
 }
-
-} /* namespace */
 
 extern "C" int gkmhip_scan_group(const gkmhip_ctx *ctx, int width, int stride)
 {

@@ -581,14 +581,21 @@ class GramContext:
         """One delta per row (pos, ref_len, alt_off, alt_len) of the HOST int32 array var, alt the HOST uint8 array of all
         alternate bases; lm_ptr / codes_ptr: the device words and codes of the nbases bases (include/gkm_hip.h
         gkmhip_delta_variants)."""
-        var = np.ascontiguousarray(var, dtype=np.int32).reshape(-1, 4)
-        alt = np.ascontiguousarray(alt, dtype=np.uint8)
-        self._chk(self.lib.gkmhip_delta_variants(self.handle, lm_ptr, codes_ptr, int(nbases), var.ctypes.data, len(var),
-                                                 alt.ctypes.data if len(alt) else None, len(alt), W_ptr, out_ptr, stream),
+        var, alt, args = self._variant_arrays(var, alt)
+        self._chk(self.lib.gkmhip_delta_variants(self.handle, lm_ptr, codes_ptr, int(nbases), *args, W_ptr, out_ptr, stream),
                   "gkmhip_delta_variants")
 
-    # l-mer weight panels (include/gkm_hip.h, gkm_panel.hip): P_ptr = 4^L rows of `ms` device doubles, the first `nm` of a
-    # row the models' weights; the model index is the last axis of every output
+    @staticmethod
+    def _variant_arrays(var, alt):
+        """The host arrays of a variant launch -> (var, alt, args): the contiguous int32 (n, 4) and uint8 arrays, which the
+        caller holds until the C call returns, and (var pointer, nvar, alt pointer or None, nalt) as the entries take
+        them."""
+        var = np.ascontiguousarray(var, dtype=np.int32).reshape(-1, 4)
+        alt = np.ascontiguousarray(alt, dtype=np.uint8)
+        return var, alt, (var.ctypes.data, len(var), alt.ctypes.data if len(alt) else None, len(alt))
+
+    # l-mer weight panels (include/gkm_hip.h; gkm_panel.hip, gkm_delta.hip): P_ptr = 4^L rows of `ms` device doubles, the
+    # first `nm` of a row the models' weights; the model index is the last axis of every output
     def panel_score(self, col_begin, col_end, P_ptr, nm, ms, out_ptr, stream=0):
         """lmer_score for every model of a panel -> out_ptr, (col_end - col_begin) x nm doubles (gkmhip_panel_score)."""
         self._chk(self.lib.gkmhip_panel_score(self.handle, int(col_begin), int(col_end), P_ptr, int(nm), int(ms), out_ptr,
@@ -606,10 +613,8 @@ class GramContext:
 
     def panel_delta_variants(self, lm_ptr, codes_ptr, nbases, var, alt, P_ptr, nm, ms, out_ptr, stream=0):
         """delta_variants for every model of a panel -> out_ptr, len(var) x nm doubles (gkmhip_panel_delta_variants)."""
-        var = np.ascontiguousarray(var, dtype=np.int32).reshape(-1, 4)
-        alt = np.ascontiguousarray(alt, dtype=np.uint8)
-        self._chk(self.lib.gkmhip_panel_delta_variants(self.handle, lm_ptr, codes_ptr, int(nbases), var.ctypes.data, len(var),
-                                                       alt.ctypes.data if len(alt) else None, len(alt), P_ptr, int(nm),
+        var, alt, args = self._variant_arrays(var, alt)
+        self._chk(self.lib.gkmhip_panel_delta_variants(self.handle, lm_ptr, codes_ptr, int(nbases), *args, P_ptr, int(nm),
                                                        int(ms), out_ptr, stream), "gkmhip_panel_delta_variants")
 
     def self_norms(self, sq_ptr, stream=0):

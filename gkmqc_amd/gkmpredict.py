@@ -951,6 +951,19 @@ class LmerTable(_FoldedModel):
         if self.W.shape != (4 ** self.L,):
             raise ModelError("a table for L = %d needs 4^L = %d weights" % (self.L, 4 ** self.L))
 
+    # what the drivers that serve a table and a panel alike ask of either (_score_folded, _scan_folded,
+    # _saturation_folded, _delta_values)
+    cols = ()                                                              # the trailing shape of a result
+
+    def device_weights(self):
+        """The host array the launches read."""
+        return self.W
+
+    def launcher(self, ctx, name):
+        """The context's launch `name` (lmer_score, scan_score, delta_sat or delta_variants) from this table: that method
+        itself, called as (..., weights pointer, out pointer, stream)."""
+        return getattr(ctx, name)
+
     def save(self, path):
         """Write the weights file (format: INTEGRATION.md §5b): `# key value` header lines, then LMER<TAB>weight for
         every canonical l-mer in lexicographic ACGT order, with repr() floats."""
@@ -1103,21 +1116,46 @@ def score_with_table(table, fasta_or_sequences, device=0, block=None, on_block=N
     beyond it the exact score).  Only the queries are uploaded: per block the exact self norms (gkmhip_self_profiles) and one gather per l-mer (k_lmer_score); bit-identical for every block size.
     on_block(dict) (measurements): called after every block with its size, k_lmer_score's milliseconds and the block's
     wall time."""
+    return _score_folded(table, fasta_or_sequences, device, block, on_block)
+
+
+def _models(cols):
+    """what a panel's measurement dicts hold beside the table's"""
+    return dict(models=cols[0]) if cols else {}
+
+
+def _per_item(v, cols):
+    """a vector of one value per item (numpy or torch), broadcastable against (items,) + cols"""
+    return v.reshape((-1,) + (1,) * len(cols))
+
+
+def _rho_operand(folded, dev):
+    """rho as the epilogues add it: a table's float as it is, a panel's (n_models,) on the device"""
+    import torch
+    return torch.from_numpy(folded.rho).to(dev) if folded.cols else folded.rho
+
+
+def _score_folded(folded, fasta_or_sequences, device, block, on_block):
+    """The body `score_with_table` and `score_with_panel` share -> (names, scores (Q,) + folded.cols).  folded: the table
+    or panel (checked)."""
     import torch
     seqs, names = _as_queries(fasta_or_sequences)
-    check_queries(table, seqs)
-    blocks = _Blocks(table, seqs, device, block, default_table_block(_longest(seqs)), exact=True)
-    ctx, sq, dev = blocks.ctx, blocks.sq, blocks.dev
-    out = np.empty(len(seqs))
+    check_queries(folded, seqs)
+    blocks = _Blocks(folded, seqs, device, block, default_table_block(_longest(seqs)), exact=True)
+    ctx, sq, dev, cols = blocks.ctx, blocks.sq, blocks.dev, folded.cols
+    out = np.empty((len(seqs),) + cols)
     with torch.cuda.device(dev):
-        W = torch.from_numpy(table.W).to(dev)
-        T = torch.empty(blocks.qb_max, dtype=torch.float64, device=dev)
+        W = torch.from_numpy(folded.device_weights()).to(dev)
+        rho = _rho_operand(folded, dev)
+        T = torch.empty((blocks.qb_max,) + cols, dtype=torch.float64, device=dev)
+        launch = folded.launcher(ctx, "lmer_score")
         for b in blocks:
-            ctx.lmer_score(0, b.qb, W.data_ptr(), T.data_ptr(), blocks.stream)
-            out[b.q0:b.q1] = (T[:b.qb] / sq[:b.qb] + table.rho).cpu().numpy()
+            launch(0, b.qb, W.data_ptr(), T.data_ptr(), blocks.stream)
+            out[b.q0:b.q1] = (T[:b.qb] / _per_item(sq[:b.qb], cols) + rho).cpu().numpy()
             if on_block is not None:
-                on_block(dict(queries=b.qb, score_kernel_ms=ctx.last_kernel_ms(), lmers=ctx.last_comparisons(),
-                              kernel=ctx.last_kernel_name(), wall_ms=(time.perf_counter() - b.t0) * 1e3))
+                on_block(dict(queries=b.qb, **_models(cols), score_kernel_ms=ctx.last_kernel_ms(),
+                              lmers=ctx.last_comparisons(), kernel=ctx.last_kernel_name(),
+                              wall_ms=(time.perf_counter() - b.t0) * 1e3))
     return names, out
 
 
@@ -1350,18 +1388,29 @@ def default_scan_chunk(d, budget=BLOCK_BYTES):
 
 def check_scan(table, width, stride, chunk=None):
     """What `scan` refuses before it reads anything or touches the device."""
-    if not isinstance(table, LmerTable):
-        raise ModelError("scan: needs an l-mer weight table (gkmpredict weights), not a model")
-    check_table_model(table, "scan")
-    if int(width) < table.L:
-        raise ModelError("scan: the width %d is below L = %d" % (width, table.L))
+    _check_scan(LmerTable, "scan", table, width, stride, chunk)
+
+
+def _check_folded(want, what, folded):
+    """What every function that takes a table (want: LmerTable) or a panel (LmerPanel) refuses first: anything else."""
+    if not isinstance(folded, want):
+        raise ModelError("%s: needs an l-mer weight table (gkmpredict weights), not a model" % what if want is LmerTable else
+                         "%s: needs an l-mer weight panel (gkmpredict panel), not a table or a model" % what)
+    check_table_model(folded, what)
+
+
+def _check_scan(want, what, folded, width, stride, chunk):
+    """check_scan's and check_panel_scan's refusals; what: the prefix of every message"""
+    _check_folded(want, what, folded)
+    if int(width) < folded.L:
+        raise ModelError("%s: the width %d is below L = %d" % (what, width, folded.L))
     if int(width) > SCAN_MAX_WIDTH:
-        raise ModelError("scan: the width %d is above %d, the longest sequence a score is defined for"
-                         % (width, SCAN_MAX_WIDTH))
+        raise ModelError("%s: the width %d is above %d, the longest sequence a score is defined for"
+                         % (what, width, SCAN_MAX_WIDTH))
     if int(stride) < 1:
-        raise ModelError("scan: the stride must be at least 1")
+        raise ModelError("%s: the stride must be at least 1" % what)
     if chunk is not None and int(chunk) < int(width):
-        raise ModelError("scan: a chunk must hold at least one window (%d bases)" % width)
+        raise ModelError("%s: a chunk must hold at least one window (%d bases)" % (what, width))
 
 
 def scan(table, fasta_or_sequences, width, stride=1, device=0, chunk=None, on_chunk=None):
@@ -1373,25 +1422,33 @@ def scan(table, fasta_or_sequences, width, stride=1, device=0, chunk=None, on_ch
     chunk: bases per device chunk (default_scan_chunk).  on_chunk(dict) (measurements): called after every chunk with
     its windows, k_scan_profiles' milliseconds (HIP events), its l-mer comparisons and the chunk's wall time."""
     check_scan(table, width, stride, chunk)
-    width, stride = int(width), int(stride)
+    return _scan_folded(table, "scan", fasta_or_sequences, width, stride, device, chunk or default_scan_chunk(table.d),
+                        on_chunk)
+
+
+def _scan_folded(folded, what, fasta_or_sequences, width, stride, device, chunk, on_chunk):
+    """The body `scan` and `scan_with_panel` share -> [(name, starts, scores (windows,) + folded.cols)].  folded: the
+    table or panel (checked with width, stride and chunk); what: the prefix of the messages; chunk: bases per chunk."""
+    width, stride, chunk = int(width), int(stride), int(chunk)
     records = _as_scan_records(fasta_or_sequences)
     if not any(len(codes) >= width for _, codes, _ in records):
-        raise ModelError("scan: no record holds a window of %d bases" % width)
+        raise ModelError("%s: no record holds a window of %d bases" % (what, width))
     import torch
-    L, d = table.L, table.d
-    chunk = int(chunk) if chunk else default_scan_chunk(d)
-    ctx = dv.cached_context(*table.kernel_params(), device=device)
+    L, d, cols = folded.L, folded.d, folded.cols
+    ctx = dv.cached_context(*folded.kernel_params(), device=device)
     dev = torch.device("cuda", device)
-    c = dv.mismatch_weights(table.kernel_type, L, table.k)[:d + 1]
-    wt = dv.position_weights(table.kernel_type, width - L + 1, table.M, table.H)
+    c = dv.mismatch_weights(folded.kernel_type, L, folded.k)[:d + 1]
+    wt = dv.position_weights(folded.kernel_type, width - L + 1, folded.M, folded.H)
     out = []
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
-        W = torch.from_numpy(table.W).to(dev)
+        W = torch.from_numpy(folded.device_weights()).to(dev)
+        rho = _rho_operand(folded, dev)
         d_wt = torch.from_numpy(wt).to(dev)
+        launch = folded.launcher(ctx, "scan_score")
         for name, codes, valid in records:
             nw = scan_window_count(len(codes), width, stride)
-            scores = np.empty(nw)
+            scores = np.empty((nw,) + cols)
             ok = window_validity(valid, width, stride)
             for w0, w1, b0, b1 in scan_chunk_plan(len(codes), width, stride, chunk):
                 t0 = time.perf_counter()
@@ -1403,13 +1460,14 @@ def scan(table, fasta_or_sequences, width, stride=1, device=0, chunk=None, on_ch
                 prof = torch.empty((nwin, d + 1), dtype=torch.int64, device=dev)
                 ctx.scan_profiles(lm.data_ptr(), nlm, d_wt.data_ptr(), width, stride, nwin, prof.data_ptr(), stream)
                 if on_chunk is not None:
-                    info = dict(windows=nwin, bases=b1 - b0, profile_kernel_ms=ctx.last_kernel_ms(),
+                    info = dict(windows=nwin, bases=b1 - b0, **_models(cols), profile_kernel_ms=ctx.last_kernel_ms(),
                                 comparisons=ctx.last_comparisons(), kernel=ctx.last_kernel_name())
-                T = torch.empty(nwin, dtype=torch.float64, device=dev)
-                ctx.scan_score(lm.data_ptr(), nlm, d_wt.data_ptr(), width, stride, nwin, W.data_ptr(), T.data_ptr(),
-                               stream)
+                T = torch.empty((nwin,) + cols, dtype=torch.float64, device=dev)
+                launch(lm.data_ptr(), nlm, d_wt.data_ptr(), width, stride, nwin, W.data_ptr(), T.data_ptr(), stream)
+                if on_chunk is not None and cols:                          # (a panel reports its score kernel too)
+                    info.update(score_kernel=ctx.last_kernel_name(), score_kernel_ms=ctx.last_kernel_ms())
                 sq = _norms_from_profiles(prof, c)
-                scores[w0:w1] = (T / sq + table.rho).cpu().numpy()
+                scores[w0:w1] = (T / _per_item(sq, cols) + rho).cpu().numpy()
                 if on_chunk is not None:
                     info["wall_ms"] = (time.perf_counter() - t0) * 1e3
                     on_chunk(info)
@@ -1587,12 +1645,16 @@ def check_delta(table, variants=None, records=None, chunk=None):
     small for a context and, with `variants`, an allele with a character other than A, C, G, T or longer than
     DELTA_MAX_ALLELE after trimming and a negative position; with the `records` they refer to as well ([(name, codes,
     valid)], as read_long_fasta gives them), an unknown record and a position outside its record."""
-    if not isinstance(table, LmerTable):
-        raise ModelError("delta: needs an l-mer weight table (gkmpredict weights), not a model")
-    check_table_model(table, "delta")
-    if chunk is not None and int(chunk) < delta_min_chunk(table.L):
-        raise ModelError("delta: a chunk must hold a variant's context (at least %d bases for L = %d)"
-                         % (delta_min_chunk(table.L), table.L))
+    _check_delta(LmerTable, "delta", table, variants, records, chunk)
+
+
+def _check_delta(want, what, folded, variants, records, chunk):
+    """check_delta's and check_panel_delta's refusals; what: the prefix of the messages about the table or panel and the
+    chunk (a variant's are `delta:` either way)"""
+    _check_folded(want, what, folded)
+    if chunk is not None and int(chunk) < delta_min_chunk(folded.L):
+        raise ModelError("%s: a chunk must hold a variant's context (at least %d bases for L = %d)"
+                         % (what, delta_min_chunk(folded.L), folded.L))
     if variants is not None:
         _resolve_variants(records, list(variants), match=False)
 
@@ -1622,17 +1684,16 @@ def delta(table, fasta_or_sequences, variants, device=0, chunk=None, on_chunk=No
     chunk: bases per device chunk (default_delta_chunk).  on_chunk(dict) (measurements): called after every chunk with
     its variants, bases, k_delta_variants' milliseconds (HIP events), its gathers and the chunk's wall time."""
     check_delta(table, chunk=chunk)
-    return _delta_values(table, (), lambda: table.W, lambda ctx, *args: ctx.delta_variants(*args), fasta_or_sequences,
-                         variants, device, chunk, on_chunk)
+    return _delta_values(table, fasta_or_sequences, variants, device, chunk, on_chunk)
 
 
-def _delta_values(folded, cols, weights, launch, fasta_or_sequences, variants, device, chunk, on_chunk):
+def _delta_values(folded, fasta_or_sequences, variants, device, chunk, on_chunk):
     """The body `delta` and `delta_with_panel` share: the variants resolved, sorted and checked once, then one launch per
-    chunk -> float64 (len(variants),) + cols.  folded: the table or panel (checked), for L and the context; weights(): the
-    host array the launches read; launch(ctx, lm_ptr, codes_ptr, nbases, var, alt, W_ptr, out_ptr, stream)."""
+    chunk -> float64 (len(variants),) + folded.cols.  folded: the table or panel (checked)."""
     variants = list(variants)
     records = _as_scan_records(fasta_or_sequences)
     rec, pos, rlen, alts = _resolve_variants(records, variants)
+    cols = folded.cols
     out = np.empty((len(variants),) + cols)
     if not len(variants):
         return out
@@ -1644,7 +1705,8 @@ def _delta_values(folded, cols, weights, launch, fasta_or_sequences, variants, d
     dev = torch.device("cuda", device)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
-        W = torch.from_numpy(weights()).to(dev)
+        W = torch.from_numpy(folded.device_weights()).to(dev)
+        launch = folded.launcher(ctx, "delta_variants")
         for j in np.unique(rec).tolist():
             _, codes, valid = records[j]
             T = len(codes)
@@ -1663,16 +1725,13 @@ def _delta_values(folded, cols, weights, launch, fasta_or_sequences, variants, d
                 var[:, 2] = np.cumsum(alen[mine]) - alen[mine]
                 alt = np.frombuffer(b"".join([alts[i] for i in mine.tolist()]), dtype=np.uint8)
                 d_out = torch.empty((len(mine),) + cols, dtype=torch.float64, device=dev)
-                launch(ctx, lm.data_ptr() if lm is not None else None, d_codes.data_ptr(), b1 - b0, var, alt,
-                       W.data_ptr(), d_out.data_ptr(), stream)
-                out[mine] = np.where(ok[v0:v1].reshape((-1,) + (1,) * len(cols)), d_out.cpu().numpy(), np.nan)
+                launch(lm.data_ptr() if lm is not None else None, d_codes.data_ptr(), b1 - b0, var, alt, W.data_ptr(),
+                       d_out.data_ptr(), stream)
+                out[mine] = np.where(_per_item(ok[v0:v1], cols), d_out.cpu().numpy(), np.nan)
                 if on_chunk is not None:
-                    info = dict(variants=len(mine), bases=b1 - b0, kernel_ms=ctx.last_kernel_ms(),
-                                gathers=ctx.last_comparisons(), kernel=ctx.last_kernel_name(),
-                                wall_ms=(time.perf_counter() - t0) * 1e3)
-                    if cols:
-                        info["models"] = cols[0]
-                    on_chunk(info)
+                    on_chunk(dict(variants=len(mine), bases=b1 - b0, kernel_ms=ctx.last_kernel_ms(),
+                                  gathers=ctx.last_comparisons(), kernel=ctx.last_kernel_name(),
+                                  wall_ms=(time.perf_counter() - t0) * 1e3, **_models(cols)))
     return out
 
 
@@ -1685,30 +1744,36 @@ def delta_saturation(table, fasta_or_sequences, device=0, chunk=None, on_chunk=N
     chunk: bases per device chunk (default_delta_chunk).  on_chunk(dict) (measurements): called after every chunk with
     its positions, bases, k_delta_sat's milliseconds (HIP events), its gathers and the chunk's wall time."""
     check_delta(table, chunk=chunk)
+    return _saturation_folded(table, fasta_or_sequences, device, chunk or default_delta_chunk(), on_chunk)
+
+
+def _saturation_folded(folded, fasta_or_sequences, device, chunk, on_chunk):
+    """The body `delta_saturation` and `delta_saturation_with_panel` share -> [(name, (T, 4) + folded.cols)].  folded: the
+    table or panel (checked with chunk); chunk: bases per chunk."""
     records = _as_scan_records(fasta_or_sequences)
-    L = table.L
+    L, cols, chunk = folded.L, folded.cols, int(chunk)
     for name, codes, _ in records:
         if len(codes) < L:
             raise ModelError("delta-saturation: record %r has %d bases, fewer than L = %d" % (name, len(codes), L))
     import torch
-    chunk = int(chunk) if chunk else default_delta_chunk()
-    ctx = dv.cached_context(*table.kernel_params(), device=device)
+    ctx = dv.cached_context(*folded.kernel_params(), device=device)
     dev = torch.device("cuda", device)
     out = []
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
-        W = torch.from_numpy(table.W).to(dev)
+        W = torch.from_numpy(folded.device_weights()).to(dev)
+        launch = folded.launcher(ctx, "delta_sat")
         for name, codes, valid in records:
             T = len(codes)
-            D = np.empty((T, 4))
+            D = np.empty((T, 4) + cols)
             for t0, t1, b0, b1 in delta_saturation_chunk_plan(T, L, chunk):
                 w0 = time.perf_counter()
                 _, lm = _delta_upload(ctx, codes, valid, b0, b1, L, dev, stream)
-                d_out = torch.empty((t1 - t0, 4), dtype=torch.float64, device=dev)
-                ctx.delta_sat(lm.data_ptr(), len(lm), t0 - b0, t1 - b0, W.data_ptr(), d_out.data_ptr(), stream)
+                d_out = torch.empty((t1 - t0, 4) + cols, dtype=torch.float64, device=dev)
+                launch(lm.data_ptr(), len(lm), t0 - b0, t1 - b0, W.data_ptr(), d_out.data_ptr(), stream)
                 D[t0:t1] = d_out.cpu().numpy()
                 if on_chunk is not None:
-                    on_chunk(dict(positions=t1 - t0, bases=b1 - b0, kernel_ms=ctx.last_kernel_ms(),
+                    on_chunk(dict(positions=t1 - t0, bases=b1 - b0, **_models(cols), kernel_ms=ctx.last_kernel_ms(),
                                   gathers=ctx.last_comparisons(), kernel=ctx.last_kernel_name(),
                                   wall_ms=(time.perf_counter() - w0) * 1e3))
             out.append((name, D))
@@ -1797,6 +1862,8 @@ PANEL_MAX_BYTES = 8 << 30       # the device image 4^L * ms * 8 of a panel, at m
 _PANEL_SHARED = ("kernel_type", "L", "k", "d", "M", "H")
 _PANEL_INTS = ("kernel_type", "L", "k", "d", "M")
 _PANEL_KEYS = ("format",) + _PANEL_SHARED + ("names", "rho", "W")
+_PANEL_LAUNCH = dict(lmer_score="panel_score", scan_score="panel_scan_score", delta_sat="panel_delta_sat",
+                     delta_variants="panel_delta_variants")    # a table's launch -> the panel's (LmerPanel.launcher)
 
 
 def panel_row_stride(n_models):
@@ -1874,6 +1941,16 @@ class LmerPanel(_FoldedModel):
         P[:, :self.n_models] = self.W
         return P
 
+    # LmerTable's members for the shared drivers: the model index is the last axis of every result
+    cols = property(lambda self: (self.n_models,))
+    device_weights = device_rows
+
+    def launcher(self, ctx, name):
+        """LmerTable.launcher's counterpart, called the same way: the context's panel launch with n_models and the row
+        stride bound behind the weights pointer."""
+        method, nm, ms = getattr(ctx, _PANEL_LAUNCH[name]), self.n_models, panel_row_stride(self.n_models)
+        return lambda *args: method(*args[:-2], nm, ms, *args[-2:])
+
     def save(self, path):
         """Write the panel file (format: INTEGRATION.md §5b) to exactly `path`: an uncompressed .npz with the format tag,
         the six shared parameters, names, rho and the rows of the canonical l-mers in ascending order (W[rc(u)] ==
@@ -1939,9 +2016,7 @@ def load_lmer_panel(path):
 
 def check_panel(panel, what):
     """What every panel function refuses first: a table or a model where a panel is needed."""
-    if not isinstance(panel, LmerPanel):
-        raise ModelError("%s: needs an l-mer weight panel (gkmpredict panel), not a table or a model" % what)
-    check_table_model(panel, what)
+    _check_folded(LmerPanel, what, panel)
 
 
 def score_with_panel(panel, fasta_or_sequences, device=0, block=None, on_block=None):
@@ -1949,25 +2024,8 @@ def score_with_panel(panel, fasta_or_sequences, device=0, block=None, on_block=N
     result for member m, bit for bit, whatever the block size.  Per block the exact self norms once (they depend on the
     shared parameters only) and one k_panel_score launch: one row read per l-mer for all models.
     on_block(dict) (measurements): score_with_table's keys and `models`."""
-    import torch
     check_panel(panel, "predict-panel")
-    seqs, names = _as_queries(fasta_or_sequences)
-    check_queries(panel, seqs)
-    blocks = _Blocks(panel, seqs, device, block, default_table_block(_longest(seqs)), exact=True)
-    ctx, sq, dev = blocks.ctx, blocks.sq, blocks.dev
-    nm, ms = panel.n_models, panel_row_stride(panel.n_models)
-    out = np.empty((len(seqs), nm))
-    with torch.cuda.device(dev):
-        P = torch.from_numpy(panel.device_rows()).to(dev)
-        rho = torch.from_numpy(panel.rho).to(dev)
-        T = torch.empty((blocks.qb_max, nm), dtype=torch.float64, device=dev)
-        for b in blocks:
-            ctx.panel_score(0, b.qb, P.data_ptr(), nm, ms, T.data_ptr(), blocks.stream)
-            out[b.q0:b.q1] = (T[:b.qb] / sq[:b.qb, None] + rho[None, :]).cpu().numpy()
-            if on_block is not None:
-                on_block(dict(queries=b.qb, models=nm, score_kernel_ms=ctx.last_kernel_ms(), lmers=ctx.last_comparisons(),
-                              kernel=ctx.last_kernel_name(), wall_ms=(time.perf_counter() - b.t0) * 1e3))
-    return names, out
+    return _score_folded(panel, fasta_or_sequences, device, block, on_block)
 
 
 def default_panel_scan_chunk(d, n_models, budget=BLOCK_BYTES):
@@ -1977,16 +2035,7 @@ def default_panel_scan_chunk(d, n_models, budget=BLOCK_BYTES):
 
 def check_panel_scan(panel, width, stride, chunk=None):
     """What `scan_with_panel` refuses before it reads anything or touches the device (check_scan's refusals)."""
-    check_panel(panel, "scan-panel")
-    if int(width) < panel.L:
-        raise ModelError("scan-panel: the width %d is below L = %d" % (width, panel.L))
-    if int(width) > SCAN_MAX_WIDTH:
-        raise ModelError("scan-panel: the width %d is above %d, the longest sequence a score is defined for"
-                         % (width, SCAN_MAX_WIDTH))
-    if int(stride) < 1:
-        raise ModelError("scan-panel: the stride must be at least 1")
-    if chunk is not None and int(chunk) < int(width):
-        raise ModelError("scan-panel: a chunk must hold at least one window (%d bases)" % width)
+    _check_scan(LmerPanel, "scan-panel", panel, width, stride, chunk)
 
 
 def scan_with_panel(panel, fasta_or_sequences, width, stride=1, device=0, chunk=None, on_chunk=None):
@@ -1997,63 +2046,14 @@ def scan_with_panel(panel, fasta_or_sequences, width, stride=1, device=0, chunk=
     chunk: bases per device chunk (default_panel_scan_chunk).  on_chunk(dict) (measurements): scan's keys, `models`,
     `score_kernel` and `score_kernel_ms`."""
     check_panel_scan(panel, width, stride, chunk)
-    width, stride = int(width), int(stride)
-    records = _as_scan_records(fasta_or_sequences)
-    if not any(len(codes) >= width for _, codes, _ in records):
-        raise ModelError("scan-panel: no record holds a window of %d bases" % width)
-    import torch
-    L, d, nm, ms = panel.L, panel.d, panel.n_models, panel_row_stride(panel.n_models)
-    chunk = int(chunk) if chunk else default_panel_scan_chunk(d, nm)
-    ctx = dv.cached_context(*panel.kernel_params(), device=device)
-    dev = torch.device("cuda", device)
-    c = dv.mismatch_weights(panel.kernel_type, L, panel.k)[:d + 1]
-    wt = dv.position_weights(panel.kernel_type, width - L + 1, panel.M, panel.H)
-    out = []
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        P = torch.from_numpy(panel.device_rows()).to(dev)
-        rho = torch.from_numpy(panel.rho).to(dev)
-        d_wt = torch.from_numpy(wt).to(dev)
-        for name, codes, valid in records:
-            nw = scan_window_count(len(codes), width, stride)
-            scores = np.empty((nw, nm))
-            ok = window_validity(valid, width, stride)
-            for w0, w1, b0, b1 in scan_chunk_plan(len(codes), width, stride, chunk):
-                t0 = time.perf_counter()
-                d_codes = torch.from_numpy(codes[b0:b1]).to(dev)
-                d_valid = torch.from_numpy(valid[b0:b1].view(np.uint8)).to(dev)
-                nlm, nwin = b1 - b0 - L + 1, w1 - w0
-                lm = torch.empty(nlm, dtype=torch.int32, device=dev)
-                ctx.scan_lmers(d_codes.data_ptr(), d_valid.data_ptr(), b1 - b0, lm.data_ptr(), stream)
-                prof = torch.empty((nwin, d + 1), dtype=torch.int64, device=dev)
-                ctx.scan_profiles(lm.data_ptr(), nlm, d_wt.data_ptr(), width, stride, nwin, prof.data_ptr(), stream)
-                if on_chunk is not None:
-                    info = dict(windows=nwin, bases=b1 - b0, models=nm, profile_kernel_ms=ctx.last_kernel_ms(),
-                                comparisons=ctx.last_comparisons(), kernel=ctx.last_kernel_name())
-                T = torch.empty((nwin, nm), dtype=torch.float64, device=dev)
-                ctx.panel_scan_score(lm.data_ptr(), nlm, d_wt.data_ptr(), width, stride, nwin, P.data_ptr(), nm, ms,
-                                     T.data_ptr(), stream)
-                if on_chunk is not None:
-                    info.update(score_kernel=ctx.last_kernel_name(), score_kernel_ms=ctx.last_kernel_ms())
-                sq = _norms_from_profiles(prof, c)
-                scores[w0:w1] = (T / sq[:, None] + rho[None, :]).cpu().numpy()
-                if on_chunk is not None:
-                    info["wall_ms"] = (time.perf_counter() - t0) * 1e3
-                    on_chunk(info)
-            scores[~ok] = np.nan
-            out.append((name, np.arange(nw, dtype=np.int64) * stride, scores))
-    return out
+    return _scan_folded(panel, "scan-panel", fasta_or_sequences, width, stride, device,
+                        chunk or default_panel_scan_chunk(panel.d, panel.n_models), on_chunk)
 
 
 def check_panel_delta(panel, variants=None, records=None, chunk=None):
     """What `delta_with_panel` and `delta_saturation_with_panel` refuse before they touch the device (check_delta's
     refusals)."""
-    check_panel(panel, "delta-panel")
-    if chunk is not None and int(chunk) < delta_min_chunk(panel.L):
-        raise ModelError("delta-panel: a chunk must hold a variant's context (at least %d bases for L = %d)"
-                         % (delta_min_chunk(panel.L), panel.L))
-    if variants is not None:
-        _resolve_variants(records, list(variants), match=False)
+    _check_delta(LmerPanel, "delta-panel", panel, variants, records, chunk)
 
 
 def delta_with_panel(panel, fasta_or_sequences, variants, device=0, chunk=None, on_chunk=None):
@@ -2062,11 +2062,7 @@ def delta_with_panel(panel, fasta_or_sequences, variants, device=0, chunk=None, 
     are the same).  The variants are resolved, sorted and checked once -- most of delta's time -- and each chunk is one
     k_panel_delta_variants launch.  on_chunk(dict) (measurements): delta's keys and `models`."""
     check_panel_delta(panel, chunk=chunk)
-    nm, ms = panel.n_models, panel_row_stride(panel.n_models)
-    return _delta_values(panel, (nm,), panel.device_rows,
-                         lambda ctx, lm, codes, nbases, var, alt, P, out, stream:
-                         ctx.panel_delta_variants(lm, codes, nbases, var, alt, P, nm, ms, out, stream),
-                         fasta_or_sequences, variants, device, chunk, on_chunk)
+    return _delta_values(panel, fasta_or_sequences, variants, device, chunk, on_chunk)
 
 
 def delta_saturation_with_panel(panel, fasta_or_sequences, device=0, chunk=None, on_chunk=None):
@@ -2074,34 +2070,8 @@ def delta_saturation_with_panel(panel, fasta_or_sequences, device=0, chunk=None,
     delta_saturation's map for member m, bit for bit, and D[t, b, m] is delta_with_panel's value of that SNV.
     on_chunk(dict) (measurements): delta_saturation's keys and `models`."""
     check_panel_delta(panel, chunk=chunk)
-    records = _as_scan_records(fasta_or_sequences)
-    L, nm, ms = panel.L, panel.n_models, panel_row_stride(panel.n_models)
-    for name, codes, _ in records:
-        if len(codes) < L:
-            raise ModelError("delta-saturation: record %r has %d bases, fewer than L = %d" % (name, len(codes), L))
-    import torch
-    chunk = int(chunk) if chunk else max(delta_min_chunk(L), int(BLOCK_BYTES // (16 + 32 * nm)))
-    ctx = dv.cached_context(*panel.kernel_params(), device=device)
-    dev = torch.device("cuda", device)
-    out = []
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        P = torch.from_numpy(panel.device_rows()).to(dev)
-        for name, codes, valid in records:
-            T = len(codes)
-            D = np.empty((T, 4, nm))
-            for t0, t1, b0, b1 in delta_saturation_chunk_plan(T, L, chunk):
-                w0 = time.perf_counter()
-                _, lm = _delta_upload(ctx, codes, valid, b0, b1, L, dev, stream)
-                d_out = torch.empty((t1 - t0, 4, nm), dtype=torch.float64, device=dev)
-                ctx.panel_delta_sat(lm.data_ptr(), len(lm), t0 - b0, t1 - b0, P.data_ptr(), nm, ms, d_out.data_ptr(), stream)
-                D[t0:t1] = d_out.cpu().numpy()
-                if on_chunk is not None:
-                    on_chunk(dict(positions=t1 - t0, bases=b1 - b0, models=nm, kernel_ms=ctx.last_kernel_ms(),
-                                  gathers=ctx.last_comparisons(), kernel=ctx.last_kernel_name(),
-                                  wall_ms=(time.perf_counter() - w0) * 1e3))
-            out.append((name, D))
-    return out
+    return _saturation_folded(panel, fasta_or_sequences, device, chunk or
+                              max(delta_min_chunk(panel.L), int(BLOCK_BYTES // (16 + 32 * panel.n_models))), on_chunk)
 
 
 def _panel_row(lead, values):

@@ -325,7 +325,7 @@ int gkmhip_delta_sat(gkmhip_ctx *ctx, const uint32_t *lm, int64_t nlm, int64_t t
 int gkmhip_delta_variants(gkmhip_ctx *ctx, const uint32_t *lm, const uint8_t *codes, int64_t nbases, const int32_t *var,
                           int nvar, const uint8_t *alt, int64_t nalt, const double *W, double *out, void *stream);
 
-/* ---- l-mer weight panels: many tables per lookup (gkm_panel.hip) ----
+/* ---- l-mer weight panels: many tables per lookup (gkm_panel.hip, gkm_delta.hip) ----
  * nm tables (1 <= nm <= GKMHIP_PANEL_MAX) that share the context's parameters, interleaved: P[u * ms + m] = W_m[u], DEVICE,
  * 4^L rows of ms doubles, ms >= nm and ms % 8 == 0 (rows of whole 64-byte lines), what lies beyond column nm never
  * surfaces.  Each call is its single-table counterpart for every model at once -- the same arguments, the same refusals

@@ -255,6 +255,54 @@ def test_api_refuses_before_it_touches_the_device(gp):
         gp.scan(panel, [x], 8)
 
 
+def _refusal(gp, call):
+    with pytest.raises(gp.ModelError) as e:
+        call()
+    return str(e.value)
+
+
+def test_panel_checks_refuse_what_the_table_checks_refuse(gp):
+    """check_panel_scan / check_panel_delta share their bodies with check_scan / check_delta: the same bad argument gives
+    the same message behind the prefix.  The texts are written out here, not taken from the code under test."""
+    table, panel = _table(gp), gp.LmerPanel(_tables(gp, 2))
+    rbf_table, rbf_panel = _table(gp, kernel_type=2), gp.LmerPanel(_tables(gp, 2))
+    rbf_table.kernel_type = rbf_panel.kernel_type = 3                      # (no constructor hands one out)
+    rbf = "RBF kernels (types 3 and 5) have no l-mer weight table (their score is not linear in the query's l-mers)"
+    scans = [((4, 1, None), "the width 4 is below L = 5"),
+             ((2048, 1, None), "the width 2048 is above 2047, the longest sequence a score is defined for"),
+             ((8, 0, None), "the stride must be at least 1"),
+             ((8, 1, 7), "a chunk must hold at least one window (8 bases)")]
+    for args, text in scans:
+        assert _refusal(gp, lambda: gp.check_scan(table, *args)) == "scan: " + text
+        assert _refusal(gp, lambda: gp.check_panel_scan(panel, *args)) == "scan-panel: " + text
+    assert _refusal(gp, lambda: gp.check_scan(rbf_table, 8, 1)) == "scan: " + rbf
+    assert _refusal(gp, lambda: gp.check_panel_scan(rbf_panel, 8, 1)) == "scan-panel: " + rbf
+    assert gp.delta_min_chunk(5) == 264
+    chunk = "a chunk must hold a variant's context (at least 264 bases for L = 5)"
+    assert _refusal(gp, lambda: gp.check_delta(table, chunk=263)) == "delta: " + chunk
+    assert _refusal(gp, lambda: gp.check_panel_delta(panel, chunk=263)) == "delta-panel: " + chunk
+    assert _refusal(gp, lambda: gp.check_delta(rbf_table)) == "delta: " + rbf
+    assert _refusal(gp, lambda: gp.check_panel_delta(rbf_panel)) == "delta-panel: " + rbf
+    # a bad variant is `delta:`'s on either side
+    allele = "delta: variant 0 (0, 0, 'A', 'N'): an allele holds a character other than A, C, G, T"
+    assert _refusal(gp, lambda: gp.check_delta(table, variants=[(0, 0, "A", "N")])) == allele
+    assert _refusal(gp, lambda: gp.check_panel_delta(panel, variants=[(0, 0, "A", "N")])) == allele
+    # the wrong object: each side names what it needs
+    for wrong in (object(), panel):
+        assert _refusal(gp, lambda: gp.check_scan(wrong, 8, 1)) == \
+            "scan: needs an l-mer weight table (gkmpredict weights), not a model"
+        assert _refusal(gp, lambda: gp.check_delta(wrong)) == \
+            "delta: needs an l-mer weight table (gkmpredict weights), not a model"
+    for wrong in (object(), table):
+        assert _refusal(gp, lambda: gp.check_panel_scan(wrong, 8, 1)) == \
+            "scan-panel: needs an l-mer weight panel (gkmpredict panel), not a table or a model"
+        assert _refusal(gp, lambda: gp.check_panel_delta(wrong)) == \
+            "delta-panel: needs an l-mer weight panel (gkmpredict panel), not a table or a model"
+    # and nothing is refused that was not
+    assert gp.check_scan(table, 8, 1, 8) is None and gp.check_panel_scan(panel, 8, 1, 8) is None
+    assert gp.check_delta(table, chunk=264) is None and gp.check_panel_delta(panel, chunk=264) is None
+
+
 def test_panel_output_files_round_trip(gp, tmp_path):
     path = str(tmp_path / "o.tsv")
     names = ["a.txt", "b"]
