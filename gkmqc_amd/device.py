@@ -143,6 +143,16 @@ def load():
     L.gkmhip_scan_score.argtypes = (vp, vp, i64, vp, i32, i32, i64, vp, vp, vp)
     L.gkmhip_scan_group.restype = i32
     L.gkmhip_scan_group.argtypes = (vp, i32, i32)
+    if hasattr(L, "gkmhip_regions_count"):   # (as the panel calls below: older builds lack them; GramContext's
+                                             # region methods say so when called on one)
+        L.gkmhip_regions_scratch_bytes.restype = i64
+        L.gkmhip_regions_scratch_bytes.argtypes = (i64, i64)
+        L.gkmhip_regions_count.restype = i32
+        L.gkmhip_regions_count.argtypes = (vp, vp, i64, vp, i64, i32, i32, i64, dbl, i64, vp, i64, vp, vp)
+        L.gkmhip_regions_fill.restype = i32
+        L.gkmhip_regions_fill.argtypes = (vp, vp, i64, vp, i64, i32, i32, i64, dbl, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp)
+        L.gkmhip_regions_span.restype = i32
+        L.gkmhip_regions_span.argtypes = ()
     L.gkmhip_delta_sat.restype = i32
     L.gkmhip_delta_sat.argtypes = (vp, vp, i64, i64, i64, vp, vp, vp)
     L.gkmhip_delta_variants.restype = i32
@@ -569,6 +579,42 @@ class GramContext:
     def scan_group(self, width, stride):
         """Windows per stretch of k_scan_profiles for (L, width, stride); 0 where the scan refuses them."""
         return self.lib.gkmhip_scan_group(self.handle, int(width), int(stride))
+
+    def _need_regions(self):
+        if not hasattr(self.lib, "gkmhip_regions_count"):
+            raise GkmError("%s holds no gkmhip_regions_count: it was built before the region calls" % lib_path())
+
+    def regions_scratch_bytes(self, nlm, nwin):
+        """Device bytes regions_count and regions_fill need for nwin windows over nlm l-mer words; -1 where refused."""
+        self._need_regions()
+        return self.lib.gkmhip_regions_scratch_bytes(int(nlm), int(nwin))
+
+    def regions_span(self):
+        """Windows one workgroup of the region kernels owns."""
+        self._need_regions()
+        return self.lib.gkmhip_regions_span()
+
+    def regions_count(self, score_ptr, ld, lm_ptr, nlm, width, stride, nwin, threshold, gap, scratch_ptr, scratch_bytes,
+                      stream=0):
+        """-> the regions among the nwin windows of a scan launch whose finished scores are score_ptr[i * ld] (device
+        doubles): runs of windows without a flagged word and with a score >= threshold, at most `gap` others between two
+        of them (include/gkm_hip.h gkmhip_regions_count).  Waits for the stream."""
+        self._need_regions()
+        count = ctypes.c_int64(-1)
+        self._chk(self.lib.gkmhip_regions_count(self.handle, score_ptr, int(ld), lm_ptr, int(nlm), int(width), int(stride),
+                                                int(nwin), float(threshold), int(gap), scratch_ptr, int(scratch_bytes),
+                                                ctypes.addressof(count), stream), "gkmhip_regions_count")
+        return count.value
+
+    def regions_fill(self, score_ptr, ld, lm_ptr, nlm, width, stride, nwin, threshold, gap, scratch_ptr, scratch_bytes,
+                     capacity, first_ptr, last_ptr, summit_ptr, windows_ptr, peak_ptr, stream=0):
+        """After regions_count with the same arguments and scratch: the regions' first, last and summit windows and window
+        counts (int32) and peaks (float64) into device arrays of `capacity` elements (gkmhip_regions_fill)."""
+        self._need_regions()
+        self._chk(self.lib.gkmhip_regions_fill(self.handle, score_ptr, int(ld), lm_ptr, int(nlm), int(width), int(stride),
+                                               int(nwin), float(threshold), int(gap), scratch_ptr, int(scratch_bytes),
+                                               int(capacity), first_ptr, last_ptr, summit_ptr, windows_ptr, peak_ptr,
+                                               stream), "gkmhip_regions_fill")
 
     def delta_sat(self, lm_ptr, nlm, t_begin, t_end, W_ptr, out_ptr, stream=0):
         """Every SNV of the positions [t_begin, t_end) of the bases the nlm words at lm_ptr cover -> out_ptr, (t_end -

@@ -1429,29 +1429,61 @@ def scan(table, fasta_or_sequences, width, stride=1, device=0, chunk=None, on_ch
 def _scan_folded(folded, what, fasta_or_sequences, width, stride, device, chunk, on_chunk):
     """The body `scan` and `scan_with_panel` share -> [(name, starts, scores (windows,) + folded.cols)].  folded: the
     table or panel (checked with width, stride and chunk); what: the prefix of the messages; chunk: bases per chunk."""
-    width, stride, chunk = int(width), int(stride), int(chunk)
+    width, stride = int(width), int(stride)
+    records = _scan_records(what, fasta_or_sequences, width)
+    out = []
+    for name, codes, valid in records:
+        nw = scan_window_count(len(codes), width, stride)
+        out.append((name, np.arange(nw, dtype=np.int64) * stride, np.empty((nw,) + folded.cols)))
+    for ch in _scan_chunks(folded, records, width, stride, device, chunk, on_chunk is not None):
+        out[ch.record][2][ch.w0:ch.w1] = ch.scores.cpu().numpy()
+        if on_chunk is not None:
+            ch.info["wall_ms"] = (time.perf_counter() - ch.t0) * 1e3
+            on_chunk(ch.info)
+    for (_, _, valid), (_, _, scores) in zip(records, out):
+        scores[~window_validity(valid, width, stride)] = np.nan
+    return out
+
+
+def _scan_records(what, fasta_or_sequences, width):
+    """The records of a scan, or the refusal every scan shares: none of them holds a window."""
     records = _as_scan_records(fasta_or_sequences)
     if not any(len(codes) >= width for _, codes, _ in records):
         raise ModelError("%s: no record holds a window of %d bases" % (what, width))
+    return records
+
+
+class _ScanChunk:
+    """What the chunk loop hands over per chunk, all of it on the device: the windows [w0, w1) of records[record], the
+    chunk's nlm l-mer words (int32 tensor lm) and the windows' finished scores ((windows,) + folded.cols, rho included;
+    whatever stands at a window over an invalid base is not a score).  ctx, stream: for further launches on the chunk;
+    info: the measurements so far (None unless asked for); t0: when the chunk began."""
+    __slots__ = ("record", "w0", "w1", "lm", "nlm", "scores", "ctx", "stream", "info", "t0")
+
+
+def _scan_chunks(folded, records, width, stride, device, chunk, measure, score_ms=False):
+    """The chunk loop of every scan, a generator of _ScanChunk: per chunk of each record the upload, the l-mer words, the
+    windows' self profiles (k_scan_profiles), the table's or panel's score launch and the epilogue T / sq + rho.  The
+    consumer runs between two chunks, on the loop's device and stream.  measure: fill info with scan's on_chunk keys;
+    score_ms: a table reports its score kernel too."""
     import torch
+    chunk = int(chunk)
     L, d, cols = folded.L, folded.d, folded.cols
     ctx = dv.cached_context(*folded.kernel_params(), device=device)
     dev = torch.device("cuda", device)
     c = dv.mismatch_weights(folded.kernel_type, L, folded.k)[:d + 1]
     wt = dv.position_weights(folded.kernel_type, width - L + 1, folded.M, folded.H)
-    out = []
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
         W = torch.from_numpy(folded.device_weights()).to(dev)
         rho = _rho_operand(folded, dev)
         d_wt = torch.from_numpy(wt).to(dev)
         launch = folded.launcher(ctx, "scan_score")
-        for name, codes, valid in records:
-            nw = scan_window_count(len(codes), width, stride)
-            scores = np.empty((nw,) + cols)
-            ok = window_validity(valid, width, stride)
+        for r, (name, codes, valid) in enumerate(records):
             for w0, w1, b0, b1 in scan_chunk_plan(len(codes), width, stride, chunk):
-                t0 = time.perf_counter()
+                ch = _ScanChunk()
+                ch.record, ch.w0, ch.w1, ch.ctx, ch.stream, ch.info = r, w0, w1, ctx, stream, None
+                ch.t0 = time.perf_counter()
                 d_codes = torch.from_numpy(codes[b0:b1]).to(dev)
                 d_valid = torch.from_numpy(valid[b0:b1].view(np.uint8)).to(dev)
                 nlm, nwin = b1 - b0 - L + 1, w1 - w0
@@ -1459,21 +1491,16 @@ def _scan_folded(folded, what, fasta_or_sequences, width, stride, device, chunk,
                 ctx.scan_lmers(d_codes.data_ptr(), d_valid.data_ptr(), b1 - b0, lm.data_ptr(), stream)
                 prof = torch.empty((nwin, d + 1), dtype=torch.int64, device=dev)
                 ctx.scan_profiles(lm.data_ptr(), nlm, d_wt.data_ptr(), width, stride, nwin, prof.data_ptr(), stream)
-                if on_chunk is not None:
-                    info = dict(windows=nwin, bases=b1 - b0, **_models(cols), profile_kernel_ms=ctx.last_kernel_ms(),
-                                comparisons=ctx.last_comparisons(), kernel=ctx.last_kernel_name())
+                if measure:
+                    ch.info = dict(windows=nwin, bases=b1 - b0, **_models(cols), profile_kernel_ms=ctx.last_kernel_ms(),
+                                   comparisons=ctx.last_comparisons(), kernel=ctx.last_kernel_name())
                 T = torch.empty((nwin,) + cols, dtype=torch.float64, device=dev)
                 launch(lm.data_ptr(), nlm, d_wt.data_ptr(), width, stride, nwin, W.data_ptr(), T.data_ptr(), stream)
-                if on_chunk is not None and cols:                          # (a panel reports its score kernel too)
-                    info.update(score_kernel=ctx.last_kernel_name(), score_kernel_ms=ctx.last_kernel_ms())
+                if measure and (cols or score_ms):                         # (a panel reports its score kernel too)
+                    ch.info.update(score_kernel=ctx.last_kernel_name(), score_kernel_ms=ctx.last_kernel_ms())
                 sq = _norms_from_profiles(prof, c)
-                scores[w0:w1] = (T / _per_item(sq, cols) + rho).cpu().numpy()
-                if on_chunk is not None:
-                    info["wall_ms"] = (time.perf_counter() - t0) * 1e3
-                    on_chunk(info)
-            scores[~ok] = np.nan
-            out.append((name, np.arange(nw, dtype=np.int64) * stride, scores))
-    return out
+                ch.lm, ch.nlm, ch.scores = lm, nlm, T / _per_item(sq, cols) + rho
+                yield ch
 
 
 def write_scan(path, results, width):
@@ -1499,6 +1526,171 @@ def read_scan(path):
         for line in f.read().split("\n")[:-1]:
             name, a, b, v = line.rsplit("\t", 3)
             out.append((name, int(a), int(b), float(v)))
+    return out
+
+
+# ------------------------------------------------------------------ regions of a scan
+REGION_FIELDS = ("start", "end", "peak", "summit", "windows")   # the arrays of a `regions` dict, in file order
+_REGION_KEYS = ("first", "last", "summit", "windows", "peak")   # of a region in window indices, as the device reports it
+REGION_MAX_GAP = 1 << 40  # the largest gap the device layer takes (gkmhip_regions_count)
+
+
+def _check_regions(what, threshold, gap, n_models=None):
+    """The refusals `scan_regions` adds to `scan`'s -> the thresholds, one float per member (one in all for a table)."""
+    if isinstance(gap, bool) or not isinstance(gap, (int, np.integer)):
+        raise ModelError("%s: the gap must be an integer, not %r" % (what, gap))
+    if gap < 0:
+        raise ModelError("%s: the gap must be at least 0" % what)
+    if gap > REGION_MAX_GAP:
+        raise ModelError("%s: the gap must be at most 2^40 windows" % what)
+    if n_models is None or np.ndim(threshold) == 0:
+        values = [threshold] * (n_models or 1)
+    else:
+        values = list(threshold)
+        if len(values) != n_models:
+            raise ModelError("%s: %d thresholds for the panel's %d members" % (what, len(values), n_models))
+    try:
+        values = [float(v) for v in values]
+    except (TypeError, ValueError):
+        raise ModelError("%s: the threshold must be a number%s" % (what, "" if n_models is None else " or one per member"))
+    if any(v != v for v in values):
+        raise ModelError("%s: the threshold is NaN" % what)
+    return values
+
+
+def check_scan_regions(table, width, stride, threshold=0.0, gap=0, chunk=None):
+    """What `scan_regions` refuses before it reads anything or touches the device: check_scan's refusals, a gap that is
+    negative, above 2^40 or no integer, a NaN threshold.  -> the threshold as a float."""
+    _check_scan(LmerTable, "scan-regions", table, width, stride, chunk)
+    return _check_regions("scan-regions", threshold, gap)[0]
+
+
+def check_panel_scan_regions(panel, width, stride, threshold=0.0, gap=0, chunk=None):
+    """check_scan_regions for `scan_regions_with_panel`: check_panel_scan's refusals, the gap, and the thresholds -- one
+    for all members or one per member, none of them NaN.  -> the thresholds, one float per member."""
+    _check_scan(LmerPanel, "scan-regions-panel", panel, width, stride, chunk)
+    return _check_regions("scan-regions-panel", threshold, gap, panel.n_models)
+
+
+def _no_regions():
+    return dict(first=np.empty(0, np.int64), last=np.empty(0, np.int64), summit=np.empty(0, np.int64),
+                windows=np.empty(0, np.int64), peak=np.empty(0, np.float64))
+
+
+def stitch_regions(per_chunk, gap):
+    """The regions of a record's chunks, each found as if its chunk stood alone -> the record's.  per_chunk: one dict per
+    chunk, in order, of the arrays first, last, summit, windows (integers) and peak (float64) in the RECORD's window
+    indices, ascending.  A region merges with the one before it when its first window lies within gap + 1 of that one's
+    last (inside a chunk none does; across chunk boundaries a merge may cascade): the merged region runs from the first
+    one's `first` to the last one's `last`, its windows add up, and its peak and summit are those of the part with the
+    largest peak, the earliest such part on a tie.  Only the order of the regions enters, not how they are divided among
+    the dicts.  -> a dict of the same five arrays (int64, float64)."""
+    parts = [c for c in per_chunk if len(c["first"])]
+    if not parts:
+        return _no_regions()
+    first, last, summit, windows = (np.concatenate([np.asarray(c[key], dtype=np.int64) for c in parts])
+                                    for key in _REGION_KEYS[:4])
+    peak = np.concatenate([np.asarray(c["peak"], dtype=np.float64) for c in parts])
+    begins = np.ones(len(first), dtype=bool)
+    begins[1:] = first[1:] - last[:-1] > int(gap) + 1
+    at = np.flatnonzero(begins)
+    group = np.cumsum(begins) - 1
+    top = np.flatnonzero(peak == np.maximum.reduceat(peak, at)[group])     # the parts that attain their region's peak
+    top = top[np.concatenate(([True], group[top][1:] != group[top][:-1]))]  # the earliest of each region
+    return dict(first=first[at], last=last[np.append(at[1:], len(first)) - 1], summit=summit[top],
+                windows=np.add.reduceat(windows, at), peak=peak[top])
+
+
+def _regions_in_bases(r, width, stride):
+    """a region dict in window indices -> the `regions` dict of scan_regions, in bases"""
+    return dict(start=r["first"] * stride, end=r["last"] * stride + width, peak=r["peak"], summit=r["summit"] * stride,
+                windows=r["windows"])
+
+
+def _chunk_regions(ch, col, ld, width, stride, threshold, gap, scratch):
+    """The regions of column `col` of a chunk's scores, in the record's window indices -> (dict, bytes copied back,
+    the region kernels' milliseconds).  Only the count and the regions themselves leave the device."""
+    import torch
+    ctx, nwin = ch.ctx, ch.w1 - ch.w0
+    args = (ch.scores.data_ptr() + 8 * col, ld, ch.lm.data_ptr(), ch.nlm, width, stride, nwin, threshold, gap,
+            scratch.data_ptr(), scratch.numel())
+    n = ctx.regions_count(*args, ch.stream)
+    ms = ctx.last_kernel_ms() if ch.info is not None else 0.0
+    if n == 0:
+        return _no_regions(), 8, ms
+    ints = torch.empty((4, n), dtype=torch.int32, device=scratch.device)
+    peak = torch.empty(n, dtype=torch.float64, device=scratch.device)
+    ctx.regions_fill(*args, n, *(ints[k].data_ptr() for k in range(4)), peak.data_ptr(), ch.stream)
+    if ch.info is not None:
+        ms += ctx.last_kernel_ms()
+    h = ints.cpu().numpy().astype(np.int64)
+    out = dict(first=h[0] + ch.w0, last=h[1] + ch.w0, summit=h[2] + ch.w0, windows=h[3], peak=peak.cpu().numpy())
+    return out, 8 + 64 + 24 * n, ms                                        # the count; fill's header; 4 int32 + 1 double
+
+
+def _scan_regions_folded(folded, what, fasta_or_sequences, width, stride, thresholds, gap, device, chunk, on_chunk):
+    """The body `scan_regions` and `scan_regions_with_panel` share -> [(name, [regions per member])]: the chunk loop of
+    `scan`, then per chunk and member one count and one fill call on the member's column of the device scores."""
+    import torch
+    width, stride, gap = int(width), int(stride), int(gap)
+    records = _scan_records(what, fasta_or_sequences, width)
+    nm = len(thresholds)
+    found = [[[] for _ in range(nm)] for _ in records]
+    for ch in _scan_chunks(folded, records, width, stride, device, chunk, on_chunk is not None, score_ms=True):
+        scratch = torch.empty(ch.ctx.regions_scratch_bytes(ch.nlm, ch.w1 - ch.w0), dtype=torch.uint8,
+                              device=ch.scores.device)
+        got = [_chunk_regions(ch, m, nm, width, stride, thresholds[m], gap, scratch) for m in range(nm)]
+        for m, (r, _, _) in enumerate(got):
+            found[ch.record][m].append(r)
+        if on_chunk is not None:
+            counts = [len(r["first"]) for r, _, _ in got]
+            ch.info.update(regions=counts if folded.cols else counts[0], copied_bytes=sum(b for _, b, _ in got),
+                           region_kernels_ms=sum(ms for _, _, ms in got))
+            ch.info["wall_ms"] = (time.perf_counter() - ch.t0) * 1e3
+            on_chunk(ch.info)
+    return [(name, [_regions_in_bases(stitch_regions(per_chunk, gap), width, stride) for per_chunk in members])
+            for (name, _, _), members in zip(records, found)]
+
+
+def scan_regions(table, fasta_or_sequences, width, stride=1, threshold=0.0, gap=0, device=0, chunk=None, on_chunk=None):
+    """The regions of a scan -> [(name, regions)] per record, in file order.  A window passes when it has a score (it
+    covers only A, C, G, T) and the score `scan` returns for it, rho included, is >= threshold (a NaN never passes;
+    -inf passes every scored window).  Consecutive passing windows belong to one region when at most `gap` windows lie
+    between them.  regions: a dict of arrays, one element per region in ascending order: start (the first passing
+    window's start), end (the last one's start + width), summit (the start of the first passing window that attains the
+    peak) and windows (how many passed), int64, and peak (the largest score among them), float64.  A record shorter than
+    `width` or without a passing window has empty arrays.  Whatever `chunk` and whatever precedes the record, the result
+    is bit for bit this definition applied to `scan`'s output.
+    The reduction runs on the device (k_regions_summaries, k_regions_fill): per chunk only the region count and the
+    regions are copied back, and no per-window array exists on the host.  on_chunk(dict) (measurements): scan's keys,
+    `score_kernel` and `score_kernel_ms`, `regions`, `copied_bytes` (what the chunk brought back from the device) and
+    `region_kernels_ms` (HIP events)."""
+    threshold = check_scan_regions(table, width, stride, threshold, gap, chunk)
+    res = _scan_regions_folded(table, "scan-regions", fasta_or_sequences, width, stride, [threshold], gap, device,
+                               chunk or default_scan_chunk(table.d), on_chunk)
+    return [(name, members[0]) for name, members in res]
+
+
+def write_regions(path, results):
+    """The `scan-regions` output: one line per region, name<TAB>start<TAB>end<TAB>peak<TAB>summit<TAB>windows (0-based
+    start, end exclusive, the peak at %.17g, which reads back to the same double); a record without regions writes
+    nothing.  -> the regions written."""
+    n = 0
+    with open(path, "w") as f:
+        for name, r in results:
+            f.write("".join("%s\t%d\t%d\t%.17g\t%d\t%d\n" % ((name,) + row)
+                            for row in zip(*(r[key].tolist() for key in REGION_FIELDS))))
+            n += len(r["start"])
+    return n
+
+
+def read_regions(path):
+    """-> [(name, start, end, peak, summit, windows)] from a file written by write_regions."""
+    out = []
+    with open(path) as f:
+        for line in f.read().split("\n")[:-1]:
+            name, a, b, v, s, n = line.rsplit("\t", 5)
+            out.append((name, int(a), int(b), float(v), int(s), int(n)))
     return out
 
 
@@ -2050,6 +2242,40 @@ def scan_with_panel(panel, fasta_or_sequences, width, stride=1, device=0, chunk=
                         chunk or default_panel_scan_chunk(panel.d, panel.n_models), on_chunk)
 
 
+def scan_regions_with_panel(panel, fasta_or_sequences, width, stride=1, threshold=0.0, gap=0, device=0, chunk=None,
+                            on_chunk=None):
+    """`scan_regions` for every member of a panel -> [(name, [regions of member 0, of member 1, ...])]: member m's regions
+    are scan_regions' for panel.table(m), bit for bit.  threshold: one for all members or one per member.  Per chunk the
+    profiles and k_panel_scan_score run once; the region calls run once per member on its column of the device result
+    (leading dimension n_models, no copy).  on_chunk(dict): scan_with_panel's keys, `regions` (one count per member),
+    `copied_bytes` and `region_kernels_ms` (both summed over the members)."""
+    thresholds = check_panel_scan_regions(panel, width, stride, threshold, gap, chunk)
+    return _scan_regions_folded(panel, "scan-regions-panel", fasta_or_sequences, width, stride, thresholds, gap, device,
+                                chunk or default_panel_scan_chunk(panel.d, panel.n_models), on_chunk)
+
+
+def write_panel_regions(path, panel_names, results):
+    """The `scan-regions-panel` output: write_regions' line with the member's name in front,
+    member<TAB>name<TAB>start<TAB>end<TAB>peak<TAB>summit<TAB>windows; records in file order, the members of a record in
+    panel order.  -> the regions written."""
+    n = 0
+    with open(path, "w") as f:
+        for name, members in results:
+            for member, r in zip(panel_names, members):
+                f.write("".join("%s\t%s\t%d\t%d\t%.17g\t%d\t%d\n" % ((member, name) + row)
+                                for row in zip(*(r[key].tolist() for key in REGION_FIELDS))))
+                n += len(r["start"])
+    return n
+
+
+def read_panel_regions(path):
+    """-> [(member, name, start, end, peak, summit, windows)] from a file written by write_panel_regions."""
+    out = []
+    for lead, a, b, v, s, n in read_regions(path):
+        out.append(tuple(lead.split("\t", 1)) + (a, b, v, s, n))
+    return out
+
+
 def check_panel_delta(panel, variants=None, records=None, chunk=None):
     """What `delta_with_panel` and `delta_saturation_with_panel` refuse before they touch the device (check_delta's
     refusals)."""
@@ -2154,6 +2380,23 @@ def _add_arguments(p, *positionals, block=True):
         p.add_argument(name)
 
 
+def _add_region_options(p, threshold_help):
+    p.add_argument("--width", type=int, required=True, help="bases per window (L..2047)")
+    p.add_argument("--stride", type=int, default=1, help="bases between window starts (default: 1)")
+    p.add_argument("--threshold", default="0", help=threshold_help)
+    p.add_argument("--gap", type=int, default=0, help="windows below the threshold a region may bridge (default: 0)")
+    p.add_argument("--chunk", type=int, default=None, help="bases per device chunk (default: from device memory)")
+
+
+def region_thresholds(text, panel=False):
+    """--threshold -> a float, or for a panel a list of them when commas separate several."""
+    try:
+        values = [float(x) for x in text.split(",")] if panel else [float(text)]
+    except ValueError:
+        raise ModelError("--threshold: %r is no number%s" % (text, " (or comma-separated numbers)" if panel else ""))
+    return values[0] if len(values) == 1 else values
+
+
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m gkmqc_amd.gkmpredict",
                                 description="train a gkm-SVM on all sequences / score FASTA sequences with it (MI355X)")
@@ -2192,6 +2435,11 @@ def build_parser():
     n.add_argument("--stride", type=int, default=1, help="bases between window starts (default: 1)")
     n.add_argument("--chunk", type=int, default=None, help="bases per device chunk (default: from device memory)")
     _add_arguments(n, "seqs_fa", "weights", "output", block=False)
+    nr = sub.add_parser("scan-regions", help="scan the sequences of seqs.fa with an l-mer weight table and report the "
+                                             "regions whose windows score at least --threshold: name<TAB>start<TAB>end"
+                                             "<TAB>peak<TAB>summit<TAB>windows per region")
+    _add_region_options(nr, "the score a window must reach (default: 0, the decision boundary)")
+    _add_arguments(nr, "weights", "seqs_fa", "output", block=False)
     i = sub.add_parser("importance-table", help="fold a model into its per-base importance table: one value per (l-mer, "
                                                 "offset), a binary .npz file")
     _add_arguments(i, "model", "output", block=False)
@@ -2225,6 +2473,10 @@ def build_parser():
     ps.add_argument("--stride", type=int, default=1, help="bases between window starts (default: 1)")
     ps.add_argument("--chunk", type=int, default=None, help="bases per device chunk (default: from device memory)")
     _add_arguments(ps, "seqs_fa", "panel", "output", block=False)
+    pr = sub.add_parser("scan-regions-panel", help="scan-regions for every member of a panel: the member's name, then "
+                                                   "scan-regions' columns")
+    _add_region_options(pr, "one value for all members or one per member, comma-separated (default: 0)")
+    _add_arguments(pr, "panel", "seqs_fa", "output", block=False)
     pd = sub.add_parser("delta-panel", help="the effect of the variants of variants.tsv on the sequences of seqs.fa for "
                                             "every member of a panel: a header, then the variant's columns and one delta "
                                             "per member")
@@ -2319,6 +2571,24 @@ def main(argv=None):
             os.replace(tmp, a.output)
             print("%d windows scored, %d over a non-ACGT character left out -> %s"
                   % (sum(len(r[1]) for r in results) - omitted, omitted, a.output), file=sys.stderr)
+        elif a.cmd in ("scan-regions", "scan-regions-panel"):
+            if not os.path.isfile(a.seqs_fa):
+                raise ModelError("cannot read %s" % a.seqs_fa)
+            panel = a.cmd == "scan-regions-panel"
+            threshold = region_thresholds(a.threshold, panel)
+            tmp = a.output + ".tmp"
+            if panel:
+                folded = load_lmer_panel(a.panel)
+                check_panel_scan_regions(folded, a.width, a.stride, threshold, a.gap, a.chunk)
+                results = scan_regions_with_panel(folded, a.seqs_fa, a.width, a.stride, threshold, a.gap, a.device, a.chunk)
+                n = write_panel_regions(tmp, folded.names, results)
+            else:
+                folded = load_lmer_table(a.weights)
+                check_scan_regions(folded, a.width, a.stride, threshold, a.gap, a.chunk)
+                results = scan_regions(folded, a.seqs_fa, a.width, a.stride, threshold, a.gap, a.device, a.chunk)
+                n = write_regions(tmp, results)
+            os.replace(tmp, a.output)
+            print("%d regions at a threshold of %s, gap %d -> %s" % (n, a.threshold, a.gap, a.output), file=sys.stderr)
         elif a.cmd in ("delta", "delta-saturation"):
             for path in (a.seqs_fa,) + ((a.variants,) if a.cmd == "delta" else ()):
                 if not os.path.isfile(path):

@@ -297,6 +297,36 @@ int gkmhip_scan_score(gkmhip_ctx *ctx, const uint32_t *lm, int64_t nlm, const ui
 /* windows per stretch of k_scan_profiles: a function of (L, width, stride) only; 0 for arguments the scan refuses */
 int gkmhip_scan_group(const gkmhip_ctx *ctx, int width, int stride);
 
+/* ---- regions of a scan: thresholded runs of windows with their summits (gkm_regions.hip) ----
+ * Over the nwin windows of a scan launch (the same lm, nlm, width, stride) and their finished scores score[i ld] (DEVICE;
+ * ld >= 1, so a column of a panel's nwin x nm result is served where it lies).  Window i PASSES when none of its
+ * width - L + 1 words of lm is flagged (bit 31) and score[i ld] >= threshold by IEEE comparison (a NaN never passes; a
+ * threshold of -inf passes every window without a flagged word; a NaN threshold is refused).  Consecutive passing windows
+ * p < q belong to one region when q - p <= gap + 1 (gap >= 0).  A region is five values in window indices of THIS launch:
+ * first, last (its first and last passing window), windows (how many passed), peak (the largest score among them) and
+ * summit (the first passing window that attains it); regions ascend.  The launch knows nothing of its neighbours.
+ * Nothing is added and no atomic is used: the same arguments give the same bytes on every run.
+ *
+ * gkmhip_regions_count: *count (HOST) = the regions of the launch; complete on return (it waits for `stream`).  scratch:
+ * DEVICE, 8-byte aligned, at least gkmhip_regions_scratch_bytes(nlm, nwin) bytes (-1 for nlm < 1, nlm >= 2^40 or nwin
+ * outside 1..2^30); it keeps what gkmhip_regions_fill needs.
+ * gkmhip_regions_fill: after gkmhip_regions_count with the same arguments and scratch (anything else is refused, error 2,
+ * from a 64-byte header it reads back): regions 0 .. count - 1 into the five DEVICE arrays of `capacity` elements each.
+ * No cell beyond count - 1 is written.  capacity < count: error 2 and nothing is written.  count == 0: nothing is
+ * launched and the arrays may be NULL.
+ * last_kernel_ms / last_kernel_name: k_regions_summaries for the count call (the events bracket all its launches: the
+ * prefix count of flagged words, the wave summaries and their scan) and k_regions_fill for the fill call;
+ * last_comparisons: nwin.  gkmhip_regions_span: the windows one workgroup of either kernel owns. */
+int64_t gkmhip_regions_scratch_bytes(int64_t nlm, int64_t nwin);
+int gkmhip_regions_count(gkmhip_ctx *ctx, const double *score, int64_t ld, const uint32_t *lm, int64_t nlm, int width,
+                         int stride, int64_t nwin, double threshold, int64_t gap, void *scratch, int64_t scratch_bytes,
+                         int64_t *count, void *stream);
+int gkmhip_regions_fill(gkmhip_ctx *ctx, const double *score, int64_t ld, const uint32_t *lm, int64_t nlm, int width,
+                        int stride, int64_t nwin, double threshold, int64_t gap, void *scratch, int64_t scratch_bytes,
+                        int64_t capacity, int32_t *first, int32_t *last, int32_t *summit, int32_t *windows, double *peak,
+                        void *stream);
+int gkmhip_regions_span(void);
+
 /* ---- variant effects from an l-mer weight table: deltaSVM (gkm_delta.hip) ----
  * The change in the summed weights of the l-mers a variant touches.  For a base string z with n = len(z) - L + 1 l-mers
  * u_0 .. u_{n-1}, S(z) = ((0.0 + W[u_0]) + W[u_1]) + ... + W[u_{n-1}] in plain double additions, 0.0 when n < 1.  No
