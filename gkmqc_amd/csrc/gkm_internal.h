@@ -39,6 +39,12 @@
  *                          k_regions_scan_words, k_regions_word_prefix, k_regions_summaries, k_regions_scan,
  *                          k_regions_fill), gkmhip_regions_count, gkmhip_regions_fill, gkmhip_regions_scratch_bytes,
  *                          gkmhip_regions_span
+ *   gkm_wordcnt.h          the prefix count of flagged l-mer words (k_regions_word_sums, k_regions_scan_words,
+ *                          k_regions_word_prefix) that gkm_regions.hip and gkm_dist.hip both launch
+ *   gkm_dist.hip           the distribution of a scan's scores: histograms of the scored windows by a digit of an
+ *                          order-preserving key or by edges, and a bounded collection of the scores under key prefixes
+ *                          (k_dist_digits, k_dist_edges, k_dist_collect), gkmhip_dist_digits, gkmhip_dist_edges,
+ *                          gkmhip_dist_collect, gkmhip_dist_scratch_bytes, gkmhip_dist_digit_bits
  */
 #ifndef GKM_INTERNAL_H
 #define GKM_INTERNAL_H

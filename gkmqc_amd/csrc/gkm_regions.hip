@@ -7,7 +7,7 @@
  * associative, so every tree gives the same bits, and nothing here adds two doubles.
  *
  * Kernels
- *   k_regions_word_sums, k_regions_scan_words, k_regions_word_prefix
+ *   k_regions_word_sums, k_regions_scan_words, k_regions_word_prefix (gkm_wordcnt.h, shared with gkm_dist.hip)
  *                         cnt[p] = flagged words among lm[0 .. p), p = 0 .. nlm: ballots and population counts per 64
  *                         words, the block totals scanned by one wave in a launch of its own.  Window i holds no flagged
  *                         word when cnt[i s + n] == cnt[i s]: two loads, whatever the width.
@@ -33,16 +33,13 @@
  * No workgroup waits for another: what crosses workgroups crosses a launch boundary.  No atomics: a slot is a rank
  * computed from the input order, so order and values are the same bytes on every run.
  */
-#include "gkm_lmer_dev.h"
+#include "gkm_wordcnt.h"
 
 namespace {
 
-constexpr int RG_THREADS = 256;
-constexpr int RG_WAVES = RG_THREADS / 64;
 constexpr int RG_STEPS = 4;                   /* steps of 64 windows per wave */
 constexpr int RG_WAVE = 64 * RG_STEPS;        /* windows per wave: one summary */
 constexpr int RG_SPAN = RG_WAVE * RG_WAVES;   /* windows per workgroup */
-constexpr int RW_PER = 16, RW_TILE = RG_THREADS * RW_PER; /* steps of 64 words per wave / words per workgroup */
 constexpr int64_t RG_MAGIC = 0x31534E4F49474552LL;        /* "REGIONS1" */
 
 /* what k_regions_scan leaves at the head of the scratch: the count, and the launch it belongs to */
@@ -168,8 +165,6 @@ struct Walk {
     Agg open;                  /* of the passing windows of the region still open */
 };
 
-__device__ __forceinline__ unsigned long long lanes_below(int lane) { return (1ull << lane) - 1ull; }
-
 /* The 64 windows from i0 on.  FILL: begins and closed regions go to `out`; otherwise the first region that closes is kept in
  * *head (the walk started without a carry: it is the range's head). */
 template <bool FILL>
@@ -223,75 +218,6 @@ __device__ __forceinline__ void regions_step(const RegArgs &a, int64_t i0, int l
     if (w.first < 0) w.first = (int32_t)i0 + __builtin_ctzll(pm);
     w.last = (int32_t)i0 + 63 - __builtin_clzll(pm);
     w.nreg += __popcll(sm);
-}
-
-__device__ __forceinline__ bool word_flag(const uint32_t *__restrict__ lm, int64_t nlm, int64_t p)
-{
-    return p < nlm && (lm[p] & LMER_BAD);
-}
-
-__global__ __launch_bounds__(RG_THREADS) void k_regions_word_sums(const uint32_t *__restrict__ lm, int64_t nlm,
-                                                                  uint32_t *__restrict__ sums)
-{
-    __shared__ uint32_t wtot[RG_WAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t p0 = (int64_t)blockIdx.x * RW_TILE + (int64_t)wave * (64 * RW_PER) + lane;
-    uint32_t tot = 0u;
-#pragma unroll
-    for (int r = 0; r < RW_PER; r++) tot += (uint32_t)__popcll(__ballot(word_flag(lm, nlm, p0 + r * 64)));
-    if (lane == 0) wtot[wave] = tot;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t all = 0u;
-        for (int w = 0; w < RG_WAVES; w++) all += wtot[w];
-        sums[blockIdx.x] = all;
-    }
-}
-
-/* one wave: sums -> their exclusive prefix, in place */
-__global__ __launch_bounds__(64) void k_regions_scan_words(uint32_t *__restrict__ sums, int nsums)
-{
-    const int lane = threadIdx.x;
-    uint32_t carry = 0u;
-    for (int base = 0; base < nsums; base += 64) {
-        const int e = base + lane;
-        const uint32_t v = e < nsums ? sums[e] : 0u;
-        uint32_t inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t u = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += u;
-        }
-        if (e < nsums) sums[e] = carry + inc - v;
-        carry += __shfl(inc, 63, 64);
-    }
-}
-
-/* cnt[p], p = 0 .. nlm */
-__global__ __launch_bounds__(RG_THREADS) void k_regions_word_prefix(const uint32_t *__restrict__ lm, int64_t nlm,
-                                                                    const uint32_t *__restrict__ sums,
-                                                                    uint32_t *__restrict__ cnt)
-{
-    __shared__ uint32_t wtot[RG_WAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t p0 = (int64_t)blockIdx.x * RW_TILE + (int64_t)wave * (64 * RW_PER) + lane;
-    unsigned long long m[RW_PER];
-    uint32_t tot = 0u;
-#pragma unroll
-    for (int r = 0; r < RW_PER; r++) {
-        m[r] = __ballot(word_flag(lm, nlm, p0 + r * 64));
-        tot += (uint32_t)__popcll(m[r]);
-    }
-    if (lane == 0) wtot[wave] = tot;
-    __syncthreads();
-    uint32_t run = sums[blockIdx.x];
-    for (int w = 0; w < wave; w++) run += wtot[w];
-#pragma unroll
-    for (int r = 0; r < RW_PER; r++) {
-        const int64_t p = p0 + r * 64;
-        if (p <= nlm) cnt[p] = run + (uint32_t)__popcll(m[r] & lanes_below(lane));
-        run += (uint32_t)__popcll(m[r]);
-    }
 }
 
 __global__ __launch_bounds__(RG_THREADS) void k_regions_summaries(RegArgs a, int64_t nent, RegEntries e)
@@ -373,8 +299,6 @@ __global__ __launch_bounds__(RG_THREADS) void k_regions_fill(RegArgs a, int64_t 
     }
 }
 
-inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 /* the pieces of the scratch, in bytes from its start */
 struct RegPlan {
     int64_t nent, wblocks;
@@ -386,7 +310,7 @@ RegPlan regions_plan(int64_t nlm, int64_t nwin)
 {
     RegPlan p;
     p.nent = (nwin + RG_WAVE - 1) / RG_WAVE;
-    p.wblocks = (nlm + 1 + RW_TILE - 1) / RW_TILE;
+    p.wblocks = wordcnt_blocks(nlm);
     p.cnt = 256;
     p.sums = p.cnt + pad256((size_t)(nlm + 1) * 4);
     p.ent = p.sums + pad256((size_t)p.wblocks * 4);
@@ -462,9 +386,7 @@ extern "C" int gkmhip_regions_count(gkmhip_ctx *ctx, const double *score, int64_
     hipStream_t stream = (hipStream_t)stream_;
     if (int rc = gkm_launch_enter(ctx)) return rc;
     if (int rc = gkm_launch_begin(ctx, stream)) return rc;
-    hipLaunchKernelGGL(k_regions_word_sums, dim3((unsigned)p.wblocks), dim3(RG_THREADS), 0, stream, lm, nlm, sums);
-    hipLaunchKernelGGL(k_regions_scan_words, dim3(1), dim3(64), 0, stream, sums, (int)p.wblocks);
-    hipLaunchKernelGGL(k_regions_word_prefix, dim3((unsigned)p.wblocks), dim3(RG_THREADS), 0, stream, lm, nlm, sums, cnt);
+    wordcnt_launch(lm, nlm, sums, cnt, stream);
     hipLaunchKernelGGL(k_regions_summaries, dim3(blocks), dim3(RG_THREADS), 0, stream, a, p.nent, e);
     hipLaunchKernelGGL(k_regions_scan, dim3(1), dim3(64), 0, stream, e, p.nent, gap,
                        regions_header(ld, nlm, width, stride, nwin, threshold, gap), (RegHeader *)s);

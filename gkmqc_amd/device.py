@@ -153,6 +153,17 @@ def load():
         L.gkmhip_regions_fill.argtypes = (vp, vp, i64, vp, i64, i32, i32, i64, dbl, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp)
         L.gkmhip_regions_span.restype = i32
         L.gkmhip_regions_span.argtypes = ()
+    if hasattr(L, "gkmhip_dist_digits"):     # (likewise: GramContext's dist methods say so on an older build)
+        L.gkmhip_dist_digit_bits.restype = i32
+        L.gkmhip_dist_digit_bits.argtypes = ()
+        L.gkmhip_dist_scratch_bytes.restype = i64
+        L.gkmhip_dist_scratch_bytes.argtypes = (i64, i64)
+        L.gkmhip_dist_digits.restype = i32
+        L.gkmhip_dist_digits.argtypes = (vp, vp, i64, vp, i64, i32, i32, i64, vp, i32, i32, vp, vp, i64, vp)
+        L.gkmhip_dist_edges.restype = i32
+        L.gkmhip_dist_edges.argtypes = (vp, vp, i64, vp, i64, i32, i32, i64, vp, i32, vp, vp, i64, vp)
+        L.gkmhip_dist_collect.restype = i32
+        L.gkmhip_dist_collect.argtypes = (vp, vp, i64, vp, i64, i32, i32, i64, vp, i32, i32, vp, i64, vp, vp, i64, vp)
     L.gkmhip_delta_sat.restype = i32
     L.gkmhip_delta_sat.argtypes = (vp, vp, i64, i64, i64, vp, vp, vp)
     L.gkmhip_delta_variants.restype = i32
@@ -615,6 +626,59 @@ class GramContext:
                                                int(nwin), float(threshold), int(gap), scratch_ptr, int(scratch_bytes),
                                                int(capacity), first_ptr, last_ptr, summit_ptr, windows_ptr, peak_ptr,
                                                stream), "gkmhip_regions_fill")
+
+    def _need_dist(self):
+        if not hasattr(self.lib, "gkmhip_dist_digits"):
+            raise GkmError("%s holds no gkmhip_dist_digits: it was built before the distribution calls" % lib_path())
+
+    def dist_digit_bits(self):
+        """B, the key bits one refinement level resolves (include/gkm_hip.h gkmhip_dist_digit_bits)."""
+        self._need_dist()
+        return self.lib.gkmhip_dist_digit_bits()
+
+    def dist_scratch_bytes(self, nlm, nwin):
+        """Device bytes each dist call needs for nwin windows over nlm l-mer words; -1 where refused."""
+        self._need_dist()
+        return self.lib.gkmhip_dist_scratch_bytes(int(nlm), int(nwin))
+
+    @staticmethod
+    def _prefix_array(prefix):
+        """the HOST prefixes of a dist call -> (the contiguous uint64 array, held until the C call returns, its pointer)"""
+        prefix = np.ascontiguousarray(prefix, dtype=np.uint64).reshape(-1)
+        return prefix, (prefix.ctypes.data if len(prefix) else None)
+
+    def dist_digits(self, score_ptr, ld, lm_ptr, nlm, width, stride, nwin, prefix, prefix_bits, hist_ptr, scratch_ptr,
+                    scratch_bytes, stream=0):
+        """Adds the scored windows of a scan launch (finished scores score_ptr[i * ld], device doubles) to the device
+        uint64 histogram at hist_ptr by the next digit of their keys: prefix, a HOST sequence of up to 64 strictly
+        ascending values of prefix_bits bits, selects the windows and the histogram's row; an empty one is level 0
+        (include/gkm_hip.h gkmhip_dist_digits).  Does not wait."""
+        self._need_dist()
+        prefix, pptr = self._prefix_array(prefix)
+        self._chk(self.lib.gkmhip_dist_digits(self.handle, score_ptr, int(ld), lm_ptr, int(nlm), int(width), int(stride),
+                                              int(nwin), pptr, len(prefix), int(prefix_bits), hist_ptr, scratch_ptr,
+                                              int(scratch_bytes), stream), "gkmhip_dist_digits")
+
+    def dist_edges(self, score_ptr, ld, lm_ptr, nlm, width, stride, nwin, edges_ptr, nedges, hist_ptr, scratch_ptr,
+                   scratch_bytes, stream=0):
+        """Adds the scored windows to the nedges + 1 device uint64 counters at hist_ptr, a score v at the number of
+        edges <= v: edges_ptr = nedges ascending device doubles (gkmhip_dist_edges).  Does not wait."""
+        self._need_dist()
+        self._chk(self.lib.gkmhip_dist_edges(self.handle, score_ptr, int(ld), lm_ptr, int(nlm), int(width), int(stride),
+                                             int(nwin), edges_ptr, int(nedges), hist_ptr, scratch_ptr, int(scratch_bytes),
+                                             stream), "gkmhip_dist_edges")
+
+    def dist_collect(self, score_ptr, ld, lm_ptr, nlm, width, stride, nwin, prefix, prefix_bits, out_ptr, capacity,
+                     counter_ptr, scratch_ptr, scratch_bytes, stream=0):
+        """Appends the scores of the scored windows whose keys begin with one of the HOST prefixes to the device doubles
+        at out_ptr, from the device int64 at counter_ptr on, which advances by the matches; positions >= capacity are
+        dropped (gkmhip_dist_collect).  Does not wait."""
+        self._need_dist()
+        prefix, pptr = self._prefix_array(prefix)
+        self._chk(self.lib.gkmhip_dist_collect(self.handle, score_ptr, int(ld), lm_ptr, int(nlm), int(width), int(stride),
+                                               int(nwin), pptr, len(prefix), int(prefix_bits), out_ptr, int(capacity),
+                                               counter_ptr, scratch_ptr, int(scratch_bytes), stream),
+                  "gkmhip_dist_collect")
 
     def delta_sat(self, lm_ptr, nlm, t_begin, t_end, W_ptr, out_ptr, stream=0):
         """Every SNV of the positions [t_begin, t_end) of the bases the nlm words at lm_ptr cover -> out_ptr, (t_end -

@@ -59,6 +59,7 @@ The other half of a gkm-SVM next to the cross-validation of `gkmsvm.py` (the cou
 """
 import argparse
 import logging
+import math
 import os
 import sys
 import time
@@ -1694,6 +1695,369 @@ def read_regions(path):
     return out
 
 
+# ------------------------------------------------------------------ score distributions of a scan
+DIST_MAX_THRESHOLDS = 4096  # edges one gkmhip_dist_edges launch takes
+DIST_MAX_RANKS = 64         # prefixes one gkmhip_dist_digits launch carries: one target per requested rank at most
+DIST_DIGIT_BITS = 13        # gkmhip_dist_digit_bits of this build (the device's own value is what a scan uses)
+_KEY_SIGN, _KEY_ALL = np.uint64(1 << 63), np.uint64(0xFFFFFFFFFFFFFFFF)
+
+
+def score_keys(values):
+    """float64 -> uint64 keys: b ^ (b >> 63 ? ~0 : 1 << 63) of the bits b.  Ascending keys are ascending non-NaN
+    doubles, -0.0 just below +0.0; the map is a bijection of the 64-bit words."""
+    b = np.ascontiguousarray(values, dtype=np.float64).view(np.uint64)
+    return b ^ np.where(b >> np.uint64(63), _KEY_ALL, _KEY_SIGN)
+
+
+def keys_to_scores(keys):
+    """The inverse of score_keys: the same bits back."""
+    k = np.ascontiguousarray(keys, dtype=np.uint64)
+    return (k ^ np.where(k >> np.uint64(63), _KEY_SIGN, _KEY_ALL)).view(np.float64)
+
+
+def dist_level_bits(digit_bits=DIST_DIGIT_BITS):
+    """The key bits each refinement level resolves for B = digit_bits: ceil(64 / B) levels, the first of
+    64 - B (levels - 1) bits, every later one of B."""
+    B = int(digit_bits)
+    if not 1 <= B <= 64:
+        raise ModelError("a level resolves 1..64 bits, not %d" % B)
+    levels = -(-64 // B)
+    return [64 - B * (levels - 1)] + [B] * (levels - 1)
+
+
+def dist_boundaries(digit_bits=DIST_DIGIT_BITS):
+    """The bits resolved after each level; the last is 64."""
+    return np.cumsum(dist_level_bits(digit_bits)).tolist()
+
+
+def quantile_ranks(n, q):
+    """The order statistic a quantile q in [0, 1] of n values names: min(n - 1, floor(q (n - 1))) in Python floats."""
+    return [min(int(n) - 1, int(math.floor(float(x) * (int(n) - 1)))) for x in q]
+
+
+class _RankSearch:
+    """Radix selection of order statistics from histograms of a multiset of keys that is never held: a state machine.
+    `request` is what it needs next -- ("hist", prefixes, prefix_bits) or ("collect", prefixes, prefix_bits, total), or
+    None when `values` holds the answer -- and feed(result) hands it over: for "hist" the counts (len(prefixes) or 1,
+    2^bits of the level) of the keys that begin with each prefix by their next digit, for "collect" the `total` values
+    whose keys begin with one of the prefixes, in any order.  want(n) -> the ranks, once the first histogram has given
+    n.  All targets (the distinct prefixes the ranks fall under, each with the count of keys below it) descend one level
+    per pass in lockstep; they are collected as soon as they hold at most collect_cap keys together, and decoded when
+    all 64 bits are resolved, which ends the search whatever the values are."""
+
+    def __init__(self, want, collect_cap, digit_bits):
+        self.want, self.cap, self.bits = want, int(collect_cap), dist_level_bits(digit_bits)
+        self.level, self.prefix_bits = 0, 0
+        self.prefixes = np.empty(0, dtype=np.uint64)
+        self.request = ("hist", self.prefixes, 0)
+        self.n = self.ranks = self.values = None
+
+    def feed(self, result):
+        if self.request[0] == "collect":
+            self.values, self.request = self._read_off(result), None
+            return
+        bits = self.bits[self.level]
+        counts = np.asarray(result, dtype=np.int64).reshape(max(len(self.prefixes), 1), 1 << bits)
+        if self.level == 0:
+            self.n = int(counts.sum())
+            self.ranks = np.asarray(self.want(self.n), dtype=np.int64).reshape(-1)
+            self.target = np.zeros(len(self.ranks), dtype=np.int64)       # the row of each rank's target
+            self.below = np.zeros(1, dtype=np.int64)                      # per target: the keys below it
+            self.prefixes = np.zeros(1, dtype=np.uint64)
+        cum = np.cumsum(counts, axis=1)
+        local = self.ranks - self.below[self.target]
+        digit = np.array([np.searchsorted(cum[t], r, side="right") for t, r in zip(self.target, local)], dtype=np.int64)
+        if (digit >> bits).any():
+            raise ModelError("the histogram of a refinement pass does not hold the windows of the pass before it")
+        count = counts[self.target, digit]
+        below = self.below[self.target] + cum[self.target, digit] - count
+        prefix = (self.prefixes[self.target] << np.uint64(bits)) | digit.astype(np.uint64)
+        self.level, self.prefix_bits = self.level + 1, self.prefix_bits + bits
+        self.prefixes, first, self.target = np.unique(prefix, return_index=True, return_inverse=True)
+        self.target = self.target.reshape(-1)
+        self.below, self.count = below[first], count[first]
+        if self.prefix_bits == 64:                                         # the prefix is the key
+            self.values, self.request = keys_to_scores(self.prefixes)[self.target], None
+        elif int(self.count.sum()) <= self.cap:
+            self.request = ("collect", self.prefixes, self.prefix_bits, int(self.count.sum()))
+        else:
+            self.request = ("hist", self.prefixes, self.prefix_bits)
+
+    def _read_off(self, values):
+        keys = np.sort(score_keys(np.asarray(values, dtype=np.float64).reshape(-1)))
+        run = np.repeat(self.prefixes, self.count)
+        if len(keys) != len(run) or not np.array_equal(keys >> np.uint64(64 - self.prefix_bits), run):
+            raise ModelError("the collected values are not the ones the histograms counted")
+        start = np.cumsum(self.count) - self.count
+        return keys_to_scores(keys[start[self.target] + self.ranks - self.below[self.target]])
+
+
+def select_order_statistics(hist_pass, collect_pass, want, collect_cap=1 << 20, digit_bits=DIST_DIGIT_BITS, on_pass=None):
+    """Order statistics of a multiset of doubles that only two callables can see -> (n, ranks, values, passes).
+    hist_pass(prefixes, prefix_bits) -> counts and collect_pass(prefixes, prefix_bits, total) -> values as _RankSearch
+    describes them (prefix_bits 0 and no prefix: the first level over everything); want(n) -> the ranks in 0..n-1.
+    values[i] is the ranks[i]-th smallest by key, the very bits.  passes: one dict per call made, in order -- kind
+    ("hist" or "collect"), prefix_bits and targets -- at most levels + 1 of them; on_pass(dict) sees each after its
+    call."""
+    search, passes = _RankSearch(want, collect_cap, digit_bits), []
+    while search.request is not None:
+        kind, prefixes, prefix_bits = search.request[:3]
+        passes.append(dict(kind=kind, prefix_bits=prefix_bits, targets=len(prefixes)))
+        search.feed(hist_pass(prefixes, prefix_bits) if kind == "hist" else collect_pass(*search.request[1:]))
+        if on_pass is not None:
+            on_pass(passes[-1])
+    return search.n, search.ranks, search.values, passes
+
+
+def _check_quantiles(what, q, ranks, collect_cap):
+    """The refusals `scan_quantiles` adds to `scan`'s -> (q as floats or None, want): want(n) -> the ranks of a call with
+    n scored windows, or the refusals that need n."""
+    if (q is None) == (ranks is None):
+        raise ModelError("%s: give either q or ranks" % what)
+    if isinstance(collect_cap, bool) or not isinstance(collect_cap, (int, np.integer)) or collect_cap < 1:
+        raise ModelError("%s: collect_cap must be an integer of at least 1" % what)
+    given = np.atleast_1d(np.asarray(q if ranks is None else ranks)).reshape(-1).tolist()
+    if not 1 <= len(given) <= DIST_MAX_RANKS:
+        raise ModelError("%s: 1..%d %s per call, not %d" % (what, DIST_MAX_RANKS, "quantiles" if ranks is None else "ranks",
+                                                           len(given)))
+    if ranks is None:
+        try:
+            qs = [float(x) for x in given]
+        except (TypeError, ValueError):
+            raise ModelError("%s: a quantile must be a number" % what)
+        if any(not 0.0 <= x <= 1.0 for x in qs):                           # (a NaN fails both comparisons)
+            raise ModelError("%s: a quantile must lie in 0..1 (and be no NaN)" % what)
+    else:
+        qs = None
+        if any(isinstance(r, bool) or not isinstance(r, (int, np.integer)) for r in given):
+            raise ModelError("%s: a rank must be an integer" % what)
+        if any(r < 0 for r in given):
+            raise ModelError("%s: a rank must lie in 0..n-1" % what)
+
+    def want(n):
+        if n == 0:
+            raise ModelError("%s: no window has a score" % what)
+        if qs is not None:
+            return quantile_ranks(n, qs)
+        if any(r >= n for r in given):
+            raise ModelError("%s: a rank must lie in 0..n-1; %d windows have a score" % (what, n))
+        return given
+    return qs, want
+
+
+def _check_thresholds(what, thresholds):
+    """The refusals `scan_tail_counts` adds to `scan`'s -> the thresholds as a float64 array, in the caller's order."""
+    try:
+        values = np.atleast_1d(np.asarray(thresholds, dtype=np.float64)).reshape(-1)
+    except (TypeError, ValueError):
+        raise ModelError("%s: a threshold must be a number" % what)
+    if not 1 <= len(values) <= DIST_MAX_THRESHOLDS:
+        raise ModelError("%s: 1..%d thresholds per call, not %d" % (what, DIST_MAX_THRESHOLDS, len(values)))
+    if np.isnan(values).any():
+        raise ModelError("%s: a threshold is NaN" % what)
+    return values
+
+
+def check_scan_tail_counts(table, width, stride, thresholds=(), chunk=None):
+    """What `scan_tail_counts` refuses before it reads anything or touches the device: check_scan's refusals, no
+    threshold, more than 4096 of them, a NaN among them.  -> the thresholds, float64."""
+    _check_scan(LmerTable, "scan-tail", table, width, stride, chunk)
+    return _check_thresholds("scan-tail", thresholds)
+
+
+def check_scan_quantiles(table, width, stride, q=None, ranks=None, chunk=None, collect_cap=1 << 20):
+    """What `scan_quantiles` refuses before it reads anything or touches the device: check_scan's refusals, both or
+    neither of q and ranks, none or more than 64 of them, a q that is NaN or outside 0..1, a rank that is negative or no
+    integer, a collect_cap below 1.  (A rank of n or more is refused once the first pass has counted n.)
+    -> (q as floats, or None where ranks were given; want: n -> the ranks of a call with n scored windows)."""
+    _check_scan(LmerTable, "scan-quantiles", table, width, stride, chunk)
+    return _check_quantiles("scan-quantiles", q, ranks, collect_cap)
+
+
+def _dist_windows(records, width, stride):
+    return sum(scan_window_count(len(codes), width, stride) for _, codes, _ in records)
+
+
+def _chunk_dist_args(ch, col, ld, width, stride):
+    return (ch.scores.data_ptr() + 8 * col, ld, ch.lm.data_ptr(), ch.nlm, width, stride, ch.w1 - ch.w0)
+
+
+def _scan_tail_folded(folded, what, fasta_or_sequences, width, stride, thresholds, device, chunk, on_chunk):
+    """The body `scan_tail_counts` and `scan_tail_counts_with_panel` share -> (windows, scored (members,), counts
+    (members, thresholds)): one scan, per chunk and member one k_dist_edges launch on the member's column; the
+    histograms come back once, after the last chunk."""
+    import torch
+    width, stride = int(width), int(stride)
+    records = _scan_records(what, fasta_or_sequences, width)
+    nm, order = folded.cols[0] if folded.cols else 1, np.argsort(thresholds, kind="stable")
+    dev = torch.device("cuda", device)
+    edges = torch.from_numpy(thresholds[order]).to(dev)
+    hist = torch.zeros((nm, len(thresholds) + 1), dtype=torch.int64, device=dev)
+    for ch in _scan_chunks(folded, records, width, stride, device, chunk, on_chunk is not None, score_ms=True):
+        nbytes = ch.ctx.dist_scratch_bytes(ch.nlm, ch.w1 - ch.w0)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ms = 0.0
+        for m in range(nm):
+            ch.ctx.dist_edges(*_chunk_dist_args(ch, m, nm, width, stride), edges.data_ptr(), len(thresholds),
+                              hist[m].data_ptr(), scratch.data_ptr(), nbytes, ch.stream)
+            if on_chunk is not None:
+                ms += ch.ctx.last_kernel_ms()
+        if on_chunk is not None:
+            ch.info.update(dist_kernels_ms=ms, copied_bytes=0)
+            ch.info["wall_ms"] = (time.perf_counter() - ch.t0) * 1e3
+            on_chunk(ch.info)
+    suffix = np.cumsum(hist.cpu().numpy()[:, ::-1], axis=1)[:, ::-1]       # [m, b]: scores with at least b edges <= them
+    counts = np.empty((nm, len(thresholds)), dtype=np.int64)
+    counts[:, order] = suffix[:, 1:]
+    return _dist_windows(records, width, stride), suffix[:, 0].copy(), counts
+
+
+def scan_tail_counts(table, fasta_or_sequences, width, stride=1, thresholds=(), device=0, chunk=None, on_chunk=None):
+    """How many scored windows of a scan reach each threshold, all records pooled -> dict(scored, unscored, thresholds,
+    counts).  A window is scored when it covers only A, C, G, T and `scan`'s score for it is no NaN; counts[i] (int64, the
+    caller's order) is the number of scored windows with score >= thresholds[i], `scan_regions`' own pass rule: the sum
+    of `windows` over scan_regions(threshold=thresholds[i], gap=0).  -inf counts every scored window, +inf only +inf
+    scores.  One scan: the host sorts the thresholds, k_dist_edges bins every chunk's scores by them on the device, and
+    only the histogram of len(thresholds) + 1 counters comes back, once.  on_chunk(dict) (measurements): scan's keys,
+    `score_kernel`, `score_kernel_ms`, `dist_kernels_ms` (HIP events) and `copied_bytes` (0: nothing per chunk)."""
+    thresholds = check_scan_tail_counts(table, width, stride, thresholds, chunk)
+    windows, scored, counts = _scan_tail_folded(table, "scan-tail", fasta_or_sequences, width, stride, thresholds, device,
+                                                chunk or default_scan_chunk(table.d), on_chunk)
+    return dict(scored=int(scored[0]), unscored=windows - int(scored[0]), thresholds=thresholds, counts=counts[0])
+
+
+def _scan_quantiles_folded(folded, what, fasta_or_sequences, width, stride, wants, collect_cap, device, chunk, on_pass):
+    """The body `scan_quantiles` and `scan_quantiles_with_panel` share -> (windows, [the finished _RankSearch of each
+    member], passes).  Every pass is one chunk loop of `scan` that serves all members still searching, each with its
+    own request: per chunk and member one k_dist_digits or k_dist_collect launch on the member's column."""
+    import torch
+    width, stride = int(width), int(stride)
+    records = _scan_records(what, fasta_or_sequences, width)
+    nm = len(wants)
+    dev = torch.device("cuda", device)
+    ctx = dv.cached_context(*folded.kernel_params(), device=device)
+    searches = [_RankSearch(want, collect_cap, ctx.dist_digit_bits()) for want in wants]
+    passes = []
+    while any(s.request is not None for s in searches):
+        active = [(m, s) for m, s in enumerate(searches) if s.request is not None]
+        bufs = {}
+        for m, s in active:
+            if s.request[0] == "hist":
+                bufs[m] = (torch.zeros(max(len(s.prefixes), 1) << s.bits[s.level], dtype=torch.int64, device=dev),)
+            else:
+                bufs[m] = (torch.empty(s.request[3], dtype=torch.float64, device=dev),
+                           torch.zeros(1, dtype=torch.int64, device=dev))
+        ms = scan_ms = 0.0
+        for ch in _scan_chunks(folded, records, width, stride, device, chunk, on_pass is not None, score_ms=True):
+            nbytes = ctx.dist_scratch_bytes(ch.nlm, ch.w1 - ch.w0)
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            if on_pass is not None:
+                scan_ms += ch.info["profile_kernel_ms"] + ch.info["score_kernel_ms"]
+            for m, s in active:
+                args = _chunk_dist_args(ch, m, nm, width, stride) + (s.request[1], s.request[2])
+                if s.request[0] == "hist":
+                    ctx.dist_digits(*args, bufs[m][0].data_ptr(), scratch.data_ptr(), nbytes, ch.stream)
+                else:
+                    ctx.dist_collect(*args, bufs[m][0].data_ptr(), s.request[3], bufs[m][1].data_ptr(), scratch.data_ptr(),
+                                     nbytes, ch.stream)
+                if on_pass is not None:
+                    ms += ctx.last_kernel_ms()
+        info = dict(kind=[s.request[0] for _, s in active], prefix_bits=[s.request[2] for _, s in active],
+                    targets=[len(s.request[1]) for _, s in active], copied_bytes=0)
+        if on_pass is not None:
+            info.update(dist_kernels_ms=ms, scan_kernels_ms=scan_ms)
+        for m, s in active:
+            if s.request[0] == "collect":
+                found = int(bufs[m][1].item())
+                if found != s.request[3]:
+                    raise dv.GkmError("%s: k_dist_collect found %d values where the histograms counted %d"
+                                      % (what, found, s.request[3]))
+                info["copied_bytes"] += 8
+            info["copied_bytes"] += 8 * bufs[m][0].numel()
+            s.feed(bufs[m][0].cpu().numpy())
+        if not folded.cols:
+            info.update(kind=info["kind"][0], prefix_bits=info["prefix_bits"][0], targets=info["targets"][0])
+        passes.append(info)
+        if on_pass is not None:
+            on_pass(info)
+    return _dist_windows(records, width, stride), searches, passes
+
+
+def scan_quantiles(table, fasta_or_sequences, width, stride=1, q=None, ranks=None, device=0, chunk=None,
+                   collect_cap=1 << 20, on_pass=None):
+    """Exact order statistics of a scan's scores, all records pooled -> dict(scored, unscored, q, ranks, values, passes).
+    Give either q (quantiles in 0..1) or ranks (0..n-1), at most 64, in any order, duplicates allowed.  With n the scored
+    windows of the call (see scan_tail_counts), order statistic r is the r-th smallest score by key (score_keys:
+    numerical order, -0.0 below +0.0) and a quantile q is order statistic min(n - 1, floor(q (n - 1))) -- not
+    np.quantile, which interpolates.  values[i] is bit for bit that element of `scan`'s own output, whatever `chunk`,
+    `collect_cap` and the order of the requests.  It is an error if no window has a score.
+    The scores are never kept: radix selection over the keys re-scans instead.  Pass 0 counts every scored window by its
+    key's first digit (k_dist_digits), which gives n and places each rank in a bin; the distinct bins are the targets,
+    refined in lockstep one level per pass until they hold at most collect_cap windows together -- then one more pass
+    gathers exactly those scores (k_dist_collect) and the host sorts them -- or until all 64 bits are resolved and the
+    prefix is the value.  At most levels + 1 passes, each a full scan; only histograms and the collected values leave the
+    device.  passes / on_pass(dict): per pass its kind ("hist" or "collect"), prefix_bits, targets, and what it brought
+    back (copied_bytes); with on_pass also dist_kernels_ms and scan_kernels_ms (k_scan_profiles + k_scan_score), HIP
+    events summed over the pass's chunks."""
+    qs, want = check_scan_quantiles(table, width, stride, q, ranks, chunk, collect_cap)
+    windows, (s,), passes = _scan_quantiles_folded(table, "scan-quantiles", fasta_or_sequences, width, stride, [want],
+                                                   int(collect_cap), device, chunk or default_scan_chunk(table.d), on_pass)
+    return dict(scored=s.n, unscored=windows - s.n, q=qs, ranks=s.ranks, values=s.values, passes=passes)
+
+
+def write_tail_counts(path, result):
+    """The `scan-tail` output: #scored<TAB>n<TAB>unscored<TAB>m, then threshold<TAB>count per threshold in the caller's
+    order, the threshold at %.17g, which reads back to the same double."""
+    with open(path, "w") as f:
+        f.write("#scored\t%d\tunscored\t%d\n" % (result["scored"], result["unscored"]))
+        f.write("".join("%.17g\t%d\n" % row for row in zip(result["thresholds"].tolist(), result["counts"].tolist())))
+
+
+def _read_dist(path, nlead, convert):
+    """-> ([the fields of the #scored lines], [the converted fields of the other lines]); nlead: names in front"""
+    heads, rows = [], []
+    with open(path) as f:
+        for line in f.read().split("\n")[:-1]:
+            fields = line.split("\t")
+            if fields[nlead] == "#scored":
+                heads.append(tuple(fields[:nlead]) + (int(fields[nlead + 1]), int(fields[nlead + 3])))
+            else:
+                rows.append(tuple(fields[:nlead]) + tuple(c(x) for c, x in zip(convert, fields[nlead:])))
+    return heads, rows
+
+
+def read_tail_counts(path):
+    """-> dict(scored, unscored, thresholds, counts) from a file written by write_tail_counts."""
+    (head,), rows = _read_dist(path, 0, (float, int))
+    return dict(scored=head[0], unscored=head[1], thresholds=np.array([r[0] for r in rows], dtype=np.float64),
+                counts=np.array([r[1] for r in rows], dtype=np.int64))
+
+
+def _q_text(q, i):
+    return "-" if q is None else "%.17g" % q[i]
+
+
+def _q_value(text):
+    return None if text == "-" else float(text)
+
+
+def write_quantiles(path, result):
+    """The `scan-quantiles` output: #scored<TAB>n<TAB>unscored<TAB>m, then q<TAB>rank<TAB>value per request in the
+    caller's order, q ("-" when ranks were asked for) and the value at %.17g."""
+    with open(path, "w") as f:
+        f.write("#scored\t%d\tunscored\t%d\n" % (result["scored"], result["unscored"]))
+        for i, (r, v) in enumerate(zip(result["ranks"].tolist(), result["values"].tolist())):
+            f.write("%s\t%d\t%.17g\n" % (_q_text(result["q"], i), r, v))
+
+
+def read_quantiles(path):
+    """-> dict(scored, unscored, q, ranks, values) from a file written by write_quantiles (q: None where "-")."""
+    (head,), rows = _read_dist(path, 0, (_q_value, int, float))
+    q = [r[0] for r in rows]
+    return dict(scored=head[0], unscored=head[1], q=None if None in q else q,
+                ranks=np.array([r[1] for r in rows], dtype=np.int64), values=np.array([r[2] for r in rows], dtype=np.float64))
+
+
 # ------------------------------------------------------------------ variant effects (deltaSVM)
 DELTA_MAX_ALLELE = 255    # bases of an allele after trimming (GKMHIP_DELTA_MAX_ALLELE)
 _ALLELE_CODES = {ord(ch): i & 3 for i, ch in enumerate("ACGTacgt")}
@@ -2276,6 +2640,75 @@ def read_panel_regions(path):
     return out
 
 
+def check_panel_scan_tail_counts(panel, width, stride, thresholds=(), chunk=None):
+    """check_scan_tail_counts for `scan_tail_counts_with_panel` -> the thresholds, float64."""
+    _check_scan(LmerPanel, "scan-tail-panel", panel, width, stride, chunk)
+    return _check_thresholds("scan-tail-panel", thresholds)
+
+
+def check_panel_scan_quantiles(panel, width, stride, q=None, ranks=None, chunk=None, collect_cap=1 << 20):
+    """check_scan_quantiles for `scan_quantiles_with_panel`."""
+    _check_scan(LmerPanel, "scan-quantiles-panel", panel, width, stride, chunk)
+    return _check_quantiles("scan-quantiles-panel", q, ranks, collect_cap)
+
+
+def scan_tail_counts_with_panel(panel, fasta_or_sequences, width, stride=1, thresholds=(), device=0, chunk=None,
+                                on_chunk=None):
+    """`scan_tail_counts` for every member of a panel, the same thresholds for all -> dict(scored, unscored (int64, one
+    per member), thresholds, counts (n_models, thresholds)): row m is scan_tail_counts' result for panel.table(m), bit
+    for bit.  One scan serves all members: k_panel_scan_score once per chunk, then one k_dist_edges launch per member on
+    its column of the device result.  on_chunk(dict): scan_with_panel's keys, `dist_kernels_ms` and `copied_bytes`."""
+    thresholds = check_panel_scan_tail_counts(panel, width, stride, thresholds, chunk)
+    windows, scored, counts = _scan_tail_folded(panel, "scan-tail-panel", fasta_or_sequences, width, stride, thresholds,
+                                                device, chunk or default_panel_scan_chunk(panel.d, panel.n_models), on_chunk)
+    return dict(scored=scored, unscored=windows - scored, thresholds=thresholds, counts=counts)
+
+
+def scan_quantiles_with_panel(panel, fasta_or_sequences, width, stride=1, q=None, ranks=None, device=0, chunk=None,
+                              collect_cap=1 << 20, on_pass=None):
+    """`scan_quantiles` for every member of a panel, the same requests for all -> dict(scored, unscored (int64, one per
+    member), q, ranks, values (both (n_models, requests)), passes): row m is scan_quantiles' result for panel.table(m), bit
+    for bit.  One chunk loop per pass serves all members; each carries its own targets and collects when ITS targets fit
+    collect_cap, so a pass may count for one member and collect for another.  passes / on_pass(dict): kind, prefix_bits
+    and targets are lists, one entry per member still searching; the other keys are summed over them."""
+    qs, want = check_panel_scan_quantiles(panel, width, stride, q, ranks, chunk, collect_cap)
+    windows, found, passes = _scan_quantiles_folded(panel, "scan-quantiles-panel", fasta_or_sequences, width, stride,
+                                                    [want] * panel.n_models, int(collect_cap), device,
+                                                    chunk or default_panel_scan_chunk(panel.d, panel.n_models), on_pass)
+    scored = np.array([s.n for s in found], dtype=np.int64)
+    return dict(scored=scored, unscored=windows - scored, q=qs, ranks=np.stack([s.ranks for s in found]),
+                values=np.stack([s.values for s in found]), passes=passes)
+
+
+def write_panel_tail_counts(path, panel_names, result):
+    """The `scan-tail-panel` output: write_tail_counts' lines per member in panel order, the member's name in front."""
+    with open(path, "w") as f:
+        for m, member in enumerate(panel_names):
+            f.write("%s\t#scored\t%d\tunscored\t%d\n" % (member, result["scored"][m], result["unscored"][m]))
+            f.write("".join("%s\t%.17g\t%d\n" % ((member,) + row)
+                            for row in zip(result["thresholds"].tolist(), result["counts"][m].tolist())))
+
+
+def read_panel_tail_counts(path):
+    """-> ([(member, scored, unscored)], [(member, threshold, count)]) from a file written by write_panel_tail_counts."""
+    return _read_dist(path, 1, (float, int))
+
+
+def write_panel_quantiles(path, panel_names, result):
+    """The `scan-quantiles-panel` output: write_quantiles' lines per member in panel order, the member's name in front."""
+    with open(path, "w") as f:
+        for m, member in enumerate(panel_names):
+            f.write("%s\t#scored\t%d\tunscored\t%d\n" % (member, result["scored"][m], result["unscored"][m]))
+            for i, (r, v) in enumerate(zip(result["ranks"][m].tolist(), result["values"][m].tolist())):
+                f.write("%s\t%s\t%d\t%.17g\n" % (member, _q_text(result["q"], i), r, v))
+
+
+def read_panel_quantiles(path):
+    """-> ([(member, scored, unscored)], [(member, q or None, rank, value)]) from a file written by
+    write_panel_quantiles."""
+    return _read_dist(path, 1, (_q_value, int, float))
+
+
 def check_panel_delta(panel, variants=None, records=None, chunk=None):
     """What `delta_with_panel` and `delta_saturation_with_panel` refuse before they touch the device (check_delta's
     refusals)."""
@@ -2397,6 +2830,30 @@ def region_thresholds(text, panel=False):
     return values[0] if len(values) == 1 else values
 
 
+def _add_dist_options(p, quantiles):
+    p.add_argument("--width", type=int, required=True, help="bases per window (L..2047)")
+    p.add_argument("--stride", type=int, default=1, help="bases between window starts (default: 1)")
+    p.add_argument("--chunk", type=int, default=None, help="bases per device chunk (default: from device memory)")
+    if quantiles:
+        p.add_argument("--q", default=None, help="comma-separated quantiles in 0..1, at most 64")
+        p.add_argument("--ranks", default=None, help="comma-separated order statistics 0..n-1 instead of --q")
+        p.add_argument("--collect-cap", type=int, default=1 << 20,
+                       help="scores the last pass may gather on the device (default: 2^20)")
+    else:
+        p.add_argument("--thresholds", default="", help="comma-separated scores, at most 4096")
+
+
+def dist_list(option, text, convert):
+    """A comma-separated option -> its values, or None where it was not given."""
+    if text is None:
+        return None
+    try:
+        return [convert(x) for x in text.split(",")] if text else []
+    except ValueError:
+        raise ModelError("%s: %r is no comma-separated list of %s" % (option, text,
+                                                                     "integers" if convert is int else "numbers"))
+
+
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m gkmqc_amd.gkmpredict",
                                 description="train a gkm-SVM on all sequences / score FASTA sequences with it (MI355X)")
@@ -2477,6 +2934,16 @@ def build_parser():
                                                    "scan-regions' columns")
     _add_region_options(pr, "one value for all members or one per member, comma-separated (default: 0)")
     _add_arguments(pr, "panel", "seqs_fa", "output", block=False)
+    for name, panel, quantiles, what in (
+            ("scan-tail", False, False, "how many scored windows of a scan reach each of --thresholds, all records "
+                                        "pooled: #scored<TAB>n<TAB>unscored<TAB>m, then threshold<TAB>count"),
+            ("scan-quantiles", False, True, "exact quantiles (--q) or order statistics (--ranks) of a scan's scores, all "
+                                            "records pooled: #scored<TAB>n<TAB>unscored<TAB>m, then q<TAB>rank<TAB>value"),
+            ("scan-tail-panel", True, False, "scan-tail for every member of a panel: the member's name in front"),
+            ("scan-quantiles-panel", True, True, "scan-quantiles for every member of a panel: the member's name in front")):
+        ds = sub.add_parser(name, help=what)
+        _add_dist_options(ds, quantiles)
+        _add_arguments(ds, "panel" if panel else "weights", "seqs_fa", "output", block=False)
     pd = sub.add_parser("delta-panel", help="the effect of the variants of variants.tsv on the sequences of seqs.fa for "
                                             "every member of a panel: a header, then the variant's columns and one delta "
                                             "per member")
@@ -2589,6 +3056,30 @@ def main(argv=None):
                 n = write_regions(tmp, results)
             os.replace(tmp, a.output)
             print("%d regions at a threshold of %s, gap %d -> %s" % (n, a.threshold, a.gap, a.output), file=sys.stderr)
+        elif a.cmd in ("scan-tail", "scan-tail-panel", "scan-quantiles", "scan-quantiles-panel"):
+            if not os.path.isfile(a.seqs_fa):
+                raise ModelError("cannot read %s" % a.seqs_fa)
+            panel = a.cmd.endswith("-panel")
+            folded = load_lmer_panel(a.panel) if panel else load_lmer_table(a.weights)
+            tmp = a.output + ".tmp"
+            if a.cmd.startswith("scan-tail"):
+                thresholds = dist_list("--thresholds", a.thresholds, float)
+                check, compute = ((check_panel_scan_tail_counts, scan_tail_counts_with_panel) if panel else
+                                  (check_scan_tail_counts, scan_tail_counts))
+                check(folded, a.width, a.stride, thresholds, a.chunk)
+                result = compute(folded, a.seqs_fa, a.width, a.stride, thresholds, a.device, a.chunk)
+                (write_panel_tail_counts(tmp, folded.names, result) if panel else write_tail_counts(tmp, result))
+                what = "%d thresholds" % len(thresholds)
+            else:
+                q, ranks = dist_list("--q", a.q, float), dist_list("--ranks", a.ranks, int)
+                check, compute = ((check_panel_scan_quantiles, scan_quantiles_with_panel) if panel else
+                                  (check_scan_quantiles, scan_quantiles))
+                check(folded, a.width, a.stride, q, ranks, a.chunk, a.collect_cap)
+                result = compute(folded, a.seqs_fa, a.width, a.stride, q, ranks, a.device, a.chunk, a.collect_cap)
+                (write_panel_quantiles(tmp, folded.names, result) if panel else write_quantiles(tmp, result))
+                what = "%d order statistics in %d scans" % (len(q if ranks is None else ranks), len(result["passes"]))
+            os.replace(tmp, a.output)
+            print("%s of %s scored windows -> %s" % (what, np.max(result["scored"]), a.output), file=sys.stderr)
         elif a.cmd in ("delta", "delta-saturation"):
             for path in (a.seqs_fa,) + ((a.variants,) if a.cmd == "delta" else ()):
                 if not os.path.isfile(path):

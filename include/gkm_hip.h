@@ -327,6 +327,48 @@ int gkmhip_regions_fill(gkmhip_ctx *ctx, const double *score, int64_t ld, const 
                         void *stream);
 int gkmhip_regions_span(void);
 
+/* ---- the distribution of a scan's scores: digit histograms, edge histograms, bounded collection (DESIGN.md §5p;
+ * gkm_dist.hip) ----
+ * Over the nwin windows of a scan launch and their finished scores score[i ld], as the region calls take them.  Window i
+ * is SCORED when none of its width - L + 1 words of lm is flagged (bit 31) and score[i ld] is no NaN; what stands at any
+ * other window is never used as a value.  The KEY of a double with the bits b is b ^ (b >> 63 ? ~0 : 1 << 63), a
+ * bijection of 64-bit words under which ascending keys are ascending non-NaN doubles, -0.0 just below +0.0.
+ *
+ * gkmhip_dist_digit_bits: B, the bits of a key one refinement level resolves.  The 64 bits are resolved in
+ * ceil(64 / B) levels: the first takes the top 64 - B (levels - 1) bits, every later one the next B; the level
+ * boundaries are the numbers of bits resolved after each level.
+ * gkmhip_dist_scratch_bytes: what each call below needs as `scratch` (DEVICE, 8-byte aligned); -1 for nlm outside
+ * 1..2^40 - 1 or nwin outside 1..2^30.
+ *
+ * gkmhip_dist_digits ADDS to hist (DEVICE uint64, never zeroed here: a pass runs over many launches).  nprefix == 0
+ * (prefix_bits 0): every scored window adds 1 at hist[its key's first-level digit], 2^(first level's bits) counters.
+ * Otherwise prefix is a HOST array of 1..64 strictly ascending values of prefix_bits bits, prefix_bits a level boundary
+ * below 64 (anything else: error 2): a scored window whose key's top prefix_bits bits equal prefix[j] adds 1 at
+ * hist[j 2^B + the key's next B bits]; other windows add nothing.  hist: max(nprefix, 1) rows.
+ * gkmhip_dist_edges ADDS 1 at hist[#{j : edges[j] <= v}] for every scored window's score v (numpy's searchsorted(edges, v,
+ * side="right"), compared as doubles): edges DEVICE, nedges in 1..4096 ascending doubles without a NaN, which is the
+ * caller's duty (they are read on the device only); hist: nedges + 1 counters.
+ * gkmhip_dist_collect: every scored window whose key's top prefix_bits bits equal one of the 1..64 prefixes appends its
+ * score to out (DEVICE) at the running *counter (DEVICE int64, in and out): *counter advances by the matches whatever
+ * the capacity, and values at positions >= capacity are dropped, not written.  The order of the appended values is
+ * not defined; their multiset is.
+ *
+ * All counting is by integer atomics, so the counters are the same bytes on every run.  Nothing but the documented
+ * cells is written.  A workgroup owns 1024 consecutive windows.  The calls launch on `stream` and do not wait.
+ * last_kernel_name: k_dist_digits, k_dist_edges, k_dist_collect (the events bracket the prefix count of flagged words
+ * too); last_comparisons: nwin. */
+int gkmhip_dist_digit_bits(void);
+int64_t gkmhip_dist_scratch_bytes(int64_t nlm, int64_t nwin);
+int gkmhip_dist_digits(gkmhip_ctx *ctx, const double *score, int64_t ld, const uint32_t *lm, int64_t nlm, int width,
+                       int stride, int64_t nwin, const uint64_t *prefix, int nprefix, int prefix_bits, uint64_t *hist,
+                       void *scratch, int64_t scratch_bytes, void *stream);
+int gkmhip_dist_edges(gkmhip_ctx *ctx, const double *score, int64_t ld, const uint32_t *lm, int64_t nlm, int width,
+                      int stride, int64_t nwin, const double *edges, int nedges, uint64_t *hist, void *scratch,
+                      int64_t scratch_bytes, void *stream);
+int gkmhip_dist_collect(gkmhip_ctx *ctx, const double *score, int64_t ld, const uint32_t *lm, int64_t nlm, int width,
+                        int stride, int64_t nwin, const uint64_t *prefix, int nprefix, int prefix_bits, double *out,
+                        int64_t capacity, int64_t *counter, void *scratch, int64_t scratch_bytes, void *stream);
+
 /* ---- variant effects from an l-mer weight table: deltaSVM (gkm_delta.hip) ----
  * The change in the summed weights of the l-mers a variant touches.  For a base string z with n = len(z) - L + 1 l-mers
  * u_0 .. u_{n-1}, S(z) = ((0.0 + W[u_0]) + W[u_1]) + ... + W[u_{n-1}] in plain double additions, 0.0 when n < 1.  No
