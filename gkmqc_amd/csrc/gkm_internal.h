@@ -45,6 +45,11 @@
  *                          order-preserving key or by edges, and a bounded collection of the scores under key prefixes
  *                          (k_dist_digits, k_dist_edges, k_dist_collect), gkmhip_dist_digits, gkmhip_dist_edges,
  *                          gkmhip_dist_collect, gkmhip_dist_scratch_bytes, gkmhip_dist_digit_bits
+ *   gkm_wsim.hip           the kernel between every window of one long sequence and every window of another: tiles of
+ *                          window pairs whose l-mer pairs are compared once, a difference array per mismatch class, the
+ *                          normalisation by the windows' norms, the best column of every row (k_wsim_profiles,
+ *                          k_wsim_normalize, k_wsim_best), gkmhip_wsim_profiles, gkmhip_wsim_normalize, gkmhip_wsim_best,
+ *                          gkmhip_wsim_group
  */
 #ifndef GKM_INTERNAL_H
 #define GKM_INTERNAL_H

@@ -143,6 +143,15 @@ def load():
     L.gkmhip_scan_score.argtypes = (vp, vp, i64, vp, i32, i32, i64, vp, vp, vp)
     L.gkmhip_scan_group.restype = i32
     L.gkmhip_scan_group.argtypes = (vp, i32, i32)
+    if hasattr(L, "gkmhip_wsim_profiles"):   # (as the calls below: older builds lack them; GramContext's wsim methods say so)
+        L.gkmhip_wsim_profiles.restype = i32
+        L.gkmhip_wsim_profiles.argtypes = (vp, vp, i64, vp, i64, i32, i32, i32, i64, i64, vp, i64, vp, vp)
+        L.gkmhip_wsim_normalize.restype = i32
+        L.gkmhip_wsim_normalize.argtypes = (vp, vp, i64, i64, i64, vp, vp, vp)
+        L.gkmhip_wsim_best.restype = i32
+        L.gkmhip_wsim_best.argtypes = (vp, vp, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp, vp)
+        L.gkmhip_wsim_group.restype = i32
+        L.gkmhip_wsim_group.argtypes = (i32, i32, i32, i32, i32, vp, vp)
     if hasattr(L, "gkmhip_regions_count"):   # (as the panel calls below: older builds lack them; GramContext's
                                              # region methods say so when called on one)
         L.gkmhip_regions_scratch_bytes.restype = i64
@@ -284,6 +293,18 @@ def distance_weights(kernel_type, max_n, M=50, H=50.0):
     reference's w(n, p) (src/libgkm.c:912-925) equals wd[|n//2 - p|] for every n."""
     dmax = max_n // 2 + 1
     return np.ascontiguousarray(position_weights(kernel_type, 2 * dmax + 1, M, H)[dmax:])
+
+
+def wsim_group(L, d, width, stride_x, stride_y):
+    """(gx, gy): the windows of x and of y that one tile of k_wsim_profiles holds, a function of the five arguments only
+    (include/gkm_hip.h gkmhip_wsim_group; needs no device); (0, 0) for arguments the launch refuses."""
+    lib = load()
+    if not hasattr(lib, "gkmhip_wsim_group"):
+        raise GkmError("%s holds no gkmhip_wsim_group: it was built before the window-pair calls" % lib_path())
+    gx, gy = ctypes.c_int(0), ctypes.c_int(0)
+    lib.gkmhip_wsim_group(int(L), int(d), int(width), int(stride_x), int(stride_y), ctypes.addressof(gx),
+                          ctypes.addressof(gy))
+    return gx.value, gy.value
 
 
 class FlatSequences:
@@ -590,6 +611,41 @@ class GramContext:
     def scan_group(self, width, stride):
         """Windows per stretch of k_scan_profiles for (L, width, stride); 0 where the scan refuses them."""
         return self.lib.gkmhip_scan_group(self.handle, int(width), int(stride))
+
+    def _need_wsim(self):
+        if not hasattr(self.lib, "gkmhip_wsim_profiles"):
+            raise GkmError("%s holds no gkmhip_wsim_profiles: it was built before the window-pair calls" % lib_path())
+
+    def wsim_profiles(self, lmx_ptr, nlmx, lmy_ptr, nlmy, width, stride_x, stride_y, nwx, nwy, G_ptr, ld, prof_ptr=None,
+                      stream=0):
+        """The raw kernel values of nwx windows of x by nwy windows of y, `width` bases each at the two strides, into
+        G_ptr (doubles, leading dimension ld), and their exact profiles into prof_ptr (int32, nwx x nwy x (d + 1)) unless
+        it is None: lmx_ptr, lmy_ptr the words of scan_lmers from the first window on (include/gkm_hip.h
+        gkmhip_wsim_profiles)."""
+        self._need_wsim()
+        self._chk(self.lib.gkmhip_wsim_profiles(self.handle, lmx_ptr, int(nlmx), lmy_ptr, int(nlmy), int(width),
+                                                int(stride_x), int(stride_y), int(nwx), int(nwy), G_ptr, int(ld), prof_ptr,
+                                                stream), "gkmhip_wsim_profiles")
+
+    def wsim_normalize(self, G_ptr, ld, nwx, nwy, sqx_ptr, sqy_ptr, stream=0):
+        """In place G / (sqx[i] sqy[j]), RBF contexts exp(gamma (K - 1)); no unit diagonal (gkmhip_wsim_normalize)."""
+        self._need_wsim()
+        self._chk(self.lib.gkmhip_wsim_normalize(self.handle, G_ptr, int(ld), int(nwx), int(nwy), sqx_ptr, sqy_ptr, stream),
+                  "gkmhip_wsim_normalize")
+
+    def wsim_best(self, K_ptr, ld, nwx, nwy, start_x, stride_x, start_y, stride_y, min_separation, best_j_ptr, best_k_ptr,
+                  stream=0):
+        """Per row the eligible column with the largest K (the lower one on a tie) into best_j_ptr (int64, -1: none) and
+        its value into best_k_ptr (NaN: none); eligible: not a NaN, and the two windows' starts at least min_separation
+        bases apart (gkmhip_wsim_best)."""
+        self._need_wsim()
+        self._chk(self.lib.gkmhip_wsim_best(self.handle, K_ptr, int(ld), int(nwx), int(nwy), int(start_x), int(stride_x),
+                                            int(start_y), int(stride_y), int(min_separation), best_j_ptr, best_k_ptr,
+                                            stream), "gkmhip_wsim_best")
+
+    def wsim_group(self, width, stride_x, stride_y):
+        """(gx, gy): the windows of a tile of k_wsim_profiles for this context's (L, d); (0, 0) where refused."""
+        return wsim_group(self.L, self.d, width, stride_x, stride_y)
 
     def _need_regions(self):
         if not hasattr(self.lib, "gkmhip_regions_count"):

@@ -297,6 +297,46 @@ int gkmhip_scan_score(gkmhip_ctx *ctx, const uint32_t *lm, int64_t nlm, const ui
 /* windows per stretch of k_scan_profiles: a function of (L, width, stride) only; 0 for arguments the scan refuses */
 int gkmhip_scan_group(const gkmhip_ctx *ctx, int width, int stride);
 
+/* ---- windowed kernel matrices between two long sequences (gkm_wsim.hip) ----
+ * The gkm kernel between every window of `width` bases (L <= width <= 2047) of a record x at stride_x and every window
+ * of a record y at stride_y, each pair as if the two windows were sequences of their own.  Unweighted kernel types only
+ * (0..3): with positional weights a pair's value would depend on the window that holds it.  Like the scan calls these
+ * take the context for L, d, the coefficients, the RBF flag and gamma only, and plain DEVICE pointers.  lmx, lmy: the
+ * words of gkmhip_scan_lmers from the first window's first l-mer on (they may point into longer arrays); nlmx, nlmy: the
+ * words readable from there, at least (nw - 1) stride + n with n = width - L + 1.  Window i of x = the l-mers
+ * [i stride_x, i stride_x + n) of lmx, window j of y = [j stride_y, j stride_y + n) of lmy.
+ *
+ * gkmhip_wsim_profiles: G[i ld + j] = ((0.0 + c_0 P_0) + c_1 P_1) + ... + c_d P_d, the raw value of gkmhip_gram_rows for
+ * the two windows cut out, with
+ *   P_m(i, j) = sum_{p in window i} sum_{q in window j} ([m(f_p, g_q) = m] + [m(f_p, rc g_q) = m])
+ * and, where prof is not NULL, prof[(i nwy + j) (d + 1) + m] = P_m(i, j) (int32; 2 n^2 < 2^31).  Cells of G beyond
+ * column nwy of a row are not written; nothing else is.  A flagged l-mer takes part in no pair (the caller gives the
+ * windows that hold one a NaN norm).  One workgroup serves a tile of gkmhip_wsim_group windows of x by windows of y and
+ * compares every l-mer pair of the tile once per strand, not once per window pair.  last_kernel_ms / last_comparisons
+ * (the sum over tiles of 2 Sx Sy, the l-mer words of the tile on either axis) / last_kernel_name describe
+ * k_wsim_profiles.  Refused with error 2, nothing written: a NULL lmx, lmy or G, a width outside L..2047, a stride
+ * below 1, nwx or nwy outside 1..2^30 or more than 2^38 pairs, ld < nwy, windows beyond nlmx or nlmy, more than
+ * 2^31 - 1 tiles. */
+int gkmhip_wsim_profiles(gkmhip_ctx *ctx, const uint32_t *lmx, int64_t nlmx, const uint32_t *lmy, int64_t nlmy, int width,
+                         int stride_x, int stride_y, int64_t nwx, int64_t nwy, double *G, int64_t ld, int32_t *prof,
+                         void *stream);
+/* in place: G[i ld + j] / (sqx[i] sqy[j]) (the product first, one division, as gkmhip_normalize_block), RBF contexts
+ * exp(gamma (K - 1)) of that.  No unit diagonal is forced.  A NaN norm makes its row (sqx) or column (sqy) NaN.
+ * last_* describe k_wsim_normalize. */
+int gkmhip_wsim_normalize(gkmhip_ctx *ctx, double *G, int64_t ld, int64_t nwx, int64_t nwy, const double *sqx,
+                          const double *sqy, void *stream);
+/* per row i of K (nwx x nwy, leading dimension ld): best_j[i] = the ELIGIBLE column with the largest K[i ld + j], the
+ * lowest such j on a tie, best_k[i] = its value; -1 and NaN where no column is eligible.  Column j is eligible when
+ * K[i ld + j] is not a NaN and |start_x + i stride_x - (start_y + j stride_y)| >= min_separation (bases; 0: every
+ * column).  Starts and min_separation in 0..2^40.  One wave per row, no atomics.  last_* describe k_wsim_best. */
+int gkmhip_wsim_best(gkmhip_ctx *ctx, const double *K, int64_t ld, int64_t nwx, int64_t nwy, int64_t start_x,
+                     int64_t stride_x, int64_t start_y, int64_t stride_y, int64_t min_separation, int64_t *best_j,
+                     double *best_k, void *stream);
+/* windows of a tile of k_wsim_profiles along x and y: a function of (L, d, width, stride_x, stride_y) only; 1 along an
+ * axis whose stride is at least n.  Needs no context and no device.  0, or 2 (and 0, 0) for arguments the launch
+ * refuses. */
+int gkmhip_wsim_group(int L, int d, int width, int stride_x, int stride_y, int *gx, int *gy);
+
 /* ---- regions of a scan: thresholded runs of windows with their summits (gkm_regions.hip) ----
  * Over the nwin windows of a scan launch (the same lm, nlm, width, stride) and their finished scores score[i ld] (DEVICE;
  * ld >= 1, so a column of a panel's nwin x nm result is served where it lies).  Window i PASSES when none of its
