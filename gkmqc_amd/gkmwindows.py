@@ -24,6 +24,7 @@ import numpy as np
 
 from . import device as dv
 from . import gkmpredict as gp
+from .gkmquery import _norms_from_profiles
 
 MAX_WIDTH = gp.SCAN_MAX_WIDTH
 BLOCK_BYTES = gp.BLOCK_BYTES          # device memory one block of K (windows of x by windows of y, doubles) may take
@@ -116,7 +117,7 @@ def _axis_chunks(ctx, codes, valid, width, stride, chunk, c, dev, stream, ones):
         ctx.scan_lmers(d_codes.data_ptr(), d_valid.data_ptr(), b1 - b0, ax.lm.data_ptr(), stream)
         prof = torch.empty((w1 - w0, d + 1), dtype=torch.int64, device=dev)
         ctx.scan_profiles(ax.lm.data_ptr(), ax.nlm, ones.data_ptr(), width, stride, w1 - w0, prof.data_ptr(), stream)
-        ax.sq = gp._norms_from_profiles(prof, c)
+        ax.sq = _norms_from_profiles(prof, c)
         ok = torch.from_numpy(gp.window_validity(valid[b0:b1], width, stride)).to(dev)
         ax.sq.masked_fill_(~ok, float("nan"))
         yield ax

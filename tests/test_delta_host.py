@@ -194,15 +194,16 @@ def test_refusals(gp):
 
 
 def test_reference_allele_must_match_the_record(gp):
+    from gkmqc_amd.gkmdelta import _resolve_variants
     recs = _records(gp)
-    rec, pos, rlen, alts = gp._resolve_variants(recs, [("chr1 first", 7, "AACG", "A"), (0, 4, "TTC", "TTA"),
-                                                      ("chr1 first", 5, "A", "T"), ("two", 8, "", "ac")])
+    rec, pos, rlen, alts = _resolve_variants(recs, [("chr1 first", 7, "AACG", "A"), (0, 4, "TTC", "TTA"),
+                                                   ("chr1 first", 5, "A", "T"), ("two", 8, "", "ac")])
     assert rec.tolist() == [0, 0, 0, 1] and pos.tolist() == [8, 6, 5, 8] and rlen.tolist() == [3, 1, 1, 0]
     assert alts == [b"", b"\x00", b"\x03", b"\x00\x01"]                     # base 5 is invalid: any allele matches there
     with pytest.raises(gp.ModelError, match=r"variant 1 \('chr1 first', 7, 'AAGG', 'A'\).*does not match.*AACG"):
-        gp._resolve_variants(recs, [("two", 0, "A", "C"), ("chr1 first", 7, "AAGG", "A")])
+        _resolve_variants(recs, [("two", 0, "A", "C"), ("chr1 first", 7, "AAGG", "A")])
     with pytest.raises(gp.ModelError, match="does not match"):
-        gp._resolve_variants(recs, [("chr1 first", 0, "C", "C")])
+        _resolve_variants(recs, [("chr1 first", 0, "C", "C")])
     gp.check_delta(_table(gp), [("chr1 first", 0, "C", "C")], recs)        # (not check_delta's: it reads no bases)
 
 

@@ -257,7 +257,8 @@ def test_gather_entries_describe_their_kernels(dv, gp, itables, queries):
     ctx = dv.GramContext(*tab.kernel_params(), device=0)
     try:
         stream = torch.cuda.current_stream().cuda_stream
-        flat = gp._as_queries(qs)[0]
+        from gkmqc_amd import gkmquery
+        flat = gkmquery._as_queries(qs)[0]
         ctx.set_sequences(flat, stream)
         V = torch.from_numpy(tab.V).cuda()
         nb, lmers = int(flat.off[-1]), sum(len(x) - tab.L + 1 for x in qs)

@@ -78,13 +78,14 @@ class _Launcher:
         self.nb = sum(len(s) for s in seqs[c0:c1])
         c = dv.mismatch_weights(t, L, k)[:d + 1]
         self.sq = torch.empty(len(seqs), dtype=torch.float64, device="cuda")
-        gp._exact_norms(self.ctx, len(seqs), c, self.sq, self.stream)
+        from gkmqc_amd import gkmquery
+        gkmquery._exact_norms(self.ctx, len(seqs), c, self.sq, self.stream)
         self.ld = c1 - c0 + 3
         self.gx = torch.zeros((n_sv, self.ld), dtype=torch.float64, device="cuda")
         self.ctx.gram_block(self.rows, c0, c1, self.gx.data_ptr(), self.ld, self.stream)
         prof = torch.empty((self.nb, 4, d + 1), dtype=torch.int64, device="cuda")
         self.ctx.ism_self_profiles(c0, c1, prof.data_ptr(), self.stream)
-        self.ysq = gp._mutant_norms_sq(prof, c).sqrt_()
+        self.ysq = gkmquery._mutant_norms_sq(prof, c).sqrt_()
 
     def block(self, fu, fb, dual, pad=0, sentinel=-7.25, want_base=True):
         torch = self.torch

@@ -96,9 +96,10 @@ def test_an_rbf_table_is_refused(gp):
 def test_size_limit_is_checked_before_any_allocation(gp, monkeypatch):
     tables = _tables(gp, 9)
     assert gp.PANEL_MAX_BYTES >= 4 ** 12 * 64 * 8
-    monkeypatch.setattr(gp, "PANEL_MAX_BYTES", 4 ** 5 * 16 * 8)
+    from gkmqc_amd import gkmtables
+    monkeypatch.setattr(gkmtables, "PANEL_MAX_BYTES", 4 ** 5 * 16 * 8)
     assert gp.LmerPanel(tables).n_models == 9                              # ms = 16: exactly the limit
-    monkeypatch.setattr(gp, "PANEL_MAX_BYTES", 4 ** 5 * 16 * 8 - 1)
+    monkeypatch.setattr(gkmtables, "PANEL_MAX_BYTES", 4 ** 5 * 16 * 8 - 1)
     stacked = []
     monkeypatch.setattr(gp.np, "stack", lambda *a, **k: stacked.append(1))
     with pytest.raises(gp.ModelError, match="PANEL_MAX_BYTES"):

@@ -59,7 +59,8 @@ def test_reader_keeps_long_records_whole_and_marks_invalid_bases(gp, tmp_path):
 
 
 def test_code_arrays_take_values_from_four_up_as_invalid(gp):
-    recs = gp._as_scan_records([np.array([0, 3, 4, 255, 2], dtype=np.uint8), [1, 1]])
+    from gkmqc_amd import gkmscan
+    recs = gkmscan._as_scan_records([np.array([0, 3, 4, 255, 2], dtype=np.uint8), [1, 1]])
     assert [r[0] for r in recs] == ["seq0", "seq1"]
     assert recs[0][1].tolist() == [0, 3, 0, 0, 2] and recs[0][2].tolist() == [True, True, False, False, True]
     assert recs[1][2].all()

@@ -222,7 +222,8 @@ def test_train_svr_refuses_before_writing(gp, tmp_path):
 def test_train_svr_refuses_too_many_sequences_before_the_gram_matrix(gp, tmp_path, monkeypatch):
     names = ["s%d" % i for i in range(5)]
     fa = _fasta(tmp_path / "s.fa", names)
-    monkeypatch.setattr(gp, "MAX_SVR_SAMPLES", 4)
+    from gkmqc_amd import gkmmodel
+    monkeypatch.setattr(gkmmodel, "MAX_SVR_SAMPLES", 4)
 
     def no_gram(*a, **k):
         raise AssertionError("the Gram matrix must not be built")

@@ -1,4 +1,4 @@
-"""Time `delta` and `delta_saturation` (gkmqc_amd/gkmpredict.py) at gkmQC's shape table -- L=10 k=6 d=3 --
+"""Time `delta` and `delta_saturation` (gkmqc_amd/gkmdelta.py) at gkmQC's shape table -- L=10 k=6 d=3 --
 over a seeded record of 1 Mb: 1 000 000 random SNVs plus 100 000 indels through `delta`, the full saturation map, and
 the same variants the way a user could score them before -- score_with_table on the two materialised context strings per
 variant (the reference and the alternate allele with L - 1 bases on either side) -- in one run on one GPU.
@@ -36,6 +36,8 @@ def main():
     import torch
     from gkmqc_amd import device as dv
     from gkmqc_amd import gkmpredict as gp
+    from gkmqc_amd.gkmdelta import _resolve_variants
+    from gkmqc_amd.gkmscan import _as_scan_records
     L, k, d, T = 10, 6, 3, a.bases
     rng = np.random.default_rng(20)
     tw = rng.standard_normal(4 ** L)
@@ -55,7 +57,7 @@ def main():
             variants.append((0, p, "", gp.codes_to_text(rng.integers(0, 4, size=n))))
     nv = len(variants)
     t0 = time.perf_counter()
-    _, vpos, vrlen, valts = gp._resolve_variants(gp._as_scan_records([x]), variants)
+    _, vpos, vrlen, valts = _resolve_variants(_as_scan_records([x]), variants)
     resolve_s = time.perf_counter() - t0
     # the materialised route's strings: x[a:e] and x[a:pos] + alt + x[pos + r:e] per variant
     nm = min(nv, a.sample) if a.sample else nv

@@ -1,5 +1,5 @@
 """Randomised sweep of the column-range launch (gkmhip_gram_block + gkmhip_normalize_block, the scoring path of
-gkmqc_amd/gkmpredict.py) against the CPU oracle on the GPU box: the parameter draw and length modes of
+gkmqc_amd/gkmquery.py) against the CPU oracle on the GPU box: the parameter draw and length modes of
 tools/fuzz_parity.py, then per case a random ascending row subset (with rows inside the range and just either side of
 it), a random column range [c0, c1), a padded leading dimension, a sentinel-filled buffer with spare rows, every kernel
 (auto, general, bit-sliced where instantiated) and now and then GKM_FORCE_PACKED / GKM_COL_CHUNK (test infrastructure).

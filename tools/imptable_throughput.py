@@ -1,4 +1,4 @@
-"""Time per-base importance tables (gkmqc_amd/gkmpredict.py lmer_importance, explain_with_table,
+"""Time per-base importance tables (gkmqc_amd/gkmtables.py lmer_importance, explain_with_table,
 hypothetical_with_table) at gkmQC's shape: 600-bp peak-like sequences, L=10 k=6 d=3, weighted kernel
 (type 4).
 

@@ -1,4 +1,4 @@
-"""Time l-mer weight tables (gkmqc_amd/gkmpredict.py lmer_weights, score_with_table) at gkmQC's shape:
+"""Time l-mer weight tables (gkmqc_amd/gkmtables.py lmer_weights, score_with_table) at gkmQC's shape:
 600-bp peak-like sequences, L=10 k=6 d=3, weighted kernel (type 4).
 
     python tools/lmer_throughput.py [--n-train 5000 --n-query 100000 --no-l12 --json out.json]

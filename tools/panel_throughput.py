@@ -1,5 +1,5 @@
-"""Time the panel functions (gkmqc_amd/gkmpredict.py) against the loop over the single-table function on
-the same tables, at gkmQC's shape -- L=10 k=6 d=3, kernel type 4 -- in one process on one GPU:
+"""Time the panel functions (gkmqc_amd/gkmtables.py, gkmscan.py, gkmdelta.py) against the loop
+over the single-table function on the same tables, at gkmQC's shape -- L=10 k=6 d=3, kernel type 4 -- in one process on one GPU:
 
     scan     a seeded locus of 1 Mb at W = 600, strides 1 and 10      scan_with_panel            vs  n x scan
     score    100 000 seeded queries of 600 bp                         score_with_panel           vs  n x score_with_table

@@ -1,4 +1,4 @@
-"""Time training on all sequences and scoring new ones (gkmqc_amd/gkmpredict.py) at gkmQC's shape: 600-bp peak-like
+"""Time training on all sequences and scoring new ones (gkmqc_amd/gkmmodel.py, gkmquery.py) at gkmQC's shape: 600-bp peak-like
 sequences, L=10 k=6 d=3, weighted kernel (type 4).
 
     python tools/predict_throughput.py [--n-train 5000 --n-query 100000 --block 0 --json out.json]

@@ -1,4 +1,4 @@
-"""Time scan_quantiles and scan_tail_counts (gkmqc_amd/gkmpredict.py) against the route they replace --
+"""Time scan_quantiles and scan_tail_counts (gkmqc_amd/gkmscan.py) against the route they replace --
 `scan`, every window's score copied back, then numpy on the host -- at gkmQC's shape (L=10 k=6 d=3, kernel type 4,
 W = 600) in one process on one GPU:
 

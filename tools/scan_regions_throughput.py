@@ -1,4 +1,4 @@
-"""Time scan_regions (gkmqc_amd/gkmpredict.py) against the route it replaces -- `scan`, every window's
+"""Time scan_regions (gkmqc_amd/gkmscan.py) against the route it replaces -- `scan`, every window's
 score copied back, then the reduction on the host -- at gkmQC's shape (L=10 k=6 d=3, kernel type 4, W = 600) in one
 process on one GPU:
 

@@ -1,4 +1,4 @@
-"""Time `scan` (gkmqc_amd/gkmpredict.py) against the materialised path -- score_with_table on the same
+"""Time `scan` (gkmqc_amd/gkmscan.py) against the materialised path -- score_with_table on the same
 windows, each cut out as a query of its own -- at gkmQC's shape: type 4, L=10 k=6 d=3, windows of 600 bases over a seeded
 sequence of 1 Mb, at strides 1, 10, 50 and 600, in one run on one GPU.
 

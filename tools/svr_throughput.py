@@ -1,4 +1,4 @@
-"""Time epsilon-SVR training (gkmqc_amd/svmcv.py train_svr_folds, gkmqc_amd/gkmpredict.py train_svr) at gkmQC's shape:
+"""Time epsilon-SVR training (gkmqc_amd/svmcv.py train_svr_folds, gkmqc_amd/gkmmodel.py train_svr) at gkmQC's shape:
 600-bp peak-like sequences, L=10 k=6 d=3, weighted kernel (type 4), synthetic targets (class, GC content, noise).
 
     python tools/svr_throughput.py [--n 10000 --n-small 8000 --length 600 --no-sklearn --json out.json]
