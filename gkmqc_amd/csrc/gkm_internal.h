@@ -50,6 +50,11 @@
  *                          normalisation by the windows' norms, the best column of every row (k_wsim_profiles,
  *                          k_wsim_normalize, k_wsim_best), gkmhip_wsim_profiles, gkmhip_wsim_normalize, gkmhip_wsim_best,
  *                          gkmhip_wsim_group
+ *   gkm_walign.hip         the best local path through a block of that matrix: Smith-Waterman in doubles, one wave per
+ *                          tile and one launch per tile anti-diagonal, the edges carried in place, the best cell by
+ *                          shuffles, the traceback through squares of direction bytes staged in LDS (k_walign_init,
+ *                          k_walign_tiles, k_walign_best, k_walign_trace), gkmhip_walign_block, gkmhip_walign_trace,
+ *                          gkmhip_walign_tile, gkmhip_walign_scratch_bytes
  */
 #ifndef GKM_INTERNAL_H
 #define GKM_INTERNAL_H

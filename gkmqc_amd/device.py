@@ -152,6 +152,15 @@ def load():
         L.gkmhip_wsim_best.argtypes = (vp, vp, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp, vp)
         L.gkmhip_wsim_group.restype = i32
         L.gkmhip_wsim_group.argtypes = (i32, i32, i32, i32, i32, vp, vp)
+    if hasattr(L, "gkmhip_walign_block"):   # (older builds lack them; GramContext's walign methods say so)
+        L.gkmhip_walign_tile.restype = i32
+        L.gkmhip_walign_tile.argtypes = (vp, vp)
+        L.gkmhip_walign_scratch_bytes.restype = i64
+        L.gkmhip_walign_scratch_bytes.argtypes = (i64, i64)
+        L.gkmhip_walign_block.restype = i32
+        L.gkmhip_walign_block.argtypes = (vp, vp, i64, i64, i64, i32, dbl, dbl, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp)
+        L.gkmhip_walign_trace.restype = i32
+        L.gkmhip_walign_trace.argtypes = (vp, vp, i64, i64, i64, i64, i64, vp, i64, vp, vp)
     if hasattr(L, "gkmhip_regions_count"):   # (as the panel calls below: older builds lack them; GramContext's
                                              # region methods say so when called on one)
         L.gkmhip_regions_scratch_bytes.restype = i64
@@ -305,6 +314,26 @@ def wsim_group(L, d, width, stride_x, stride_y):
     lib.gkmhip_wsim_group(int(L), int(d), int(width), int(stride_x), int(stride_y), ctypes.addressof(gx),
                           ctypes.addressof(gy))
     return gx.value, gy.value
+
+
+def _walign_lib():
+    lib = load()
+    if not hasattr(lib, "gkmhip_walign_block"):
+        raise GkmError("%s holds no gkmhip_walign_block: it was built before the window-alignment calls" % lib_path())
+    return lib
+
+
+def walign_tile():
+    """(rows, columns) of a DP tile of k_walign_tiles (include/gkm_hip.h gkmhip_walign_tile; needs no device)."""
+    rows, cols = ctypes.c_int(0), ctypes.c_int(0)
+    _walign_lib().gkmhip_walign_tile(ctypes.addressof(rows), ctypes.addressof(cols))
+    return rows.value, cols.value
+
+
+def walign_scratch_bytes(nwx, nwy):
+    """The bytes of device scratch gkmhip_walign_block needs for a block of nwx x nwy cells; -1 for a shape it refuses
+    (needs no device)."""
+    return int(_walign_lib().gkmhip_walign_scratch_bytes(int(nwx), int(nwy)))
 
 
 class FlatSequences:
@@ -646,6 +675,35 @@ class GramContext:
     def wsim_group(self, width, stride_x, stride_y):
         """(gx, gy): the windows of a tile of k_wsim_profiles for this context's (L, d); (0, 0) where refused."""
         return wsim_group(self.L, self.d, width, stride_x, stride_y)
+
+    def _need_walign(self):
+        if not hasattr(self.lib, "gkmhip_walign_block"):
+            raise GkmError("%s holds no gkmhip_walign_block: it was built before the window-alignment calls" % lib_path())
+
+    def walign_block(self, K_ptr, ld, nwx, nwy, flip, offset, gap, top_ptr, left_ptr, corner_ptr, D_ptr, ldd, best_h_ptr,
+                     best_ic_ptr, scratch_ptr, scratch_bytes, stream=0):
+        """The local-alignment DP over one block of K in DP coordinates (column c reads K[i ld + nwy - 1 - c] with flip):
+        top (nwy doubles) and left (nwx doubles) are read as the cells beyond the block's edges and overwritten in place with
+        its last row and column, corner is H(-1, -1); D (uint8 [nwx][ldd]) may be None; best_h (one double) and best_ic (two
+        int64) receive the block's best cell (gkmhip_walign_block)."""
+        self._need_walign()
+        self._chk(self.lib.gkmhip_walign_block(self.handle, K_ptr, int(ld), int(nwx), int(nwy), int(bool(flip)), float(offset),
+                                               float(gap), top_ptr, left_ptr, corner_ptr, D_ptr, int(ldd), best_h_ptr,
+                                               best_ic_ptr, scratch_ptr, int(scratch_bytes), stream), "gkmhip_walign_block")
+
+    def walign_trace(self, D_ptr, ldd, nwx, nwy, end_i, end_c, path_ptr, capacity, count_ptr, stream=0):
+        """Walks D back from (end_i, end_c): the DIAG cells as (i, c) int32 pairs into path, end first; count: three int64,
+        the pairs and the cell at which the walk stopped (gkmhip_walign_trace)."""
+        self._need_walign()
+        self._chk(self.lib.gkmhip_walign_trace(self.handle, D_ptr, int(ldd), int(nwx), int(nwy), int(end_i), int(end_c),
+                                               path_ptr, int(capacity), count_ptr, stream), "gkmhip_walign_trace")
+
+    def walign_tile(self):
+        """(rows, columns) of a DP tile of k_walign_tiles."""
+        return walign_tile()
+
+    def walign_scratch_bytes(self, nwx, nwy):
+        return walign_scratch_bytes(nwx, nwy)
 
     def _need_regions(self):
         if not hasattr(self.lib, "gkmhip_regions_count"):

@@ -1,7 +1,8 @@
-"""Windowed gkm kernel matrices between two long sequences.
+"""Windowed gkm kernel matrices between two long sequences and the best path through one (§5r).
 
     window_kernel(x, y, width, ...)   K(i, j): the gkm kernel between window i of x and window j of y, every pair
     window_best(x, y, width, ...)     per window of x the window of y with the largest K, reduced on the device
+    window_align(x, y, width, ...)    the best local path through K (Smith-Waterman over the windows), found on the device
 
 A window is `width` bases at starts 0, stride, 2 stride, ...; a pair's value is, bit for bit, the off-diagonal entry that
 device.cross_kernel returns for the two windows cut out as sequences.  K covers both strands of y (the kernel compares an
@@ -13,6 +14,7 @@ l-mer pair of a tile of window pairs once, not once per window pair that holds i
 Command line:
     python -m gkmqc_amd.gkmwindows matrix --width W [--stride-x S --stride-y S --chunk B] [-t -L -k -d -G] x.fa y.fa out.npz
     python -m gkmqc_amd.gkmwindows best   --width W [... --min-separation B]                             x.fa y.fa out.tsv
+    python -m gkmqc_amd.gkmwindows align  --width W --offset o --gap g [--orientation forward|reverse|both ...]  x.fa y.fa out.tsv
 """
 import argparse
 import math
@@ -123,10 +125,12 @@ def _axis_chunks(ctx, codes, valid, width, stride, chunk, c, dev, stream, ones):
         yield ax
 
 
-def _blocks(what, x, y, width, stride_x, stride_y, kernel_type, L, k, d, gamma, device, chunk, min_separation, on_chunk):
-    """The chunk-pair loop both entry points share, a generator of (info, ax, ay, K, ctx, stream): K the finished block
+def _blocks(what, x, y, width, stride_x, stride_y, kernel_type, L, k, d, gamma, device, chunk, min_separation, on_chunk,
+            descending_y=False):
+    """The chunk-pair loop the entry points share, a generator of (info, ax, ay, K, ctx, stream): K the finished block
     (windows of ax by windows of ay, a float64 device tensor).  The first item is the dict of the result's host arrays.
-    The norms of a chunk are formed once: those of y before the loop, those of x once per chunk of x."""
+    The norms of a chunk are formed once: those of y before the loop, those of x once per chunk of x.  descending_y: per
+    chunk of x the chunks of y from the last to the first (the blocks themselves are the same)."""
     import torch
     xc, xv = _as_record(what, x)
     yc, yv = _as_record(what, y)
@@ -145,7 +149,7 @@ def _blocks(what, x, y, width, stride_x, stride_y, kernel_type, L, k, d, gamma, 
         ones = torch.ones(width - int(L) + 1, dtype=torch.uint8, device=dev)
         y_chunks = list(_axis_chunks(ctx, yc, yv, width, sy, chunk_y, c, dev, stream, ones))
         for ax in _axis_chunks(ctx, xc, xv, width, sx, chunk_x, c, dev, stream, ones):
-            for ay in y_chunks:
+            for ay in (y_chunks[::-1] if descending_y else y_chunks):
                 t0 = time.perf_counter()
                 nwx, nwy = ax.w1 - ax.w0, ay.w1 - ay.w0
                 K = torch.empty((nwx, nwy), dtype=torch.float64, device=dev)
@@ -235,7 +239,166 @@ def window_best(x, y, width, stride_x=1, stride_y=None, kernel_type=0, L=11, k=7
     return out
 
 
+# ------------------------------------------------------------------ alignment
+ORIENTATIONS = ("forward", "reverse", "both")
+TRACE_BYTES = 1 << 32                 # device memory the direction bytes of window_align (one per window pair) may take
+
+
+def check_window_align(x_len, y_len, width, stride_x=1, stride_y=None, kernel_type=0, L=11, k=7, d=3, gamma=1.0, offset=None,
+                       gap=None, orientation="forward", chunk=None, path=True, trace_bytes=TRACE_BYTES, what="window_align"):
+    """What window_align refuses, before the device is touched: everything check_window_kernel refuses, an offset that
+    is missing or not finite, a gap penalty that is missing, negative or not finite, an unknown orientation, and with
+    path=True more window pairs than `trace_bytes` direction bytes."""
+    check_window_kernel(x_len, y_len, width, stride_x, stride_y, kernel_type, L, k, d, gamma, chunk, 0, what)
+    stride_y = stride_x if stride_y is None else stride_y
+    if offset is None or not math.isfinite(float(offset)):
+        raise WindowError("%s: the offset (the K a window pair must exceed to gain) must be a finite number" % what)
+    if gap is None or not math.isfinite(float(gap)) or float(gap) < 0:
+        raise WindowError("%s: the gap penalty must be a finite number that is not negative" % what)
+    if orientation not in ORIENTATIONS:
+        raise WindowError("%s: the orientation must be one of %s" % (what, ", ".join(ORIENTATIONS)))
+    nA, nB = gp.scan_window_count(int(x_len), int(width), int(stride_x)), gp.scan_window_count(int(y_len), int(width), int(stride_y))
+    if path and nA * nB > int(trace_bytes):
+        raise WindowError("%s: %d x %d windows need %d direction bytes on the device, above trace_bytes = %d: use larger "
+                          "strides, path=False (the score and the end only) or a larger trace_bytes"
+                          % (what, nA, nB, nA * nB, int(trace_bytes)))
+
+
+def better_cell(a, b):
+    """k_walign_tiles' rule for (H, i, c) triples: a replaces b when its H is larger, or the same positive H lies at a
+    lower i, then a lower c.  Exact and associative; (0.0, -1, -1) stands for no cell."""
+    return a[0] > b[0] or (a[0] == b[0] and a[0] > 0.0 and (a[1], a[2]) < (b[1], b[2]))
+
+
+def _align_one(xa, ya, width, stride_x, stride_y, kernel_type, L, k, d, gamma, offset, gap, flip, device, chunk, path, on_chunk):
+    """One orientation: the DP carried across _blocks' chunk pairs, then one trace -> (host arrays of _blocks, score,
+    end (i, c), pairs (n, 2) int64 ascending, in DP coordinates).  On the device: a row vector over all windows of y
+    (H of the last row done, per DP column), a column vector per chunk of x, the corner of the next block, D."""
+    import torch
+    blocks = _blocks("window_align", xa, ya, width, stride_x, stride_y, kernel_type, L, k, d, gamma, device, chunk, 0, on_chunk,
+                     descending_y=flip)
+    out = next(blocks)
+    nA, nB = len(out["x_starts"]), len(out["y_starts"])
+    row = D = col = corner = ctx = stream = None
+    bests = []
+    at = -1
+    for info, ax, ay, K, ctx, stream in blocks:
+        dev = K.device
+        nwx, nwy = ax.w1 - ax.w0, ay.w1 - ay.w0
+        if row is None:
+            row = torch.zeros(nB, dtype=torch.float64, device=dev)
+            D = torch.empty((nA, nB), dtype=torch.uint8, device=dev) if path else None
+        if ax.w0 != at:                                        # a new row of blocks: H(., -1) = 0 and so is its corner
+            at = ax.w0
+            col = torch.zeros(nwx, dtype=torch.float64, device=dev)
+            corner = torch.zeros(1, dtype=torch.float64, device=dev)
+        c0 = nB - ay.w1 if flip else ay.w0                     # the block's first DP column
+        saved = row[c0 + nwy - 1:c0 + nwy].clone()             # H(i0 - 1, c1 - 1): the corner of the block to the right
+        need = dv.walign_scratch_bytes(nwx, nwy)
+        scratch = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+        bh = torch.empty(1, dtype=torch.float64, device=dev)
+        bic = torch.empty(2, dtype=torch.int64, device=dev)
+        ctx.walign_block(K.data_ptr(), nwy, nwx, nwy, flip, offset, gap, row.data_ptr() + 8 * c0, col.data_ptr(),
+                         corner.data_ptr(), None if D is None else D.data_ptr() + ax.w0 * nB + c0, nB, bh.data_ptr(),
+                         bic.data_ptr(), scratch.data_ptr(), need, stream)
+        corner = saved
+        bests.append((bh, bic, ax.w0, c0))
+        if on_chunk is not None:
+            info["align_kernel_ms"] = ctx.last_kernel_ms()
+        _report(on_chunk, info)
+    best = (0.0, -1, -1)
+    for bh, bic, i0, c0 in bests:                              # (the first read waits for the stream)
+        i, c = bic.tolist()
+        if i >= 0 and better_cell((bh.item(), i + i0, c + c0), best):
+            best = (bh.item(), i + i0, c + c0)
+    pairs = np.zeros((0, 2), dtype=np.int64)
+    if path and best[1] >= 0:
+        cap = min(nA, nB)
+        d_path = torch.empty((cap, 2), dtype=torch.int32, device=D.device)
+        d_count = torch.empty(3, dtype=torch.int64, device=D.device)
+        ctx.walign_trace(D.data_ptr(), nB, nA, nB, best[1], best[2], d_path.data_ptr(), cap, d_count.data_ptr(), stream)
+        n = int(d_count[0].item())
+        pairs = d_path[:n].cpu().numpy().astype(np.int64)[::-1]
+    return out, best[0], (best[1], best[2]), pairs
+
+
+def window_align(x, y, width, stride_x=1, stride_y=None, kernel_type=0, L=11, k=7, d=3, gamma=1.0, offset=None, gap=None,
+                 orientation="forward", device=0, chunk=None, path=True, trace_bytes=TRACE_BYTES, on_chunk=None):
+    """The best local path through window_kernel's matrix: the chain of window pairs of x and y that resemble each other,
+    with its insertions and deletions, found on the device beside the blocks of K (which never leave it).  Smith-Waterman
+    with a linear gap penalty in doubles: a matched pair (i, j) gains K[i, j] - offset, a window skipped on either axis
+    costs gap; offset and gap are required (with offset 0 every pair gains and the alignment is the whole matrix).  A
+    pair whose K is NaN (a window over a non-ACGT character) is never matched but may be skipped at the gap's cost.
+    orientation: "forward" (y ascending along the path), "reverse" (y descending: an inverted element; K itself covers
+    both strands and does not tell) or "both" (the two runs one after the other -- K is computed twice -- and the larger
+    score, forward on a tie).
+    -> dict(score, orientation, end, start, x_index, y_index, x_start, y_start, x_valid, y_valid): the score is the
+    largest H (0.0: no pair gains; the path is empty, end and start (-1, -1)); end = (i, j), the last matched pair in x's
+    order, the best cell (the lower i, then the lower DP column on a tie); start = the first matched pair; the matched
+    pairs as window indices and as base starts, ascending in x; j in y's own numbering whatever the orientation.  With
+    path=False no direction bytes are kept: dict(score, orientation, end) only.  The same bytes for every `chunk`, and
+    bit for bit what a plain loop over window_kernel's K gives.  trace_bytes: the most direction bytes (one per window
+    pair) the device may hold.  on_chunk(dict): as window_kernel's, with align_kernel_ms, the DP's milliseconds for the
+    block.  The K along the path is not returned (the blocks are gone when the path is known): window_kernel on the
+    path's span gives it."""
+    xc, xv = _as_record("window_align", x)
+    yc, yv = _as_record("window_align", y)
+    check_window_align(len(xc), len(yc), width, stride_x, stride_y, kernel_type, L, k, d, gamma, offset, gap, orientation, chunk,
+                       path, trace_bytes)
+    xa, ya = np.where(xv, xc, 4).astype(np.uint8), np.where(yv, yc, 4).astype(np.uint8)
+    got = None
+    for name in (("forward", "reverse") if orientation == "both" else (orientation,)):
+        r = _align_one(xa, ya, width, stride_x, stride_y, kernel_type, L, k, d, gamma, float(offset), float(gap),
+                       name == "reverse", device, chunk, path, on_chunk)
+        if got is None or r[1] > got[1][1]:
+            got = (name, r)
+    name, (out, score, (ei, ec), pairs) = got
+    nB = len(out["y_starts"])
+    to_y = (lambda c: nB - 1 - c) if name == "reverse" else (lambda c: c)
+    res = dict(score=score, orientation=name, end=(ei, to_y(ec) if ei >= 0 else -1))
+    if not path:
+        return res
+    xi, yi = pairs[:, 0], to_y(pairs[:, 1])
+    res.update(start=(int(xi[0]), int(yi[0])) if len(xi) else (-1, -1), x_index=xi, y_index=yi, x_start=out["x_starts"][xi],
+               y_start=out["y_starts"][yi], x_valid=out["x_valid"], y_valid=out["y_valid"])
+    return res
+
+
 # ------------------------------------------------------------------ files
+ALIGN_FORMAT = "#score\t%.17g\torientation\t%s\tend\t%d\t%d\tstart\t%d\t%d\tpairs\t%d\n"
+
+
+def write_window_align(path, result):
+    """The `align` output: a header line #score<TAB>score (%.17g)<TAB>orientation<TAB>name<TAB>end<TAB>i<TAB>j<TAB>start
+    <TAB>i<TAB>j<TAB>pairs<TAB>n (window indices), then x_start<TAB>y_start (0-based bases) per matched pair, ascending
+    in x."""
+    with open(path, "w") as f:
+        f.write(ALIGN_FORMAT % ((result["score"], result["orientation"]) + tuple(result["end"]) + tuple(result["start"])
+                                + (len(result["x_start"]),)))
+        f.write("".join("%d\t%d\n" % p for p in zip(result["x_start"].tolist(), result["y_start"].tolist())))
+
+
+def read_window_align(path):
+    """-> dict(score, orientation, end, start, x_start, y_start) from a file written by write_window_align."""
+    with open(path) as f:
+        lines = f.read().split("\n")[:-1]
+    head = lines[0].split("\t") if lines else []
+    if len(head) != 12 or [head[i] for i in (0, 2, 4, 7, 10)] != ["#score", "orientation", "end", "start", "pairs"] \
+            or head[3] not in ORIENTATIONS[:2]:
+        raise WindowError("%s: no window alignment header" % path)
+    try:
+        out = dict(score=float(head[1]), orientation=head[3], end=(int(head[5]), int(head[6])), start=(int(head[8]), int(head[9])))
+        rows = [(int(a), int(b)) for a, b in (line.split("\t") for line in lines[1:])]
+        count = int(head[11])
+    except ValueError:
+        raise WindowError("%s: expected a number, window indices and two integers per line" % path)
+    if count != len(rows):
+        raise WindowError("%s: the header announces %d pairs, %d follow" % (path, count, len(rows)))
+    out["x_start"] = np.array([r[0] for r in rows], dtype=np.int64)
+    out["y_start"] = np.array([r[1] for r in rows], dtype=np.int64)
+    return out
+
+
 def write_window_kernel(path, result, width):
     """The `matrix` output: an uncompressed .npz (np.savez) of K, the two start arrays, the two validity masks, the width
     and a format tag."""
@@ -288,7 +451,8 @@ def build_parser():
     p = argparse.ArgumentParser(prog="gkmwindows", description=__doc__.split("\n\n")[0])
     sub = p.add_subparsers(dest="cmd", required=True)
     for name, text in (("matrix", "the kernel between every window of x and every window of y -> .npz"),
-                       ("best", "per window of x the best window of y -> TSV")):
+                       ("best", "per window of x the best window of y -> TSV"),
+                       ("align", "the best local path through the matrix: the chain of matching window pairs -> TSV")):
         q = sub.add_parser(name, help=text)
         q.add_argument("--width", type=int, required=True, help="bases per window (L..%d)" % MAX_WIDTH)
         q.add_argument("--stride-x", type=int, default=1, help="bases between window starts of x (default 1)")
@@ -296,6 +460,10 @@ def build_parser():
         if name == "best":
             q.add_argument("--min-separation", type=int, default=0,
                            help="least distance in bases between the two windows' starts (default 0: any)")
+        if name == "align":
+            q.add_argument("--offset", type=float, required=True, help="the K a window pair must exceed to gain")
+            q.add_argument("--gap", type=float, required=True, help="the cost of a window skipped on either axis (>= 0)")
+            q.add_argument("--orientation", default="forward", help="forward, reverse or both (default forward)")
         q.add_argument("--chunk", type=int, default=None, help="bases per device chunk on either axis")
         q.add_argument("-t", "--kernel-type", type=int, default=0, help="0 gapped k-mer, 1 estimated l-mer with full "
                        "filter, 2 truncated filter, 3 gkm with RBF (default 0)")
@@ -322,6 +490,12 @@ def main(argv=None):
             os.replace(tmp, a.output)
             print("%d x %d windows, %d and %d over a non-ACGT character (nan) -> %s"
                   % (len(r["x_starts"]), len(r["y_starts"]), int((~r["x_valid"]).sum()), int((~r["y_valid"]).sum()), a.output),
+                  file=sys.stderr)
+        elif a.cmd == "align":
+            r = window_align(*args[:-2], offset=a.offset, gap=a.gap, orientation=a.orientation, device=a.device, chunk=a.chunk)
+            write_window_align(tmp, r)
+            os.replace(tmp, a.output)
+            print("score %.6g, %s, %d matched window pairs -> %s" % (r["score"], r["orientation"], len(r["x_start"]), a.output),
                   file=sys.stderr)
         else:
             r = window_best(*args, min_separation=a.min_separation)

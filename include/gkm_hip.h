@@ -337,6 +337,48 @@ int gkmhip_wsim_best(gkmhip_ctx *ctx, const double *K, int64_t ld, int64_t nwx, 
  * refuses. */
 int gkmhip_wsim_group(int L, int d, int width, int stride_x, int stride_y, int *gx, int *gy);
 
+/* ---- the best local path through a windowed kernel matrix (gkm_walign.hip) ----
+ * Smith-Waterman with a linear gap penalty, in doubles, over a block K (nwx x nwy, leading dimension ld) as
+ * gkmhip_wsim_normalize leaves it, in DP coordinates (i, c): i the row of K, c its DP column, which reads K[i ld + c], or
+ * with flip != 0 K[i ld + nwy - 1 - c] (the columns walked backwards: the reverse orientation).  With offset finite and
+ * gap >= 0 finite,
+ *   v = K(i, j(c));  h = 0.0, dir = 0 (STOP)
+ *   if v == v:  t = H(i-1, c-1) + (v - offset);  if t > h: h = t, dir = 1 (DIAG)
+ *   t = H(i-1, c) - gap;                         if t > h: h = t, dir = 2 (UP)
+ *   t = H(i, c-1) - gap;                         if t > h: h = t, dir = 3 (LEFT)
+ *   H(i, c) = h;  D(i, c) = dir
+ * every comparison a strict >, in that order; a NaN K takes no diagonal step but may be crossed by gap steps.  The bits
+ * of every H follow from the definition alone: not from the tiling, the launch or the run.
+ *
+ * gkmhip_walign_block: the DP over one block, the cells beyond its upper and left edge given by the caller, so that a
+ * matrix cut into blocks is served block row by block row, each from left to right in DP columns.  top: nwy doubles,
+ * read as H(-1, 0..nwy-1) and overwritten in place with the block's last row; left: nwx doubles, read as H(0..nwx-1, -1)
+ * and overwritten in place with the block's last column; corner: one DEVICE double, H(-1, -1), read only.  D: NULL (a
+ * score-only run) or uint8 [nwx][ldd], D[i ldd + c] in DP coordinates; cells beyond column nwy of a row are not written.
+ * best_h (one double) and best_ic (two int64: i, c, local to the block): the block's best cell -- the largest H, the
+ * lower i and then the lower c on a tie -- or (0.0, -1, -1) where no H is positive.  scratch: DEVICE, 8-byte aligned, at
+ * least gkmhip_walign_scratch_bytes(nwx, nwy) bytes (-1 for nwx or nwy outside 1..2^20).  One wave serves a tile of
+ * gkmhip_walign_tile rows by columns (needs no context and no device); tile (I, J) needs (I-1, J) and (I, J-1), so the
+ * call issues one launch per tile anti-diagonal on `stream`, tiles_x + tiles_y - 1 of them, and does not wait: no
+ * workgroup waits for another.  No atomics.  last_kernel_ms (all the call's launches) / last_kernel_name describe
+ * k_walign_tiles; last_comparisons: nwx nwy cells.  Refused with error 2, nothing written: a NULL pointer other than D,
+ * ld < nwy, ldd < nwy (with or without D), nwx or nwy outside 1..2^20, a non-finite offset, a gap that is negative or not finite,
+ * a scratch too small. */
+int gkmhip_walign_tile(int *rows, int *cols);
+int64_t gkmhip_walign_scratch_bytes(int64_t nwx, int64_t nwy);
+int gkmhip_walign_block(gkmhip_ctx *ctx, const double *K, int64_t ld, int64_t nwx, int64_t nwy, int flip, double offset,
+                        double gap, double *top, double *left, const double *corner, uint8_t *D, int64_t ldd,
+                        double *best_h, int64_t *best_ic, void *scratch, int64_t scratch_bytes, void *stream);
+/* Walks D (uint8 [nwx][ldd], the WHOLE problem's, in DP coordinates) back from (end_i, end_c): DIAG to (i-1, c-1), UP to
+ * (i-1, c), LEFT to (i, c-1), until a STOP cell (any byte but 1, 2, 3 stops) or until the walk leaves the matrix.  path:
+ * the DIAG cells as (i, c) int32 pairs from the end backwards; count: three int64, the number of pairs and the cell (i, c)
+ * at which the walk stopped (the STOP cell, or the first cell outside: i or c is -1).  One wave; the 64 x 64 direction
+ * bytes up-left of the current cell are staged in LDS and walked there.  Every step lowers i + c: at most nwx + nwy
+ * steps whatever D holds.  last_* describe k_walign_trace.  Refused with error 2, nothing written: a NULL pointer,
+ * ldd < nwy, nwx or nwy outside 1..2^20, an end cell outside the matrix, capacity < min(nwx, nwy) pairs. */
+int gkmhip_walign_trace(gkmhip_ctx *ctx, const uint8_t *D, int64_t ldd, int64_t nwx, int64_t nwy, int64_t end_i,
+                        int64_t end_c, int32_t *path, int64_t capacity, int64_t *count, void *stream);
+
 /* ---- regions of a scan: thresholded runs of windows with their summits (gkm_regions.hip) ----
  * Over the nwin windows of a scan launch (the same lm, nlm, width, stride) and their finished scores score[i ld] (DEVICE;
  * ld >= 1, so a column of a panel's nwin x nm result is served where it lies).  Window i PASSES when none of its
