@@ -176,7 +176,7 @@ extern "C" void gkmhip_destroy(gkmhip_ctx *ctx)
     for (auto &scr : ctx->scratch) scr.release();
     ctx->sq.release();
     ctx->blk_rows.release(); ctx->blk_part.release(); ctx->ism_gpart.release(); ctx->ism_pself.release();
-    ctx->delta_alt.release();
+    ctx->delta_alt.release(); ctx->contract_part.release();
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     for (auto &pr : ctx->tl_pairs) {

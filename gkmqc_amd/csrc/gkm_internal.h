@@ -55,6 +55,11 @@
  *                          shuffles, the traceback through squares of direction bytes staged in LDS (k_walign_init,
  *                          k_walign_tiles, k_walign_best, k_walign_trace), gkmhip_walign_block, gkmhip_walign_trace,
  *                          gkmhip_walign_tile, gkmhip_walign_scratch_bytes
+ *   gkm_contract.hip       a weight table or panel contracted with position weight windows, one fixed order of rounded
+ *                          operations: tiles of 4^6 codes, 16 weights per lane and the levels across lanes through LDS,
+ *                          or the lanes across models and a serial walk, then a fold launch over the tiles' partials
+ *                          (k_lmer_contract, k_panel_contract, k_contract_fold), gkmhip_lmer_contract,
+ *                          gkmhip_panel_contract, gkmhip_contract_max_windows, gkmhip_contract_scratch_bytes
  */
 #ifndef GKM_INTERNAL_H
 #define GKM_INTERNAL_H
@@ -197,6 +202,8 @@ struct gkmhip_ctx {
     DevBuf<int64_t> ism_pself;
     /* gkmhip_delta_variants: the alternate bases of the call (its variant table goes through upload_rows) */
     DevBuf<uint8_t> delta_alt;
+    /* gkmhip_lmer_contract, gkmhip_panel_contract: the tiles' partials, consumed by the call's own fold launch */
+    DevBuf<double> contract_part;
 };
 
 /* the pair of events the next timed kernel is bracketed by (gkm_context.hip; the Gram launches call it themselves) */

@@ -195,6 +195,15 @@ def load():
         L.gkmhip_panel_delta_sat.argtypes = (vp, vp, i64, i64, i64, vp, i32, i32, vp, vp)
         L.gkmhip_panel_delta_variants.restype = i32
         L.gkmhip_panel_delta_variants.argtypes = (vp, vp, vp, i64, vp, i32, vp, i64, vp, i32, i32, vp, vp)
+    if hasattr(L, "gkmhip_lmer_contract"):   # (older builds lack them; GramContext's contract methods say so)
+        L.gkmhip_contract_max_windows.restype = i64
+        L.gkmhip_contract_max_windows.argtypes = (i32, i32)
+        L.gkmhip_contract_scratch_bytes.restype = i64
+        L.gkmhip_contract_scratch_bytes.argtypes = (i32, i32, i64)
+        L.gkmhip_lmer_contract.restype = i32
+        L.gkmhip_lmer_contract.argtypes = (vp, vp, vp, i64, vp, vp)
+        L.gkmhip_panel_contract.restype = i32
+        L.gkmhip_panel_contract.argtypes = (vp, vp, i32, i32, vp, i64, vp, i64, vp)
     L.gkmhip_nullidx_tile.restype = i32
     L.gkmhip_nullidx_tile.argtypes = ()
     L.gkmhip_nullidx_scratch_bytes.restype = i64
@@ -334,6 +343,24 @@ def walign_scratch_bytes(nwx, nwy):
     """The bytes of device scratch gkmhip_walign_block needs for a block of nwx x nwy cells; -1 for a shape it refuses
     (needs no device)."""
     return int(_walign_lib().gkmhip_walign_scratch_bytes(int(nwx), int(nwy)))
+
+
+def _contract_lib():
+    lib = load()
+    if not hasattr(lib, "gkmhip_lmer_contract"):
+        raise GkmError("%s holds no gkmhip_lmer_contract: it was built before the window contraction calls" % lib_path())
+    return lib
+
+
+def contract_max_windows(L, n_models=0):
+    """The most windows one lmer_contract (n_models = 0) or panel_contract call takes; -1 for refused arguments (needs no
+    device)."""
+    return int(_contract_lib().gkmhip_contract_max_windows(int(L), int(n_models)))
+
+
+def contract_scratch_bytes(L, n_models, nwin):
+    """The bytes of partial values the context holds for such a call (0 for L <= 6); -1 for refused arguments."""
+    return int(_contract_lib().gkmhip_contract_scratch_bytes(int(L), int(n_models), int(nwin)))
 
 
 class FlatSequences:
@@ -840,6 +867,20 @@ class GramContext:
         var, alt, args = self._variant_arrays(var, alt)
         self._chk(self.lib.gkmhip_panel_delta_variants(self.handle, lm_ptr, codes_ptr, int(nbases), *args, P_ptr, int(nm),
                                                        int(ms), out_ptr, stream), "gkmhip_panel_delta_variants")
+
+    # windows of position weights contracted with a table or a panel (include/gkm_hip.h; gkm_contract.hip): P_ptr = nwin x L x 4
+    # device doubles
+    def lmer_contract(self, W_ptr, P_ptr, nwin, out_ptr, stream=0):
+        """a(P) of every window against the table at W_ptr (4^L device doubles) -> out_ptr, nwin doubles
+        (gkmhip_lmer_contract)."""
+        self._chk(_contract_lib().gkmhip_lmer_contract(self.handle, W_ptr, P_ptr, int(nwin), out_ptr, stream),
+                  "gkmhip_lmer_contract")
+
+    def panel_contract(self, rows_ptr, nm, ms, P_ptr, nwin, out_ptr, ld, stream=0):
+        """lmer_contract for every model of a panel -> out_ptr, nwin x ld doubles of which the first nm of a row are
+        written (gkmhip_panel_contract)."""
+        self._chk(_contract_lib().gkmhip_panel_contract(self.handle, rows_ptr, int(nm), int(ms), P_ptr, int(nwin), out_ptr,
+                                                        int(ld), stream), "gkmhip_panel_contract")
 
     def self_norms(self, sq_ptr, stream=0):
         self._chk(self.lib.gkmhip_self_norms(self.handle, sq_ptr, stream), "gkmhip_self_norms")

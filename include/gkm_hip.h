@@ -503,6 +503,31 @@ int gkmhip_panel_delta_variants(gkmhip_ctx *ctx, const uint32_t *lm, const uint8
                                 int nvar, const uint8_t *alt, int64_t nalt, const double *P, int nm, int ms, double *out,
                                 void *stream);
 
+/* ---- a weight table or panel contracted with position weight windows (gkm_contract.hip) ----
+ * A window is L rows of four doubles, P[i][b]: l-mer position i (0 the first base, the highest bit pair of a code), base b
+ * (A, C, G, T).  Its value a(P) = sum over all 4^L codes u of W(u) prod_i P[i][u_i] is evaluated in one fixed order, the
+ * last base first, every product and sum rounded:
+ *   T_L[u] = W[u];  T_i[v] = ((T_{i+1}[4v] P[i][0] + T_{i+1}[4v+1] P[i][1]) + T_{i+1}[4v+2] P[i][2]) + T_{i+1}[4v+3] P[i][3]
+ *   a(P) = T_0[0]
+ * so the bits written follow from W and P alone: not from the tiling, the launches or the run.  No atomics.
+ *   gkmhip_lmer_contract   W: 4^L DEVICE doubles; P: nwin x L x 4 DEVICE doubles; out: nwin doubles
+ *   gkmhip_panel_contract  rows: the panel image (4^L rows of ms doubles, as above); out: nwin x ld doubles, ld >= nm, row w
+ *                          holds the nm models' values of window w, cells nm..ld-1 keep their bytes; column m is, bit for
+ *                          bit, gkmhip_lmer_contract on the table rows[:, m]
+ * The partial values of the tiles (L > 6) live in the context and grow on demand, gkmhip_contract_scratch_bytes(L, nm,
+ * nwin) bytes of them (nm = 0: a single table; -1 for refused arguments): the caller provides no scratch, and calls on
+ * one context must be ordered by their streams.  nwin == 0 succeeds without a launch.  Refused with error 2, nothing
+ * written: a NULL pointer, nwin < 0 or above gkmhip_contract_max_windows(L, nm) (at most GKMHIP_CONTRACT_MAX_WINDOWS, fewer
+ * where the partials would pass 4 GiB; -1 for L outside 2..12 or nm outside 0..64), ld < nm, nm outside 1..64, a bad ms.
+ * last_kernel_ms covers the tile kernel and the fold; last_kernel_name: k_lmer_contract / k_panel_contract;
+ * last_comparisons: 4^L nwin (times nm). */
+#define GKMHIP_CONTRACT_MAX_WINDOWS 65536
+int64_t gkmhip_contract_max_windows(int L, int nm);
+int64_t gkmhip_contract_scratch_bytes(int L, int nm, int64_t nwin);
+int gkmhip_lmer_contract(gkmhip_ctx *ctx, const double *W, const double *P, int64_t nwin, double *out, void *stream);
+int gkmhip_panel_contract(gkmhip_ctx *ctx, const double *rows, int nm, int ms, const double *P, int64_t nwin, double *out,
+                          int64_t ld, void *stream);
+
 /* ---- the genome window index of null-sequence sampling (gkm_nullidx.hip) ----
  * One chromosome: seq = T raw FASTA bytes, line breaks removed, case kept; t = the window width, 1 <= t <= 2047.  Per byte:
  * na (one of nN), cg (one of cgCG), rp (one of acgt); any other byte sets none.  The windows are the starts i in
