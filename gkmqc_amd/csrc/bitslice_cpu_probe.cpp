@@ -252,6 +252,41 @@ extern "C" int bsprobe_group_any_centres_forms(int L, int d, const uint32_t *Ahi
     return 1;
 }
 
+/* ---- the centres entry's shift-shared form (tests/test_shift_shared_trees.py) -----------------------
+ * window_group_any_grouped and the three forms of window_group_any_centres -- shift-shared (SHIFTED = true, what the shift-record
+ * kernel runs), shared and private -- on the planes given; AVg[2] is taken as it comes.  *taken: is the shift-shared form compiled
+ * for this (L, d) (shift_shared_serves), or does SHIFTED = true stay on the shared form?  Return codes as
+ * bsprobe_group_any_crossings. */
+template <int W, int L, int D, int GRP>
+static int run_group_any_shift_shared(const uint32_t *Ahi, const uint32_t *Alo, const uint32_t *AVg, const uint32_t *Bhi,
+                                      const uint32_t *Blo, uint32_t *any_grouped, uint32_t *any_shifted, uint32_t *any_shared,
+                                      uint32_t *any_private, int *taken)
+{
+    if constexpr (!top_plane_serves(L, D)) {
+        return 2;
+    } else {
+        window_group_any_grouped<W, L, D, GRP>(Ahi, Alo, AVg, Bhi, Blo, any_grouped);
+        window_group_any_centres<W, L, D, GRP, true, true>(Ahi, Alo, AVg, Bhi, Blo, any_shifted);
+        window_group_any_centres<W, L, D, GRP>(Ahi, Alo, AVg, Bhi, Blo, any_shared);
+        window_group_any_centres<W, L, D, GRP, false>(Ahi, Alo, AVg, Bhi, Blo, any_private);
+        *taken = shift_shared_serves(W, L, D, GRP) ? 1 : 0;
+        return 0;
+    }
+}
+
+#define HCASE(LL, DD) \
+    if (L == LL && d == DD) return run_group_any_shift_shared<10, LL, DD, 5>(Ahi, Alo, AVg, Bhi, Blo, any_grouped, any_shifted, any_shared, any_private, taken);
+#define HCASE_L(LL) HCASE(LL, 0) HCASE(LL, 1) HCASE(LL, 2) HCASE(LL, 3) HCASE(LL, 4)
+
+extern "C" int bsprobe_group_any_shift_shared(int L, int d, const uint32_t *Ahi, const uint32_t *Alo, const uint32_t *AVg,
+                                              const uint32_t *Bhi, const uint32_t *Blo, uint32_t *any_grouped,
+                                              uint32_t *any_shifted, uint32_t *any_shared, uint32_t *any_private, int *taken)
+{
+    HCASE_L(5) HCASE_L(6) HCASE_L(7) HCASE_L(8) HCASE_L(9) HCASE_L(10) HCASE_L(11) HCASE_L(12)
+    HCASE(11, 5) HCASE(12, 5) HCASE(12, 6)
+    return 1;
+}
+
 /* the table builders, for the same test: the three planes of a row segment (out[plane * W + w]) ... */
 extern "C" void bsprobe_row_planes(const uint8_t *codes, int len, int s0, int W, int L, uint32_t *out)
 {
@@ -413,8 +448,8 @@ static int run_packed(const uint8_t *codes, const int64_t *off, const int *rows,
                     for (int delta = 0; delta < T; delta++) {
                         uint32_t any[2];
                         if constexpr (top_plane_serves(L, D)) /* (the shift-record kernel's entry: a superset per group) */
-                            window_group_any_centres<W, L, D, SHIFT_GROUP_WORDS>(Ahi, Alo, AVg, &sb[st][0][(size_t)delta],
-                                                                                 &sb[st][1][(size_t)delta], any);
+                            window_group_any_centres<W, L, D, SHIFT_GROUP_WORDS, true, true>(Ahi, Alo, AVg, &sb[st][0][(size_t)delta],
+                                                                                             &sb[st][1][(size_t)delta], any);
                         else
                             window_group_any<W, L, D, SHIFT_GROUP_WORDS>(Ahi, Alo, AV, &sb[st][0][(size_t)delta],
                                                                          &sb[st][1][(size_t)delta], any);

@@ -666,7 +666,30 @@ GKM_HD void centre_planes(const uint32_t *x, uint32_t *b, uint32_t *pq)
     }
 }
 
-template <int W, int L, int D, int GRP, bool SHARED = true>
+/*
+ * SHIFT-SHARED TREES (SHIFTED = true, what the kernel runs where shift_shared_serves): the shared form shares the words the two
+ * centre windows have in common AS WORDS.  It does not use that an extension word is a shifted copy of a match word, Z[x] =
+ * Z[x - W] >> 1: for L >= W the second centre's GRP top words Z[HALF+L .. HALF+L+GRP-1] are the words Z[HALF+L-W ..] of the first
+ * centre one bit row on, and a column sum is bitwise, so the planes of their sum are the planes of the first centre's sum shifted.
+ * With NH = L - W head words per centre, S the five words behind the first centre's heads and U the five words that end it:
+ *     c0 = Z[HALF .. HALF+NH-1]         + S        + U (+ beta)      S = Z[HALF+NH .. HALF+NH+GRP-1]  (match words, all below W)
+ *     c1 = Z[HALF+GRP .. HALF+GRP+NH-1] + (S >> 1) + U (+ beta)      U = Z[HALF+L-GRP .. HALF+L-1]
+ * L = 11: c0 = z2 + (z3 + .. + z7) + (z8 + z9 + z'0 + z'1 + z'2), c1 = z7 + (z'3 + .. + z'7) + the same; L = 10: no heads.
+ * S and U are summed once, two full adders each (planes s; k1, k2 and u; m1, m2), the three planes of S are shifted, and per centre
+ * column 0 is one full adder over {head, s or s >> 1, u} (L = 10: the half adder of s, u with the bias of one as its third input)
+ * and column 1 two full adders over {k1, k2 (shifted for c1), m1, m2, that carry}: 4 + 3 + 4 + 2 x 6 = 23 ops where the shared form
+ * takes 4 + 2 x 10, and the extension word Z[HALF+L+HALF] (Z15 at L = 11, Z14 at L = 10) has no reader left: per shift at W = 10,
+ * L = 11, 20 + 9 + 23 + 2 x (6 + 2 + 3) + 6 = 80.  Column 1 ends in two planes as before, so the fold of the top pair is unchanged.
+ * Bit row 31: s >> 1 reads five mismatches there, which is what the five shifted words Z[x - W] >> 1 read -- the same fiction, so
+ * the identity holds on every bit of arbitrary words (tests/test_shift_shared_trees.py).  Taken for L - W <= 1, the shapes whose
+ * listing was seen to get shorter; every other pair stays on the shared form.
+ */
+constexpr bool shift_shared_serves(int W, int L, int D, int GRP)
+{
+    return top_plane_serves(L, D) && W == 2 * GRP && L >= W && L - W <= 1;
+}
+
+template <int W, int L, int D, int GRP, bool SHARED = true, bool SHIFTED = false>
 GKM_HD void window_group_any_centres(const uint32_t *Ahi, const uint32_t *Alo, const uint32_t *AVg, const uint32_t *Bhi,
                                      const uint32_t *Blo, uint32_t *any)
 {
@@ -685,7 +708,8 @@ GKM_HD void window_group_any_centres(const uint32_t *Ahi, const uint32_t *Alo, c
     for (int x = W; x < NX; x++) Z[x] = Z[x - W] >> 1;
 
     /* the overlap of the two centre windows, folded once (SHARED): NS planes for each centre's column 0, NY for its column 1 */
-    constexpr bool SH = SHARED && L >= GRP;
+    constexpr bool SS = SHIFTED && shift_shared_serves(W, L, D, GRP); /* the shift-shared form; else the form SHARED names */
+    constexpr bool SH = SHARED && L >= GRP && !SS;
     constexpr int OV0 = GRP + HALF;                      /* the overlap's first word: the second centre */
     constexpr int NOV = SH ? L - GRP : 0;                /* its words Z[OV0 .. HALF+L-1] */
     constexpr int NF = NOV / 3, REST = NOV - 3 * NF;     /* full adders, words left over */
@@ -695,7 +719,22 @@ GKM_HD void window_group_any_centres(const uint32_t *Ahi, const uint32_t *Alo, c
     constexpr bool CIN0 = BETA == 1 && !BIAS_SH;         /* ... and the one, where the overlap could not take it */
     using CS0 = ColumnSumBiased<N0, CIN0>;
     constexpr int N1 = CS0::NC + NY;                     /* planes of its column 1 */
-    constexpr bool FOLD = SH && top_pair_folds(1, P, N1);
+    /* the shift-shared form: NH head words per centre, S behind the first centre's heads, U the first centre's last GRP words */
+    constexpr int NH = SS ? L - W : 0;
+    constexpr int XS = HALF + NH, XU = HALF + L - GRP;
+    using CSS = ColumnSumBiased<NH + 2, BETA == 1>;      /* a centre's column 0: its heads, s or s >> 1, u and the one */
+    constexpr int NK = ColumnSum<GRP>::NC;               /* carries of S, and of U */
+    constexpr int N1S = 2 * NK + CSS::NC;                /* planes of its column 1 */
+    constexpr bool FOLD = SS ? top_pair_folds(1, P, N1S) : SH && top_pair_folds(1, P, N1);
+    uint32_t s0[2] = {0u, 0u}, sk[2][NK], su = 0u, sm[NK];
+    if constexpr (SS) {
+        static_assert(XS + GRP <= W && XU + GRP <= NX, "S is made of match words, U lies inside both centre windows");
+        s0[0] = ColumnSum<GRP>::run(Z + XS, sk[0]);
+        s0[1] = s0[0] >> 1; /* the sum of the words one bit row on: its planes one bit row on */
+#pragma unroll
+        for (int i = 0; i < NK; i++) sk[1][i] = sk[0][i] >> 1;
+        su = ColumnSum<GRP>::run(Z + XU, sm);
+    }
     uint32_t ss[NS > 0 ? NS : 1], sy[NY > 0 ? NY : 1];
     if constexpr (SH) {
 #pragma unroll
@@ -721,7 +760,24 @@ GKM_HD void window_group_any_centres(const uint32_t *Ahi, const uint32_t *Alo, c
     for (int g = 0; g < W / GRP; g++) {
         const int C = g * GRP + HALF; /* the group's centre word: C - 2 >= 0, C + L + 1 <= NX - 1 */
         uint32_t b[P], pq[2] = {0u, 0u};
-        if constexpr (SH) {
+        if constexpr (SS) {
+            /* column 0: the centre's heads, the sum of S (group 1: one bit row on) and of U; column 1: their carries and its own */
+            const int H0 = g == 0 ? HALF : HALF + GRP;
+            uint32_t c0[NH + 2], cc[CSS::NC], c1[N1S];
+#pragma unroll
+            for (int i = 0; i < NH; i++) c0[i] = Z[H0 + i];
+            c0[NH] = s0[g];
+            c0[NH + 1] = su;
+            b[0] = CSS::run(c0, cc);
+#pragma unroll
+            for (int i = 0; i < NK; i++) {
+                c1[i] = sk[g][i];
+                c1[NK + i] = sm[i];
+            }
+#pragma unroll
+            for (int i = 0; i < CSS::NC; i++) c1[2 * NK + i] = cc[i];
+            centre_planes<1, P, N1S, FOLD>(c1, b, pq);
+        } else if constexpr (SH) {
             /* column 0: the centre's own GRP words (group 0: below the overlap, group 1: above it) and the shared sums */
             const int X0 = g == 0 ? HALF : HALF + L;
             uint32_t c0[N0], c1[N1];

@@ -44,11 +44,13 @@ constexpr int BS_CAP = BS_TRIP + 64;
                                      profiles/r15_kernel_ab_crossings.txt has both */
 #endif
 #ifndef GKM_BS_CENTRES
-#define GKM_BS_CENTRES 2 /* the shift-record variants' counting loop: 2 = no counter at all, each group from its centre window's exact
+#define GKM_BS_CENTRES 3 /* the shift-record variants' counting loop: 2 = no counter at all, each group from its centre window's exact
                             count and the two steps either side of it, the two centre trees sharing the words they have in common and
                             the top half adder folded into the threshold (gkm_bitslice.h window_group_any_centres: 82 VALU per shift at
-                            L = 11); 1 = the same with a private tree per centre (88): profiles/r18_kernel_ab_shared_trees.txt has
-                            both; 0 = the crossings loop above (106): profiles/r16_kernel_ab_centres.txt */
+                            L = 11); 3 = the same, and where L = 10 or 11 the second centre's own words taken as the first centre's sum
+                            shifted one bit row on (the shift-shared trees: 80; other L as 2): profiles/r20_kernel_ab_shift_shared.txt;
+                            1 = as 2 with a private tree per centre (88): profiles/r18_kernel_ab_shared_trees.txt has both; 0 = the
+                            crossings loop above (106): profiles/r16_kernel_ab_centres.txt */
 #endif
 #ifndef GKM_TRIP_PRIO
 #define GKM_TRIP_PRIO 3 /* wave priority (s_setprio, 0..3) inside a trip; 0 = as rounds 1-3 */
@@ -495,7 +497,7 @@ __global__ __launch_bounds__(64, D > 4 ? 1 : (PK >= 4 && PK <= 7) ? GKM_BS_WAVES
                          * allows, the top plane of a count of matches -- one op per word for threshold, validity and OR) */
                         uint32_t grp_any[W / BS_GRP];
                         if constexpr (GROUP_VALID && SHIFTREC && GKM_BS_CENTRES != 0) /* the same words as the next two entries, no counter stepped */
-                            window_group_any_centres<W, L, D, BS_GRP, GKM_BS_CENTRES == 2>(Ahi, Alo, AVg, bh + u, bl + u, grp_any);
+                            window_group_any_centres<W, L, D, BS_GRP, GKM_BS_CENTRES >= 2, GKM_BS_CENTRES == 3>(Ahi, Alo, AVg, bh + u, bl + u, grp_any);
                         else if constexpr (GROUP_VALID && SHIFTREC) /* the same words as the next entry, the top plane never stepped */
                             window_group_any_crossings<W, L, D, BS_GRP, GKM_BS_CROSSINGS_MIDDLE != 0>(Ahi, Alo, AVg, bh + u, bl + u, grp_any);
                         else if constexpr (GROUP_VALID) /* a superset per group: see AVg above */
