@@ -49,6 +49,23 @@ def test_random_svm_problems(built, monkeypatch, capsys):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("seed", [22])
+def test_random_svm_problems_varied_diagonals(built, seed, monkeypatch, capsys):
+    """the same sweep drawing from the kinds whose diagonal is not constant or which are indefinite as well (--kinds:
+    vardiag, krein, poly beside the default three): same budget, same iteration cap"""
+    spec = importlib.util.spec_from_file_location("fuzz_svm", os.path.join(ROOT, "tools", "fuzz_svm.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    monkeypatch.setenv("GKM_SVM_MAX_ITER", "300000")
+    monkeypatch.setattr(sys, "argv", ["fuzz_svm.py", "--seconds", "15", "--seed", str(seed), "--kinds", ",".join(mod.KINDS)])
+    mod.main()
+    out = capsys.readouterr().out
+    assert "svm fuzz ok" in out
+    seen = dict((k, int(v)) for k, v in re.findall(r"(\w+) (\d+)", re.search(r"kinds: (.*)", out).group(1)))
+    assert seen["vardiag"] + seen["krein"] + seen["poly"] > 0, seen
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("seed", [13, 14])
 def test_random_block_sweep(built, seed, monkeypatch, capsys):
     """tools/fuzz_block.py: the column-range launch of the scoring path (random rows, ranges, leading dimensions,

@@ -31,8 +31,10 @@ def _rbf_matrix(n, dim, seed, dup=0):
     return np.maximum(K, K.T)
 
 
-def _compare_with_sklearn(K, n_first, trains, tests, C, tol, shrinking=False, Kd=None):
-    """Kd: the device matrix handed to the solvers (default: a contiguous copy of K)"""
+def _compare_with_sklearn(K, n_first, trains, tests, C, tol, shrinking=False, Kd=None, fitted=None):
+    """Kd: the device matrix handed to the solvers (default: a contiguous copy of K); fitted: a list that receives
+    scikit-learn's SVC of every fold -- or holds them already, from an earlier call with the same problems and
+    settings, and then spares the fits.  Returns the FoldSolutions."""
     import torch
     from sklearn.svm import SVC
     from gkmqc_amd import svmcv
@@ -43,8 +45,13 @@ def _compare_with_sklearn(K, n_first, trains, tests, C, tol, shrinking=False, Kd
     sol, handles = svmcv.train_folds(Kd, trains, y, C, tol, shrinking)
     scores = svmcv.decision_values(Kd, handles, tests)
     for f, (train, test) in enumerate(zip(trains, tests)):
-        sv = SVC(kernel="precomputed", C=C, tol=tol, shrinking=shrinking, cache_size=512)
-        sv.fit(K[train][:, train], y[train])
+        if fitted is not None and len(fitted) > f:
+            sv = fitted[f]
+        else:
+            sv = SVC(kernel="precomputed", C=C, tol=tol, shrinking=shrinking, cache_size=512)
+            sv.fit(K[train][:, train], y[train])
+            if fitted is not None:
+                fitted.append(sv)
         coef, support = sol.dual_coef(f)
         # sklearn's support_ are positions in `train`
         pos_in_train = {g: p for p, g in enumerate(train)}
@@ -57,6 +64,7 @@ def _compare_with_sklearn(K, n_first, trains, tests, C, tol, shrinking=False, Kd
         want = sv.decision_function(K[test][:, train])
         assert np.array_equal(scores[f], want), "fold %d: decision values differ by %g" % (
             f, np.abs(scores[f] - want).max())
+    return sol
 
 
 def _folds(n, n_first, ncv, seed):

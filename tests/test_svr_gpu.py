@@ -40,8 +40,10 @@ def _folds(n, ncv, seed):
     return list(trains), list(tests)
 
 
-def _compare_with_sklearn(K, z, trains, tests, C, eps, tol, shrinking=False, capped=False, Kd=None):
-    """Kd: the device matrix handed to the solvers (default: a contiguous copy of K)"""
+def _compare_with_sklearn(K, z, trains, tests, C, eps, tol, shrinking=False, capped=False, Kd=None, fitted=None):
+    """Kd: the device matrix handed to the solvers (default: a contiguous copy of K); fitted: a list that receives
+    scikit-learn's SVR of every problem -- or holds them already, from an earlier call with the same problems and
+    settings, and then spares the fits"""
     import torch
     from sklearn.svm import SVR
     from gkmqc_amd import svmcv
@@ -50,8 +52,13 @@ def _compare_with_sklearn(K, z, trains, tests, C, eps, tol, shrinking=False, cap
     sol = svmcv.train_svr_folds(Kd, trains, z, C, eps, tol, shrinking)
     pred = svmcv.svr_predict(Kd, sol, tests)
     for f, (train, test) in enumerate(zip(trains, tests)):
-        m = SVR(kernel="precomputed", C=C, epsilon=eps, tol=tol, shrinking=shrinking, cache_size=512)
-        m.fit(K[train][:, train], z[train])
+        if fitted is not None and len(fitted) > f:
+            m = fitted[f]
+        else:
+            m = SVR(kernel="precomputed", C=C, epsilon=eps, tol=tol, shrinking=shrinking, cache_size=512)
+            m.fit(K[train][:, train], z[train])
+            if fitted is not None:
+                fitted.append(m)
         assert (sol.iters[f] < 0) if capped else (sol.iters[f] >= 0), sol.iters[f]   # (0: every target within epsilon)
         assert np.array_equal(sol.support[f], m.support_), "problem %d: support set differs" % f
         assert sol.dual_coef[f].tobytes() == m.dual_coef_[0].tobytes(), "problem %d: max |diff| %g" % (
