@@ -34,6 +34,9 @@
  *   gkm_panel.hip          l-mer weight panels: up to 64 interleaved tables served by one lookup per l-mer, the lanes across
  *                          models: the two tree kernels (k_panel_score, k_panel_scan_score), gkmhip_panel_score,
  *                          gkmhip_panel_scan_score, and what every panel entry checks (panel_check, panel_shift)
+ *   gkm_panel_fold.hip     a panel folded in one pass: the comparisons of k_lmer_weights made once for all models, the
+ *                          hits compacted into an LDS list and resolved with the lanes across models into an accumulator
+ *                          tile in LDS (k_panel_weights), gkmhip_panel_weights
  *   gkm_regions.hip        regions of a scan: thresholded runs of windows with peak and summit, a prefix count of flagged
  *                          words, a segmented reduction and a compaction across launches (k_regions_word_sums,
  *                          k_regions_scan_words, k_regions_word_prefix, k_regions_summaries, k_regions_scan,

@@ -195,6 +195,9 @@ def load():
         L.gkmhip_panel_delta_sat.argtypes = (vp, vp, i64, i64, i64, vp, i32, i32, vp, vp)
         L.gkmhip_panel_delta_variants.restype = i32
         L.gkmhip_panel_delta_variants.argtypes = (vp, vp, vp, i64, vp, i32, vp, i64, vp, i32, i32, vp, vp)
+    if hasattr(L, "gkmhip_panel_weights"):   # (older builds lack it; GramContext.panel_weights says so)
+        L.gkmhip_panel_weights.restype = i32
+        L.gkmhip_panel_weights.argtypes = (vp, vp, vp, vp, i32, i32, i32, ctypes.c_uint32, ctypes.c_uint32, vp, vp)
     if hasattr(L, "gkmhip_lmer_contract"):   # (older builds lack them; GramContext's contract methods say so)
         L.gkmhip_contract_max_windows.restype = i64
         L.gkmhip_contract_max_windows.argtypes = (i32, i32)
@@ -867,6 +870,23 @@ class GramContext:
         var, alt, args = self._variant_arrays(var, alt)
         self._chk(self.lib.gkmhip_panel_delta_variants(self.handle, lm_ptr, codes_ptr, int(nbases), *args, P_ptr, int(nm),
                                                        int(ms), out_ptr, stream), "gkmhip_panel_delta_variants")
+
+    def panel_weights(self, c, v_ptr, CV_ptr, nv, nm, ms, u_begin, u_end, P_ptr, stream=0):
+        """lmer_weights for every model of a panel in one pass -> P_ptr, (u_end - u_begin) rows of ms device doubles (the
+        panel's device image; columns nm.. come back +0.0): nv classes (v_ptr: device uint32 codes) with CV_ptr = nv rows
+        of ms device doubles, CV[i, m] class i's coefficient for model m; c = d + 1 host doubles (include/gkm_hip.h
+        gkmhip_panel_weights)."""
+        if not hasattr(self.lib, "gkmhip_panel_weights"):
+            raise GkmError("panel_weights: this build of the library has no gkmhip_panel_weights")
+        c = np.ascontiguousarray(c, dtype=np.float64)
+        if len(c) != self.d + 1:
+            raise GkmError("panel_weights: c needs d + 1 = %d values" % (self.d + 1))
+        if not 0 <= int(u_begin) < int(u_end) <= 4 ** self.L:
+            raise GkmError("panel_weights: the code range must satisfy 0 <= u_begin < u_end <= 4^L")
+        if int(nv) < 0:
+            raise GkmError("panel_weights: nv must not be negative")
+        self._chk(self.lib.gkmhip_panel_weights(self.handle, c.ctypes.data, v_ptr, CV_ptr, int(nv), int(nm), int(ms),
+                                                int(u_begin), int(u_end), P_ptr, stream), "gkmhip_panel_weights")
 
     # windows of position weights contracted with a table or a panel (include/gkm_hip.h; gkm_contract.hip): P_ptr = nwin x L x 4
     # device doubles

@@ -54,7 +54,14 @@ def libsvm_order(train, y):
     """Training indices in LIBSVM's internal order (sklearn's svm_group_classes: classes sorted by
     label, the samples of a class in their original order) and the size of class 0."""
     train = np.asarray(train)
-    lab = np.asarray(y)[train]
+    return _class_order(train, np.asarray(y)[train])
+
+
+def _class_order(train, lab):
+    """libsvm_order with the labels of the training samples themselves: lab[j] belongs to train[j]."""
+    train, lab = np.asarray(train), np.asarray(lab)
+    if lab.shape != train.shape:
+        raise SvmError("a problem needs one label per training sample")
     classes = np.unique(lab)
     if len(classes) != 2:
         raise SvmError("a fold needs samples of exactly two classes")
@@ -82,13 +89,29 @@ def train_folds(K, trains, y, C=1.0, tol=1e-3, shrinking=False, about_to_launch=
     matrix K) concurrently.  Returns (FoldSolutions, device handles for `decision_values`).
     `shrinking`: LIBSVM's shrinking heuristic (scikit-learn `SVC(shrinking=True)`); it and folds of more
     than 16 384 samples run on the general solver (k_smo_general), everything else on k_smo."""
+    y = np.asarray(y)
+    return train_tasks(K, trains, [y[np.asarray(t)] for t in trains], C, tol, shrinking, about_to_launch)
+
+
+def task_orders(trains, labels):
+    """What train_tasks hands the solver per problem -> [(indices in LIBSVM's order, size of class 0)]: libsvm_order for
+    labels given per training sample (labels[t][j] belongs to trains[t][j])."""
+    if len(labels) != len(trains):
+        raise SvmError("%d label vectors for %d problems" % (len(labels), len(trains)))
+    return [_class_order(t, lab) for t, lab in zip(trains, labels)]
+
+
+def train_tasks(K, trains, labels, C=1.0, tol=1e-3, shrinking=False, about_to_launch=None):
+    """train_folds with a label vector of its own per problem: labels[t][j] is the label of sample trains[t][j].  A
+    problem is its index list in LIBSVM's order and the size of class 0, so the tasks of one labelled pool (one label
+    column each, over any subset of the pool) are solved concurrently from the pool's one matrix."""
     import torch
     if not (K.is_cuda and K.dtype == torch.float64 and K.dim() == 2 and K.shape[0] == K.shape[1]
             and K.stride(1) == 1):
         raise SvmError("K must be a square fp64 CUDA tensor with unit column stride")
     L = _lib()
     dev = K.device
-    orders = [libsvm_order(t, y) for t in trains]
+    orders = task_orders(trains, labels)
     idx = [o[0] for o in orders]
     n0 = np.array([o[1] for o in orders], dtype=np.int32)
     off = np.zeros(len(idx) + 1, dtype=np.int64)

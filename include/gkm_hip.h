@@ -503,6 +503,20 @@ int gkmhip_panel_delta_variants(gkmhip_ctx *ctx, const uint32_t *lm, const uint8
                                 int nvar, const uint8_t *alt, int64_t nalt, const double *P, int nm, int ms, double *out,
                                 void *stream);
 
+/* A panel folded in one pass (gkm_panel_fold.hip): gkmhip_lmer_weights for nm models at once, written
+ * into the panel's own device image.  For every code u of [u_begin, u_end) and every model m < nm,
+ *   P[(u - u_begin) * ms + m] = sum_{i ascending} CV[i * ms + m] * (cf + cr)      (cf, cr as gkmhip_lmer_weights defines them)
+ * from 0.0 in that order: bit for bit what gkmhip_lmer_weights writes for (v, CV[:, m]), whatever nm, ms, the range, the
+ * launch or the run (no atomics; no workgroup waits for another).  The comparisons are made once for all models.
+ *   c  HOST, d + 1 doubles;
+ *   v  DEVICE, nv l-mer codes (for a panel: the ascending union of the models' canonical classes);
+ *   CV DEVICE, nv rows of ms doubles: CV[i * ms + m] is class i's coefficient for model m (0.0 where m lacks the class);
+ *   P  DEVICE, (u_end - u_begin) rows of ms doubles; columns nm..ms-1 are written as +0.0; nothing else is written.
+ * Refusals (error 2, nothing written): those of gkmhip_lmer_weights and of the panel calls above.  last_comparisons:
+ * 2 nv (u_end - u_begin), not multiplied by nm; last_kernel_ms / last_kernel_name describe k_panel_weights. */
+int gkmhip_panel_weights(gkmhip_ctx *ctx, const double *c, const uint32_t *v, const double *CV, int nv, int nm, int ms,
+                         uint32_t u_begin, uint32_t u_end, double *P, void *stream);
+
 /* ---- a weight table or panel contracted with position weight windows (gkm_contract.hip) ----
  * A window is L rows of four doubles, P[i][b]: l-mer position i (0 the first base, the highest bit pair of a code), base b
  * (A, C, G, T).  Its value a(P) = sum over all 4^L codes u of W(u) prod_i P[i][u_i] is evaluated in one fixed order, the
