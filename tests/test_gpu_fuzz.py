@@ -92,3 +92,28 @@ def test_random_interpretation_sweep(built, seed, monkeypatch, capsys):
     monkeypatch.setattr(sys, "argv", ["fuzz_interpret.py", "--seconds", "12", "--seed", str(seed)])
     mod.main()                                   # raises SystemExit with the failing case on a mismatch
     assert "interpret fuzz ok" in capsys.readouterr().out
+
+
+# tools/fuzz_windows.py.  The seed was picked on the CPU (--dry: the draw without the device) as the first of 1..4000 whose
+# first 40 cases hold a case of each of the five kinds asserted below (the 35th takes 68 732 bytes of LDS: L = 12, d = 12,
+# W = 75, strides 1 and 63), so every longer run of it does too.  The count is set for the 12 to 15 s of the sibling sweeps:
+# 120 cases took 12.5 s on the MI355X box, run after the other window tests (130 cases took 15.9 s as the first test of a
+# process, HIP start-up included, and 170 cases 17.3 s; the oracle's share is 3.5e9 l-mer comparisons of the 120 cases).
+WINDOW_SEED, WINDOW_CASES = 549, 120
+
+
+@pytest.mark.gpu
+def test_random_window_sweep(built, monkeypatch, capsys):
+    """tools/fuzz_windows.py: the scan's words and self profiles, k_wsim_profiles' profiles and G (exact against the oracle),
+    window_kernel against cross_kernel byte for byte and window_best, over the whole legal (L, k, d, W, stride) region.  A
+    fixed count of cases, so that the same cases run on every box."""
+    spec = importlib.util.spec_from_file_location("fuzz_windows", os.path.join(ROOT, "tools", "fuzz_windows.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    monkeypatch.setattr(sys, "argv", ["fuzz_windows.py", "--cases", str(WINDOW_CASES), "--seed", str(WINDOW_SEED)])
+    mod.main()                                   # raises SystemExit with the failing case on a mismatch
+    out = capsys.readouterr().out
+    assert "window fuzz ok: %d cases" % WINDOW_CASES in out
+    seen = re.search(r"(\d+) with d >= 9, (\d+) with more than 64 KiB of LDS, (\d+) with a stretch-limited tile of k_wsim_profiles, "
+                     r"(\d+) with a stretch-limited group of k_scan_profiles, (\d+) with L <= 3", out)
+    assert seen and all(int(v) > 0 for v in seen.groups()), out

@@ -127,7 +127,8 @@ def _check_exact(dv, L, d, v, cv, ranges):
     return total
 
 
-@pytest.mark.parametrize("L,d", [(2, 1), (5, 0), (5, 2), (8, 3), (8, 8), (10, 3), (12, 4), (12, 12)])
+@pytest.mark.parametrize("L,d", [(2, 1), (5, 0), (5, 2), (8, 3), (8, 8), (10, 3), (12, 4), (12, 12),
+                                 (3, 1), (4, 2), (6, 3), (7, 3), (9, 4), (11, 3)])         # (every L of k_lmer_importance<L>)
 def test_exact_enumeration(dv, L, d):
     """share = e_m and integer cv: every V[u][i] is an exact integer count, bit for bit the numpy count (both strands; a
     palindrome credits its own row twice).  d = L is the dense case: every lane hits every class on both strands."""

@@ -12,6 +12,7 @@ import pytest
 from tests import dense_inputs as DI
 from tests import helpers
 from tests import scan_ref as SR
+from tests.window_launch import scan_profiles as _device_profiles
 
 pytestmark = pytest.mark.gpu
 
@@ -53,30 +54,6 @@ def tables(gp, tmp_path_factory, dv):
          for i, s in enumerate(seqs)]
     out["svr4"] = gp.lmer_weights(gp.train_svr(fa, z, kernel_type=4, L=10, k=6, d=3))
     return out
-
-
-def _device_profiles(dv, t, L, k, d, x, W, s, valid=None):
-    """gkmhip_scan_lmers + gkmhip_scan_profiles over every window of x -> ((windows, d + 1) int64, comparisons)"""
-    import torch
-    ctx = dv.GramContext(t, L, k, d, device=0)
-    try:
-        stream = torch.cuda.current_stream().cuda_stream
-        valid = np.ones(len(x), dtype=np.uint8) if valid is None else np.asarray(valid, dtype=np.uint8)
-        d_x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.uint8)).cuda()
-        d_v = torch.from_numpy(valid).cuda()
-        nlm = len(x) - L + 1
-        lm = torch.full((nlm + 64,), -1, dtype=torch.int32, device="cuda")          # (a guard band: nothing lands there)
-        ctx.scan_lmers(d_x.data_ptr(), d_v.data_ptr(), len(x), lm.data_ptr(), stream)
-        nwin = len(SR.starts(len(x), W, s))
-        wt = torch.from_numpy(dv.position_weights(t, W - L + 1)).cuda()
-        prof = torch.full((nwin + 1, d + 1), -7, dtype=torch.int64, device="cuda")
-        ctx.scan_profiles(lm.data_ptr(), nlm, wt.data_ptr(), W, s, nwin, prof.data_ptr(), stream)
-        torch.cuda.synchronize()
-        assert ctx.last_kernel_name() == "k_scan_profiles"
-        assert (lm[nlm:] == -1).all() and (prof[nwin] == -7).all()
-        return prof[:nwin].cpu().numpy(), ctx.last_comparisons(), lm[:nlm].cpu().numpy().view(np.uint32)
-    finally:
-        ctx.close()
 
 
 _ORACLE = {}

@@ -13,6 +13,10 @@ import pytest
 from tests import dense_inputs as DI
 from tests import helpers
 from tests import wsim_ref as WR
+from tests.window_launch import cross as _cross
+from tests.window_launch import record as _record
+from tests.window_launch import tile_count as _tile_count
+from tests.window_launch import wsim_profiles as _device_profiles
 
 pytestmark = pytest.mark.gpu
 
@@ -30,42 +34,6 @@ def dv(built):
 def gw(built):
     from gkmqc_amd import gkmwindows
     return gkmwindows
-
-
-def _words(ctx, x, guard=64):
-    """gkmhip_scan_lmers of a code array (values >= 4 invalid) -> (int32 device tensor with a guard band, nlm)"""
-    import torch
-    x = np.asarray(x, dtype=np.uint8)
-    valid = (x < 4).astype(np.uint8)
-    d_x = torch.from_numpy(np.where(x < 4, x, 0).astype(np.uint8)).cuda()
-    d_v = torch.from_numpy(valid).cuda()
-    nlm = len(x) - ctx.L + 1
-    lm = torch.full((nlm + guard,), -1, dtype=torch.int32, device="cuda")
-    ctx.scan_lmers(d_x.data_ptr(), d_v.data_ptr(), len(x), lm.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    return lm, nlm
-
-
-def _device_profiles(ctx, x, y, W, sx, sy):
-    """gkmhip_wsim_profiles over every window pair -> ((nA, nB, d + 1) int64 profiles, G, comparisons)"""
-    import torch
-    stream = torch.cuda.current_stream().cuda_stream
-    lmx, nlmx = _words(ctx, x)
-    lmy, nlmy = _words(ctx, y)
-    nA, nB = len(SR.starts(len(x), W, sx)), len(SR.starts(len(y), W, sy))
-    G = torch.full((nA + 1, nB), -7.0, dtype=torch.float64, device="cuda")
-    P = torch.full((nA + 1, nB, ctx.d + 1), -7, dtype=torch.int32, device="cuda")
-    ctx.wsim_profiles(lmx.data_ptr(), nlmx, lmy.data_ptr(), nlmy, W, sx, sy, nA, nB, G.data_ptr(), nB, P.data_ptr(), stream)
-    torch.cuda.synchronize()
-    assert ctx.last_kernel_name() == "k_wsim_profiles"
-    assert (G[nA] == -7.0).all() and (P[nA] == -7).all() and (lmx[nlmx:] == -1).all() and (lmy[nlmy:] == -1).all()
-    return P[:nA].cpu().numpy().astype(np.int64), G[:nA].cpu().numpy(), ctx.last_comparisons()
-
-
-def _record(x, W, s, windows, cap=1500):
-    """the first bases of x that hold `windows` windows (fewer where `cap` bases hold fewer)"""
-    T = min(cap, W + (windows - 1) * s)
-    assert T >= W
-    return x[:T]
 
 
 @pytest.mark.parametrize("t", [0, 1, 2])
@@ -119,18 +87,6 @@ def test_tile_edges(dv, sx, sy):
                 assert comparisons == 2 * _tile_count(W - L + 1, sx, gx, nx) * _tile_count(W - L + 1, sy, gy, ny)
     finally:
         ctx.close()
-
-
-def _tile_count(n, s, g, nw):
-    """sum over the tiles of an axis of their l-mer words n + (windows - 1) s"""
-    return sum(n + (min(g, nw - w0) - 1) * s for w0 in range(0, nw, g))
-
-
-def _cross(dv, x, y, W, sx, sy, t, L, k, d, gamma):
-    """device.cross_kernel on the windows of x and y cut out -> the (nA, nB) block of windows of x against windows of y"""
-    wx, wy = [w for _, w in SR.windows(x, W, sx)], [w for _, w in SR.windows(y, W, sy)]
-    r = dv.cross_kernel(wx + wy, list(range(len(wx))), t, L, k, d, gamma=gamma)
-    return r["K"][:, len(wx):].cpu().numpy()
 
 
 @pytest.mark.parametrize("t", [0, 1, 2, 3])
