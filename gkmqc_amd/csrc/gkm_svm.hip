@@ -19,6 +19,9 @@
  * epsilon-SVR (gkmsvm_train_svr_batch*) runs the same kernels on LIBSVM's 2l-variable problem with a
  * per-position linear term (template flag LIN; the C-SVC instantiations are unchanged), and predicts with
  * k_decision<true>, the signed sum.
+ * A box per problem and per class (gkmsvm_train_batch*_boxed, DESIGN.md §5u: class weights, a C per problem) is the template
+ * flag BOX of both kernels: wherever LIBSVM reads get_C(i) the boxed builds pick c0 or c1 of the problem's descriptor by the
+ * position's class; the unboxed instantiations keep the one kernel argument C and compile to the code they always were.
  */
 #include <hip/hip_runtime.h>
 
@@ -134,6 +137,14 @@ struct SvmProb {
 struct SvmProbLin : SvmProb {
     const double *lin;
 };
+/* A box per problem and per class (template flag BOX of k_smo / k_smo_general; gkmsvm_train_batch*_boxed):
+ * LIBSVM's get_C(i) = y_i > 0 ? Cp : Cn is c0 for the class-0 positions (k < n0, y = +1) and c1 for the rest.  The
+ * unboxed instantiations never see these fields and keep the one kernel argument C. */
+struct SvmProbBox : SvmProb {
+    double c0, c1;
+};
+template <bool LIN, bool BOX>
+using SvmProbOf = std::conditional_t<BOX, SvmProbBox, std::conditional_t<LIN, SvmProbLin, SvmProb>>;
 
 /* A candidate of the working-set selection together with everything the other threads need to
  * know about it, so that one LDS record per wave (and one barrier) publishes the winner. */
@@ -264,11 +275,12 @@ __global__ void k_diag(const double *__restrict__ K, int64_t ld, int n, double *
  * its payload in LDS, every thread then picks the block winner from the T/64 records and does
  * the (scalar) two-variable update redundantly, so no third exchange is needed.
  */
-template <int T, int SVM_R, int TABM, bool LIN>
+template <int T, int SVM_R, int TABM, bool LIN, bool BOX = false>
 __global__ __launch_bounds__(T) void k_smo(const double *__restrict__ K, int64_t ld, const double *__restrict__ diag,
-                                           const std::conditional_t<LIN, SvmProbLin, SvmProb> *probs, double C,
+                                           const SvmProbOf<LIN, BOX> *probs, double C,
                                            double eps, int max_iter)
 {
+    static_assert(!(LIN && BOX), "epsilon-SVR keeps one C");
     constexpr int NW = T / 64;
     __shared__ Cand candA[NW], candB[NW];
     __shared__ double g2s[NW];
@@ -276,6 +288,11 @@ __global__ __launch_bounds__(T) void k_smo(const double *__restrict__ K, int64_t
     const auto p = probs[blockIdx.x];
     const auto *const idx_g = as_global(p.idx);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l = p.l, n0 = p.n0;
+    /* the upper bound of position k: its class's with BOX (the position test is all that picks it), else C */
+    auto CK = [&](bool pos) {
+        if constexpr (BOX) return pos ? p.c0 : p.c1;
+        else return C;
+    };
 
     /* TAB: the samples' matrix indices and kernel diagonal live in (dynamic) LDS instead of
      * registers -- 48 VGPRs less at 16 samples per thread, which is what keeps alpha and G from
@@ -346,7 +363,7 @@ __global__ __launch_bounds__(T) void k_smo(const double *__restrict__ K, int64_t
             const int k = tid + r * T;
             const bool pos = k < n0; /* y = +1 */
             const double a_r = AL(r);
-            const bool below_C = a_r < C, above_0 = a_r > 0.0; /* (bitwise: no branches) */
+            const bool below_C = a_r < CK(pos), above_0 = a_r > 0.0; /* (bitwise: no branches) */
             const bool in_up = (k < l) & ((pos & below_C) | (!pos & above_0));
             const bool take = in_up & (G[r] <= ns);
             ns = take ? G[r] : ns;
@@ -399,7 +416,7 @@ __global__ __launch_bounds__(T) void k_smo(const double *__restrict__ K, int64_t
                 const int k = tid + r * T;
                 const bool pos = k < n0;
                 kfi[KEEP ? r : 0] = (float)kik[r];
-                const bool below_C = al[ALS ? 0 : r] < C, above_0 = al[ALS ? 0 : r] > 0.0;
+                const bool below_C = al[ALS ? 0 : r] < CK(pos), above_0 = al[ALS ? 0 : r] > 0.0;
                 const bool in_low = (k < l) & ((pos & above_0) | (!pos & below_C));
                 const double gs = G[r]; /* y_k G_k */
                 g2max = (in_low & (gs > g2max)) ? gs : g2max;
@@ -429,7 +446,7 @@ __global__ __launch_bounds__(T) void k_smo(const double *__restrict__ K, int64_t
             const float kf = (float)kik[r - r0];
             if (KEEP) kfi[KEEP ? r : 0] = kf;
             const double a_r = AL(r);
-            const bool below_C = a_r < C, above_0 = a_r > 0.0;
+            const bool below_C = a_r < CK(pos), above_0 = a_r > 0.0;
             const bool in_low = (k < l) & ((pos & above_0) | (!pos & below_C));
             const double gs = G[r]; /* y_k G_k */
             g2max = (in_low & (gs > g2max)) ? gs : g2max;
@@ -475,7 +492,38 @@ __global__ __launch_bounds__(T) void k_smo(const double *__restrict__ K, int64_t
         const double Qij = cj.q, QDj = QDG ? diag[cj.g] : TAB ? qd_s[j] : cj.qd;
         double ai = ci.alpha, aj = cj.alpha;
         const double old_i = ai, old_j = aj;
-        {
+        if constexpr (BOX) {
+            /* The same selects with LIBSVM's C_i and C_j.  y_i != y_j: the first clipping tests diff > 0, the second
+             * diff > C_i - C_j, and clips to C_i / C_j.  y_i == y_j: one class, C_i == C_j, and LIBSVM's sum > C_i
+             * (first) and sum > C_j (second) are one condition. */
+            const double Ci = CK(i < n0), Cj = CK(j < n0);
+            const bool opp = yi != yj;
+            const double q2 = 2 * Qij;
+            double quad = (QDi + QDj) + (opp ? q2 : -q2);
+            quad = quad <= 0 ? SVM_TAU : quad;
+            const double delta = ((opp ? -ci.G : ci.G) - cj.G) / quad;
+            const double diff = ai - aj, sum = ai + aj;
+            ai += opp ? delta : -delta;
+            aj += delta;
+            const bool c1 = opp ? diff > 0 : sum > Ci;
+            const bool c2 = opp ? diff > Ci - Cj : sum > Cj;
+            /* first clipping */
+            {
+                const bool hit = opp ? (c1 ? aj < 0 : ai < 0) : (c1 ? ai > Ci : aj < 0);
+                const double ni = opp ? (c1 ? diff : 0.0) : (c1 ? Ci : sum);
+                const double nj = opp ? (c1 ? 0.0 : -diff) : (c1 ? sum - Ci : 0.0);
+                ai = hit ? ni : ai;
+                aj = hit ? nj : aj;
+            }
+            /* second clipping */
+            {
+                const bool hit = opp ? (c2 ? ai > Ci : aj > Cj) : (c2 ? aj > Cj : ai < 0);
+                const double ni = opp ? (c2 ? Ci : Cj + diff) : (c2 ? sum - Cj : 0.0);
+                const double nj = opp ? (c2 ? Ci - diff : Cj) : (c2 ? Cj : sum);
+                ai = hit ? ni : ai;
+                aj = hit ? nj : aj;
+            }
+        } else {
             /* LIBSVM's two branches (y_i != y_j / y_i == y_j) differ in signs and in which bound is
              * tested first; written with selects (negation is exact, a - b == a + (-b)), so the wave
              * executes ~60 instructions instead of both branchy variants with their register copies */
@@ -569,7 +617,7 @@ __global__ __launch_bounds__(T) void k_smo(const double *__restrict__ K, int64_t
         double yG = G[r]; /* S = y G */
         bool is_free = false;
         if (k < l) {
-            if (AL(r) >= C) {
+            if (AL(r) >= CK(k < n0)) {
                 if (y < 0) ub = fmin(ub, yG); else lb = fmax(lb, yG);
             } else if (AL(r) <= 0) {
                 if (y > 0) ub = fmin(ub, yG); else lb = fmax(lb, yG);
@@ -637,6 +685,12 @@ struct GenProb {
 struct GenProbLin : GenProb {
     const double *lin; /* epsilon-SVR's p, by ORIGINAL position: p at position k is lin[aset[k]] (LIBSVM swaps p) */
 };
+struct GenProbBox : GenProb {
+    double c0, c1; /* as SvmProbBox: the bound of y = +1 (class 0) and of y = -1.  The label travels with a position
+                    * through swap_index, so get_C(k) is read off ys[k] */
+};
+template <bool LIN, bool BOX>
+using GenProbOf = std::conditional_t<BOX, GenProbBox, std::conditional_t<LIN, GenProbLin, GenProb>>;
 
 /* threads per fold: template parameter GEN_T of k_smo_general -- 1024, or 512 for folds of at most 8 192 samples */
 constexpr int GEN_U = 8; /* positions of a thread whose loads are in flight together */
@@ -714,12 +768,13 @@ __device__ __forceinline__ void block_select_min_and_max(double &v, int &k, doub
     mx = row_max(mslots[lane & (GEN_NW - 1)]);
 }
 
-template <int GEN_T, bool LDS_STATE, bool LIN>
+template <int GEN_T, bool LDS_STATE, bool LIN, bool BOX = false>
 __global__ __launch_bounds__(GEN_T) void k_smo_general(const double *__restrict__ K, int64_t ld,
                                                        const double *__restrict__ diag,
-                                                       const std::conditional_t<LIN, GenProbLin, GenProb> *probs,
+                                                       const GenProbOf<LIN, BOX> *probs,
                                                        double C, double eps, int max_iter, int shrinking, int cap)
 {
+    static_assert(!(LIN && BOX), "epsilon-SVR keeps one C");
     constexpr int GEN_NW = GEN_T / 64;
     constexpr int GEN_U = LDS_STATE ? GEN_U_LDS : GEN_T == 1024 ? GEN_U_1024 : ::GEN_U;
     __shared__ GenSel sel_s[GEN_NW], selb_s[GEN_NW]; /* first / second selection: one array each (see block_select) */
@@ -740,9 +795,14 @@ __global__ __launch_bounds__(GEN_T) void k_smo_general(const double *__restrict_
     auto *const Qi = pick<LDS_STATE>((float *)(flag_s + (size_t)10 * cap), as_global(p.Qi));
     auto *const Qj = as_global(p.Qj);
 
-    auto is_upper = [&](double a) { return a >= C; };
+    /* LIBSVM's get_C: the bound of a position with label y (BOX: its class's; else the one C, y unused) */
+    auto get_C = [&](int y) {
+        if constexpr (BOX) return y > 0 ? p.c0 : p.c1;
+        else return C;
+    };
+    auto is_upper = [&](double a, int y) { return a >= get_C(y); };
     auto is_lower = [&](double a) { return a <= 0.0; };
-    auto encode = [&](double a, int y) -> unsigned { return (a <= 0.0 ? ST_LO : 0u) | (a >= C ? ST_UP : 0u) | (y > 0 ? ST_POS : 0u); };
+    auto encode = [&](double a, int y) -> unsigned { return (a <= 0.0 ? ST_LO : 0u) | (a >= get_C(y) ? ST_UP : 0u) | (y > 0 ? ST_POS : 0u); };
     /* what the scans need of position k: is_lower_bound, is_upper_bound, the label */
     auto st_load = [&](int k) -> unsigned {
         if constexpr (LDS_STATE) return st_s[k];
@@ -805,7 +865,7 @@ __global__ __launch_bounds__(GEN_T) void k_smo_general(const double *__restrict_
             const int k = k0 + tid;
             const double a = k < active ? alpha[k] : 0.0;
             __syncthreads();
-            chunk[tid] = (k < active && !is_upper(a) && !is_lower(a)) ? a : -1.0;
+            chunk[tid] = (k < active && !is_upper(a, BOX && k < active ? ys[k] : 1) && !is_lower(a)) ? a : -1.0;
             chunk_g[tid] = k < active ? gidx[k] : 0;
             chunk_y[tid] = k < active ? ys[k] : 0;
             __syncthreads();
@@ -950,10 +1010,10 @@ __global__ __launch_bounds__(GEN_T) void k_smo_general(const double *__restrict_
         for (int k = tid; k < active; k += GEN_T) {
             const double a = alpha[k], g = G[k];
             if (ys[k] == +1) {
-                if (!is_upper(a) && -g >= g1) g1 = -g;
+                if (!is_upper(a, +1) && -g >= g1) g1 = -g;
                 if (!is_lower(a) && g >= g2) g2 = g;
             } else {
-                if (!is_upper(a) && -g >= g2) g2 = -g;
+                if (!is_upper(a, -1) && -g >= g2) g2 = -g;
                 if (!is_lower(a) && g >= g1) g1 = g;
             }
         }
@@ -967,7 +1027,7 @@ __global__ __launch_bounds__(GEN_T) void k_smo_general(const double *__restrict_
         for (int k = tid; k < active; k += GEN_T) {
             const double a = alpha[k], g = G[k];
             bool sh = false;
-            if (is_upper(a)) sh = ys[k] == +1 ? -g > Gmax1 : -g > Gmax2;
+            if (is_upper(a, BOX ? ys[k] : 1)) sh = ys[k] == +1 ? -g > Gmax1 : -g > Gmax2;
             else if (is_lower(a)) sh = ys[k] == +1 ? g > Gmax2 : g > Gmax1;
             flag_s[k] = sh ? 1 : 0;
         }
@@ -1061,10 +1121,36 @@ __global__ __launch_bounds__(GEN_T) void k_smo_general(const double *__restrict_
             } else {
                 if (ai < 0) { ai = 0; aj = -diff; }
             }
+            if constexpr (BOX) {
+                const double C_i = get_C(yi), C_j = get_C(yj);
+                if (diff > C_i - C_j) {
+                    if (ai > C_i) { ai = C_i; aj = C_i - diff; }
+                } else {
+                    if (aj > C_j) { aj = C_j; ai = C_j + diff; }
+                }
+            } else
             if (diff > C - C) {
                 if (ai > C) { ai = C; aj = C - diff; }
             } else {
                 if (aj > C) { aj = C; ai = C + diff; }
+            }
+        } else if constexpr (BOX) { /* one class: C_i == C_j, LIBSVM's sum > C_i and sum > C_j are one test */
+            const double C_i = get_C(yi), C_j = get_C(yj);
+            double quad_coef = QD_i + QD_j - 2 * Qij;
+            if (quad_coef <= 0) quad_coef = SVM_TAU;
+            const double delta = (G[i] - G[j]) / quad_coef;
+            const double sum = ai + aj;
+            ai -= delta;
+            aj += delta;
+            if (sum > C_i) {
+                if (ai > C_i) { ai = C_i; aj = sum - C_i; }
+            } else {
+                if (aj < 0) { aj = 0; ai = sum; }
+            }
+            if (sum > C_j) {
+                if (aj > C_j) { aj = C_j; ai = sum - C_j; }
+            } else {
+                if (ai < 0) { ai = 0; aj = sum; }
             }
         } else {
             double quad_coef = QD_i + QD_j - 2 * Qij;
@@ -1133,18 +1219,19 @@ __global__ __launch_bounds__(GEN_T) void k_smo_general(const double *__restrict_
         }
         GPROF(5)
         if (shrinking) { /* G_bar only matters to reconstruct_gradient */
-            const bool ui = is_upper(old_ai), uj = is_upper(old_aj);
-            if (ui != is_upper(ai)) {
+            const bool ui = is_upper(old_ai, yi), uj = is_upper(old_aj, yj);
+            const double C_i = get_C(yi), C_j = get_C(yj);
+            if (ui != is_upper(ai, yi)) {
                 __syncthreads();
                 /* Q_i of the active positions is in Qi since the second scan: only the shrunk ones are gathered (from
                  * a multiple of GEN_T on, so that position k stays with thread k mod GEN_T and no barrier is needed) */
                 q_row(i, Qi, active / GEN_T * GEN_T, l);
-                for (int k = tid; k < l; k += GEN_T) Gbar[k] = ui ? Gbar[k] - C * (double)Qi[k] : Gbar[k] + C * (double)Qi[k];
+                for (int k = tid; k < l; k += GEN_T) Gbar[k] = ui ? Gbar[k] - C_i * (double)Qi[k] : Gbar[k] + C_i * (double)Qi[k];
             }
-            if (uj != is_upper(aj)) {
+            if (uj != is_upper(aj, yj)) {
                 __syncthreads();
                 q_row(j, Qj, 0, l);
-                for (int k = tid; k < l; k += GEN_T) Gbar[k] = uj ? Gbar[k] - C * (double)Qj[k] : Gbar[k] + C * (double)Qj[k];
+                for (int k = tid; k < l; k += GEN_T) Gbar[k] = uj ? Gbar[k] - C_j * (double)Qj[k] : Gbar[k] + C_j * (double)Qj[k];
             }
         }
         /* Without shrinking no barrier is needed here: every scan and the gradient update deal position k to thread k mod GEN_T,
@@ -1172,7 +1259,7 @@ __global__ __launch_bounds__(GEN_T) void k_smo_general(const double *__restrict_
         if (k < l) {
             const double a = alpha[k];
             yG = (double)ys[k] * G[k];
-            if (is_upper(a)) {
+            if (is_upper(a, BOX ? ys[k] : 1)) {
                 if (ys[k] == -1) ub = fmin(ub, yG); else lb = fmax(lb, yG);
             } else if (is_lower(a)) {
                 if (ys[k] == +1) ub = fmin(ub, yG); else lb = fmax(lb, yG);
@@ -1252,17 +1339,31 @@ __global__ void k_decision(const double *__restrict__ K, int64_t ld, const DecPr
     p.dec[t] = sum - *p.rho;
 }
 
-/* k_smo for C-SVC (LIN = false, lin unused) or on an epsilon-SVR problem already laid out as LIBSVM's 2l positions */
-template <bool LIN>
-static int train_batch(const char *name, int device, const double *K, int64_t ld, int n, int nprob, const int *idx,
-                       const int64_t *off, const int *n0, const double *lin, double C, double eps, double *alpha,
-                       double *grad, double *rho, int *iters, void *stream_)
+/* the boxed entries' bounds (HOST, nprob x 2): every one finite and > 0, or nothing is launched */
+static bool box_ok(const char *name, const double *box, int nprob)
 {
-    using Prob = std::conditional_t<LIN, SvmProbLin, SvmProb>;
-    if (!K || n <= 0 || ld < n || nprob <= 0 || !idx || !off || !n0 || !alpha || !grad || !rho || !iters || (LIN && !lin)) {
+    for (int64_t t = 0; t < 2 * (int64_t)nprob; t++)
+        if (!(box[t] > 0.0) || !(box[t] <= DBL_MAX)) {
+            g_svm_err = std::string(name) + ": a bound is not finite or not > 0";
+            return false;
+        }
+    return true;
+}
+
+/* k_smo for C-SVC (LIN = false, lin unused) or on an epsilon-SVR problem already laid out as LIBSVM's 2l positions;
+ * BOX: C-SVC with the bounds box[2p], box[2p + 1] of problem p (C unused) */
+template <bool LIN, bool BOX = false>
+static int train_batch(const char *name, int device, const double *K, int64_t ld, int n, int nprob, const int *idx,
+                       const int64_t *off, const int *n0, const double *lin, const double *box, double C, double eps,
+                       double *alpha, double *grad, double *rho, int *iters, void *stream_)
+{
+    using Prob = SvmProbOf<LIN, BOX>;
+    if (!K || n <= 0 || ld < n || nprob <= 0 || !idx || !off || !n0 || !alpha || !grad || !rho || !iters || (LIN && !lin) ||
+        (BOX && !box)) {
         g_svm_err = std::string(name) + ": bad arguments";
         return 2;
     }
+    if constexpr (BOX) if (!box_ok(name, box, nprob)) return 2;
     hipStream_t stream = (hipStream_t)stream_;
     SVMCHK(hipSetDevice(device));
     std::vector<Prob> h((size_t)nprob);
@@ -1277,6 +1378,7 @@ static int train_batch(const char *name, int device, const double *K, int64_t ld
         SvmProb &b = h[(size_t)p];
         b = {idx + off[p], (int)l, n0[p], alpha + off[p], grad + off[p], rho + p, iters + p};
         if constexpr (LIN) h[(size_t)p].lin = lin + off[p];
+        if constexpr (BOX) { h[(size_t)p].c0 = box[2 * p]; h[(size_t)p].c1 = box[2 * p + 1]; }
     }
     const size_t probs_bytes = align256(sizeof(Prob) * (size_t)nprob);
     SvmScratch *const scr = scratch_acquire(device, probs_bytes + sizeof(double) * (size_t)n);
@@ -1315,13 +1417,13 @@ static int train_batch(const char *name, int device, const double *K, int64_t ld
 #define SMO_LAUNCH(TT, RR, TB)                                                                                  \
     if (T == TT && R == RR) {                                                                                   \
         const size_t dyn = TB == 1 ? (size_t)TT * RR * 12 : TB == 2 ? (size_t)TT * RR * 8 : 0;                  \
-        if (dyn > 0 && hipFuncSetAttribute((const void *)k_smo<TT, RR, TB, LIN>,                               \
+        if (dyn > 0 && hipFuncSetAttribute((const void *)k_smo<TT, RR, TB, LIN, BOX>,                            \
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) { \
             (void)hipGetLastError();                                                                            \
             g_svm_err = "k_smo: the device refuses this launch shape (dynamic LDS)";                            \
             return GKMSVM_RC_SHAPE_REFUSED;                                                                     \
         }                                                                                                       \
-        hipLaunchKernelGGL((k_smo<TT, RR, TB, LIN>), dim3((unsigned)nprob), dim3(TT), dyn, stream, K, ld, diag,  \
+        hipLaunchKernelGGL((k_smo<TT, RR, TB, LIN, BOX>), dim3((unsigned)nprob), dim3(TT), dyn, stream, K, ld, diag, \
                            dprobs, C, eps, max_iter);                                                           \
     } else
     SMO_LAUNCH(256, 4, 1)
@@ -1349,22 +1451,33 @@ extern "C" int gkmsvm_train_batch(int device, const double *K, int64_t ld, int n
                                   const int64_t *off, const int *n0, double C, double eps, double *alpha, double *grad,
                                   double *rho, int *iters, void *stream_)
 {
-    return train_batch<false>("gkmsvm_train_batch", device, K, ld, n, nprob, idx, off, n0, nullptr, C, eps, alpha, grad,
-                              rho, iters, stream_);
+    return train_batch<false>("gkmsvm_train_batch", device, K, ld, n, nprob, idx, off, n0, nullptr, nullptr, C, eps, alpha,
+                              grad, rho, iters, stream_);
+}
+
+extern "C" int gkmsvm_train_batch_boxed(int device, const double *K, int64_t ld, int n, int nprob, const int *idx,
+                                        const int64_t *off, const int *n0, const double *box, double eps, double *alpha,
+                                        double *grad, double *rho, int *iters, void *stream_)
+{
+    return train_batch<false, true>("gkmsvm_train_batch_boxed", device, K, ld, n, nprob, idx, off, n0, nullptr, box, 0.0,
+                                    eps, alpha, grad, rho, iters, stream_);
 }
 
 constexpr int GEN_MAX_L = 60000; /* one byte of LDS per sample for the shrinking flags */
 
-template <bool LIN>
+template <bool LIN, bool BOX = false>
 static int train_batch_general(const char *name, int device, const double *K, int64_t ld, int n, int nprob,
-                               const int *idx, const int64_t *off, const int *n0, const double *lin, double C, double eps,
-                               int shrinking, double *alpha, double *grad, double *rho, int *iters, void *stream_)
+                               const int *idx, const int64_t *off, const int *n0, const double *lin, const double *box,
+                               double C, double eps, int shrinking, double *alpha, double *grad, double *rho, int *iters,
+                               void *stream_)
 {
-    using Prob = std::conditional_t<LIN, GenProbLin, GenProb>;
-    if (!K || n <= 0 || ld < n || nprob <= 0 || !idx || !off || !n0 || !alpha || !grad || !rho || !iters || (LIN && !lin)) {
+    using Prob = GenProbOf<LIN, BOX>;
+    if (!K || n <= 0 || ld < n || nprob <= 0 || !idx || !off || !n0 || !alpha || !grad || !rho || !iters || (LIN && !lin) ||
+        (BOX && !box)) {
         g_svm_err = std::string(name) + ": bad arguments";
         return 2;
     }
+    if constexpr (BOX) if (!box_ok(name, box, nprob)) return 2;
     hipStream_t stream = (hipStream_t)stream_;
     SVMCHK(hipSetDevice(device));
     const int64_t total = off[nprob];
@@ -1400,6 +1513,7 @@ static int train_batch_general(const char *name, int device, const double *K, in
         g.fg = i0 + 4 * total + o; g.fy = i0 + 5 * total + o;
         g.Qi = f0 + o; g.Qj = f0 + total + o;
         if constexpr (LIN) h[(size_t)p].lin = lin + o;
+        if constexpr (BOX) { h[(size_t)p].c0 = box[2 * p]; h[(size_t)p].c1 = box[2 * p + 1]; }
     }
     Prob *const dprobs = (Prob *)(scratch + state_bytes);
     double *const diag = (double *)(scratch + state_bytes + probs_bytes);
@@ -1418,25 +1532,25 @@ static int train_batch_general(const char *name, int device, const double *K, in
         bool lds_state = gt == 512 && maxl <= GEN_LDS_L;
         if (const char *g = getenv("GKM_SVM_GEN_LDS")) lds_state = lds_state && atoi(g) != 0;
         size_t dyn = lds_state ? (size_t)18 * cap : (size_t)cap;
-        const void *fn = lds_state ? (const void *)k_smo_general<512, true, LIN>
-                         : gt == 512 ? (const void *)k_smo_general<512, false, LIN> : (const void *)k_smo_general<1024, false, LIN>;
+        const void *fn = lds_state ? (const void *)k_smo_general<512, true, LIN, BOX>
+                         : gt == 512 ? (const void *)k_smo_general<512, false, LIN, BOX> : (const void *)k_smo_general<1024, false, LIN, BOX>;
         e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
         if (e != hipSuccess && lds_state) { /* a device that refuses 147 KB of LDS: the state stays in global memory */
             (void)hipGetLastError();
             lds_state = false;
             dyn = (size_t)cap;
-            fn = (const void *)k_smo_general<512, false, LIN>;
+            fn = (const void *)k_smo_general<512, false, LIN, BOX>;
             e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
         }
         if (e == hipSuccess) {
             if (lds_state)
-                hipLaunchKernelGGL((k_smo_general<512, true, LIN>), dim3((unsigned)nprob), dim3(512), dyn, stream, K, ld, diag,
+                hipLaunchKernelGGL((k_smo_general<512, true, LIN, BOX>), dim3((unsigned)nprob), dim3(512), dyn, stream, K, ld, diag,
                                    dprobs, C, eps, max_iter, shrinking ? 1 : 0, cap);
             else if (gt == 512)
-                hipLaunchKernelGGL((k_smo_general<512, false, LIN>), dim3((unsigned)nprob), dim3(512), dyn, stream, K, ld, diag,
+                hipLaunchKernelGGL((k_smo_general<512, false, LIN, BOX>), dim3((unsigned)nprob), dim3(512), dyn, stream, K, ld, diag,
                                    dprobs, C, eps, max_iter, shrinking ? 1 : 0, cap);
             else
-                hipLaunchKernelGGL((k_smo_general<1024, false, LIN>), dim3((unsigned)nprob), dim3(1024), dyn, stream, K, ld,
+                hipLaunchKernelGGL((k_smo_general<1024, false, LIN, BOX>), dim3((unsigned)nprob), dim3(1024), dyn, stream, K, ld,
                                    diag, dprobs, C, eps, max_iter, shrinking ? 1 : 0, cap);
             e = hipGetLastError();
         }
@@ -1450,8 +1564,17 @@ extern "C" int gkmsvm_train_batch_general(int device, const double *K, int64_t l
                                           const int64_t *off, const int *n0, double C, double eps, int shrinking,
                                           double *alpha, double *grad, double *rho, int *iters, void *stream_)
 {
-    return train_batch_general<false>("gkmsvm_train_batch_general", device, K, ld, n, nprob, idx, off, n0, nullptr, C,
-                                      eps, shrinking, alpha, grad, rho, iters, stream_);
+    return train_batch_general<false>("gkmsvm_train_batch_general", device, K, ld, n, nprob, idx, off, n0, nullptr,
+                                      nullptr, C, eps, shrinking, alpha, grad, rho, iters, stream_);
+}
+
+extern "C" int gkmsvm_train_batch_general_boxed(int device, const double *K, int64_t ld, int n, int nprob, const int *idx,
+                                                const int64_t *off, const int *n0, const double *box, double eps,
+                                                int shrinking, double *alpha, double *grad, double *rho, int *iters,
+                                                void *stream_)
+{
+    return train_batch_general<false, true>("gkmsvm_train_batch_general_boxed", device, K, ld, n, nprob, idx, off, n0,
+                                            nullptr, box, 0.0, eps, shrinking, alpha, grad, rho, iters, stream_);
 }
 
 /* ------------------------------------------------------------------------------------------------
@@ -1525,9 +1648,9 @@ static int train_svr(const char *name, int device, const double *K, int64_t ld, 
     const dim3 grid((unsigned)((maxl + 255) / 256), (unsigned)nprob);
     hipLaunchKernelGGL(k_svr_setup, grid, dim3(256), 0, stream, d_off, idx, z, epsilon, idx2, lin);
     SVMCHK(hipGetLastError());
-    const int rc = GENERAL ? train_batch_general<true>(name, device, K, ld, n, nprob, idx2, off2.data(), n0.data(), lin, C,
+    const int rc = GENERAL ? train_batch_general<true>(name, device, K, ld, n, nprob, idx2, off2.data(), n0.data(), lin, nullptr, C,
                                                        tol, shrinking, alpha2, grad2, rho, iters, stream_)
-                           : train_batch<true>(name, device, K, ld, n, nprob, idx2, off2.data(), n0.data(), lin, C, tol,
+                           : train_batch<true>(name, device, K, ld, n, nprob, idx2, off2.data(), n0.data(), lin, nullptr, C, tol,
                                                alpha2, grad2, rho, iters, stream_);
     if (rc) return rc;
     hipLaunchKernelGGL(k_svr_coef, grid, dim3(256), 0, stream, d_off, alpha2, coef);

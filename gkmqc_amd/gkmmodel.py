@@ -11,11 +11,14 @@ from . import device as dv
 from . import svmcv
 
 FORMAT = "gkmqc-model-1"
+WEIGHTED_FORMAT = "gkmqc-model-2"      # a C-SVC trained with class weights: weight0, weight1 after C
 SVR_FORMAT = "gkmqc-svr-1"
 C_SVC, EPSILON_SVR = "c_svc", "epsilon_svr"
 _INT_KEYS = ("kernel_type", "L", "k", "d", "M", "shrinking", "n0", "n_sv")
-_FLOAT_KEYS = ("H", "gamma", "C", "tol", "rho", "epsilon")
+_FLOAT_KEYS = ("H", "gamma", "C", "weight0", "weight1", "tol", "rho", "epsilon")
 _KEYS = ("format", "kernel_type", "L", "k", "d", "M", "H", "gamma", "C", "tol", "shrinking", "rho", "n0", "n_sv")
+_WEIGHTED_KEYS = ("format", "kernel_type", "L", "k", "d", "M", "H", "gamma", "C", "weight0", "weight1", "tol", "shrinking",
+                  "rho", "n0", "n_sv")
 _SVR_KEYS = ("format", "kernel_type", "L", "k", "d", "M", "H", "gamma", "C", "tol", "shrinking", "epsilon", "rho", "n_sv")
 MAX_SVR_SAMPLES = svmcv.MAX_FOLD_SAMPLES // 2   # LIBSVM's epsilon-SVR solves 2l variables
 _ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
@@ -45,10 +48,12 @@ class Model:
     C-SVC (svm_type C_SVC): the support vectors in LIBSVM's internal order (class 0 -- the negatives -- first, n0 of
     them), `alpha` their dual variables (> 0).  epsilon-SVR (svm_type EPSILON_SVR, `epsilon` set, n0 = 0): the support
     vectors in training order, `alpha` their signed coefficients alpha_k - alpha*_k (nonzero).  For both,
-    score = sum dual_coef() K + rho: rho is scikit-learn's intercept_ (for SVR that is LIBSVM's rho negated)."""
+    score = sum dual_coef() K + rho: rho is scikit-learn's intercept_ (for SVR that is LIBSVM's rho negated).
+    `class_weight` (C-SVC only): None, or the pair (w0, w1) the model was trained with -- the weights of label 0 (the
+    negatives) and label 1 as numbers ("balanced" resolved), alpha of a class bounded by C times its weight."""
 
     def __init__(self, kernel_type, L, k, d, M, H, gamma, C, tol, shrinking, rho, n0, alpha, names, seqs, svm_type=C_SVC,
-                 epsilon=None):
+                 epsilon=None, class_weight=None):
         self.kernel_type, self.L, self.k, self.d, self.M = int(kernel_type), int(L), int(k), int(d), int(M)
         self.H, self.gamma, self.C, self.tol = float(H), float(gamma), float(C), float(tol)
         self.shrinking = bool(shrinking)
@@ -58,6 +63,12 @@ class Model:
         self.seqs = [np.ascontiguousarray(s, dtype=np.uint8) for s in seqs]
         self.svm_type = svm_type
         self.epsilon = None if epsilon is None else float(epsilon)
+        try:
+            self.class_weight = None if class_weight is None else (float(class_weight[0]), float(class_weight[1]))
+        except (TypeError, ValueError, IndexError):
+            raise ModelError("class_weight must be None or a pair of numbers")
+        if class_weight is not None and len(class_weight) != 2:
+            raise ModelError("class_weight must be None or a pair of numbers")
         _validate(self)
 
     @property
@@ -86,9 +97,14 @@ class Model:
 
     def save(self, path):
         """Write the model file (format: INTEGRATION.md).  Floats as repr(), which reads back to the same double."""
-        head = [("format", SVR_FORMAT if self.is_svr else FORMAT), ("kernel_type", self.kernel_type), ("L", self.L),
+        weighted = self.class_weight is not None
+        head = [("format", SVR_FORMAT if self.is_svr else WEIGHTED_FORMAT if weighted else FORMAT),
+                ("kernel_type", self.kernel_type), ("L", self.L),
                 ("k", self.k), ("d", self.d), ("M", self.M), ("H", repr(self.H)), ("gamma", repr(self.gamma)),
-                ("C", repr(self.C)), ("tol", repr(self.tol)), ("shrinking", int(self.shrinking))]
+                ("C", repr(self.C))]
+        if weighted:
+            head += [("weight0", repr(self.class_weight[0])), ("weight1", repr(self.class_weight[1]))]
+        head += [("tol", repr(self.tol)), ("shrinking", int(self.shrinking))]
         if self.is_svr:
             head += [("epsilon", repr(self.epsilon)), ("rho", repr(self.rho)), ("n_sv", self.n_sv)]
         else:
@@ -113,6 +129,11 @@ def _validate(m):
         raise ModelError("H, gamma and rho must be finite, C and tol positive")
     if not (len(m.alpha) == len(m.names) == len(m.seqs)) or len(m.alpha) == 0:
         raise ModelError("a model needs at least one support vector, each with alpha, name and sequence")
+    if m.class_weight is not None:
+        if m.svm_type != C_SVC:
+            raise ModelError("only a C-SVC model has class weights")
+        if not all(np.isfinite(w) and w > 0 for w in m.class_weight):
+            raise ModelError("class weights must be finite and > 0")
     if m.svm_type == EPSILON_SVR:
         if m.epsilon is None or not (np.isfinite(m.epsilon) and m.epsilon >= 0):
             raise ModelError("an SVR model needs a finite epsilon >= 0")
@@ -136,7 +157,7 @@ def _validate(m):
 
 
 def load(path):
-    """Read a model file written by Model.save (either format tag); anything malformed raises ModelError with the
+    """Read a model file written by Model.save (any of the three format tags); anything malformed raises ModelError with the
     reason."""
     with open(path) as f:
         lines = f.read().split("\n")
@@ -145,7 +166,7 @@ def load(path):
     head, i = {}, 0
     while i < len(lines) and lines[i] != "SV":
         parts = lines[i].split(" ", 1)
-        if len(parts) != 2 or parts[0] not in _KEYS + _SVR_KEYS:
+        if len(parts) != 2 or parts[0] not in _KEYS + _SVR_KEYS + _WEIGHTED_KEYS:
             raise ModelError("%s:%d: not a `key value` line of the header: %r" % (path, i + 1, lines[i]))
         if parts[0] in head:
             raise ModelError("%s:%d: key %s given twice" % (path, i + 1, parts[0]))
@@ -154,12 +175,13 @@ def load(path):
     if i == len(lines):
         raise ModelError("%s: no SV line" % path)
     svr = head.get("format") == SVR_FORMAT
-    keys = _SVR_KEYS if svr else _KEYS
+    weighted = head.get("format") == WEIGHTED_FORMAT
+    keys = _SVR_KEYS if svr else _WEIGHTED_KEYS if weighted else _KEYS
     missing = [key for key in keys if key not in head]
     if missing:
         raise ModelError("%s: missing key(s): %s" % (path, ", ".join(missing)))
-    if head["format"] not in (FORMAT, SVR_FORMAT):
-        raise ModelError("%s: format %r, expected %r or %r" % (path, head["format"], FORMAT, SVR_FORMAT))
+    if head["format"] not in (FORMAT, WEIGHTED_FORMAT, SVR_FORMAT):
+        raise ModelError("%s: format %r, expected %r, %r or %r" % (path, head["format"], FORMAT, WEIGHTED_FORMAT, SVR_FORMAT))
     extra = [key for key in head if key not in keys]
     if extra:
         raise ModelError("%s: key(s) %s do not belong to format %s" % (path, ", ".join(extra), head["format"]))
@@ -187,13 +209,28 @@ def load(path):
         return Model(val["kernel_type"], val["L"], val["k"], val["d"], val["M"], val["H"], val["gamma"], val["C"],
                      val["tol"], val["shrinking"], val["rho"], 0, alpha, names, seqs, EPSILON_SVR, val["epsilon"])
     return Model(val["kernel_type"], val["L"], val["k"], val["d"], val["M"], val["H"], val["gamma"], val["C"], val["tol"],
-                 val["shrinking"], val["rho"], val["n0"], alpha, names, seqs)
+                 val["shrinking"], val["rho"], val["n0"], alpha, names, seqs,
+                 class_weight=(val["weight0"], val["weight1"]) if weighted else None)
 
 
 # ------------------------------------------------------------------ training
+def resolve_class_weight(class_weight, y):
+    """`class_weight` of train / train_panel as numbers for the labels y: None stays None; "balanced" and a pair (w0, w1)
+    -- the weights of label 0 and label 1 -- become a pair of floats (svmcv.problem_weights)."""
+    if class_weight is None:
+        return None
+    try:
+        w = svmcv.problem_weights([np.asarray(y)], class_weight)[0]
+    except svmcv.SvmError as e:
+        raise ModelError(str(e))
+    return (float(w[0]), float(w[1]))
+
+
 def train(pos_fa, neg_fa, kernel_type=4, L=10, k=6, d=3, M=50, H=50, gamma=1.0, C=1.0, tol=1e-3, shrinking=False,
-          device=0, kernel=dv.KERNEL_AUTO):
-    """One C-SVC on every sequence of pos_fa (label 1) and neg_fa (label 0) -> Model."""
+          device=0, kernel=dv.KERNEL_AUTO, class_weight=None):
+    """One C-SVC on every sequence of pos_fa (label 1) and neg_fa (label 0) -> Model.
+    class_weight: None, "balanced" (l / (2 * count) per class, as scikit-learn) or a pair (w0, w1), the weights of label 0
+    and label 1: alpha of a class is bounded by C times its weight (scikit-learn's `class_weight`, LIBSVM's -wi)."""
     import torch
     bad = dv.check_parameters(kernel_type, L, k, d)
     if bad:
@@ -206,10 +243,11 @@ def train(pos_fa, neg_fa, kernel_type=4, L=10, k=6, d=3, M=50, H=50, gamma=1.0, 
                             np.concatenate((pos.off, pos.off[-1] + neg.off[1:])))
     names = pos_names + neg_names
     y = np.concatenate((np.repeat(1, len(pos)), np.repeat(0, len(neg))))
+    weights = resolve_class_weight(class_weight, y)
     res = dv.gram_matrix(seqs, kernel_type, L, k, d, M, H, gamma, device, kernel=kernel, symmetric=True,
                          keep_context=True)
     K = res["K"]
-    sol, _ = svmcv.train_folds(K, [np.arange(len(y))], y, C, tol, shrinking)
+    sol, _ = svmcv.train_folds(K, [np.arange(len(y))], y, C, tol, shrinking, class_weight=weights)
     if sol.iters[0] >= 0:
         a, order = sol.alpha[0], sol.idx[0]
         sv = np.nonzero(a > 0)[0]
@@ -217,13 +255,42 @@ def train(pos_fa, neg_fa, kernel_type=4, L=10, k=6, d=3, M=50, H=50, gamma=1.0, 
     else:   # the GPU solver's iteration cap: the reference's solver has none (as svmcv.crossValidate)
         from sklearn.svm import SVC
         logging.warning("training re-solved with scikit-learn (iteration cap of the GPU solver)")
-        m = SVC(kernel="precomputed", C=C, tol=tol, shrinking=bool(shrinking)).fit(K.cpu().numpy(), y)
+        m = SVC(kernel="precomputed", C=C, tol=tol, shrinking=bool(shrinking),
+                class_weight=None if weights is None else {0: weights[0], 1: weights[1]}).fit(K.cpu().numpy(), y)
         # (for two classes scikit-learn negates LIBSVM's coefficients and decision value, so intercept_ is LIBSVM's rho)
         idx, alpha, rho = m.support_, np.abs(m.dual_coef_[0]), float(m.intercept_[0])
     del K, res
     torch.cuda.empty_cache()
     return Model(kernel_type, L, k, d, M, H, gamma, C, tol, shrinking, rho, int((y[idx] == 0).sum()), alpha,
-                 [names[i] for i in idx], [seqs[i] for i in idx])
+                 [names[i] for i in idx], [seqs[i] for i in idx], class_weight=weights)
+
+
+def select(pos_fa, neg_fa, Cs, class_weights=(None,), ncv=5, repeats=1, seed=1, kernel_type=4, L=10, k=6, d=3, M=50, H=50,
+           gamma=1.0, tol=1e-3, shrinking=False, device=0, kernel=dv.KERNEL_AUTO):
+    """Cross-validate every setting of the grid `Cs` x `class_weights` on ONE Gram matrix of pos_fa (label 1) and neg_fa
+    (label 0) and one solver launch (svmcv.cross_validate_grid) -> (records, index of the best one).  Best: the highest
+    mean AUC; on a tie the smaller C, then the earlier entry of class_weights."""
+    import torch
+    bad = dv.check_parameters(kernel_type, L, k, d)
+    if bad:
+        raise ModelError("kernel parameters rejected: %s" % bad)
+    pos, _, _, _ = dv.read_fasta(pos_fa)
+    neg, _, _, _ = dv.read_fasta(neg_fa)
+    if len(pos) < ncv or len(neg) < ncv:
+        raise ModelError("cross-validation needs at least ncv = %d sequences of each class" % ncv)
+    seqs = dv.FlatSequences(np.concatenate((pos.codes, neg.codes)),
+                            np.concatenate((pos.off, pos.off[-1] + neg.off[1:])))
+    res = dv.gram_matrix(seqs, kernel_type, L, k, d, M, H, gamma, device, kernel=kernel, symmetric=True,
+                         keep_context=True)
+    K = res["K"]
+    try:
+        records = svmcv.cross_validate_grid(K, len(pos), len(neg), Cs, class_weights, ncv, repeats, seed, tol, shrinking)
+    except svmcv.SvmError as e:
+        raise ModelError(str(e))
+    finally:
+        del K, res
+        torch.cuda.empty_cache()
+    return records, svmcv.best_record(records)
 
 
 def read_targets(path, names):

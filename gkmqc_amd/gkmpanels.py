@@ -7,7 +7,7 @@ matrix, and any list of models that share their kernel parameters folded into a 
                   model, and k_panel_weights over all 4^L codes straight into the panel's device image; column m is
                   lmer_weights(models[m]).W bit for bit
 
-    python -m gkmqc_amd.gkmpanels train [-t -L -k -d -M -H -G -C -e -u] [--panel out.npz] seqs.fa labels.tsv out_prefix
+    python -m gkmqc_amd.gkmpanels train [-t -L -k -d -M -H -G -C -e -u] [--class-weight none|balanced|W0:W1] [--panel out.npz] seqs.fa labels.tsv out_prefix
     python -m gkmqc_amd.gkmpanels fold [--names a,b,...] out.npz model.txt [model.txt ...]
 
 `train` writes out_prefix.<task>.model.txt per task (and the folded panel with --panel); `fold` reads model files.  The
@@ -25,8 +25,9 @@ import numpy as np
 
 from . import device as dv
 from . import svmcv
-from .gkmmodel import Model, ModelError, load
+from .gkmmodel import Model, ModelError, load, resolve_class_weight
 from .gkmpredict import _DEVICE, _TRAIN, _opt, check_train_args
+from .gkmselect import _CLASS_WEIGHT, parse_class_weight
 from .gkmquery import _exact_norms
 from .gkmtables import (_PANEL_SHARED, PANEL_MAX_MODELS, TABLE_PIECE, LmerPanel, _check_panel_names, _check_panel_size,
                         check_table_model, lmer_classes, panel_row_stride)
@@ -95,13 +96,15 @@ def task_problems(Y):
 
 
 def train_panel(fasta, labels, kernel_type=4, L=10, k=6, d=3, M=50, H=50, gamma=1.0, C=1.0, tol=1e-3, shrinking=False,
-                device=0):
+                device=0, class_weight=None):
     """One C-SVC per task of a labelled pool -> (task names, [Model]).  fasta: the pool; labels: a label file
     (read_labels) or (task names, Y) with Y (records, tasks) of 1, 0 and NOT_IN_TASK.  One Gram matrix of the pool and
     one svmcv.train_tasks call: every task's kernel matrix is a sub-matrix of the pool's (K[i, j] depends on the pair
     alone, bit for bit), and a task is its index list in LIBSVM's order.  models[t].save writes the bytes that
     `train(pos_t.fa, neg_t.fa, ...)` writes for the task's label-1 and label-0 records in pool order.  A task that stops
-    at the GPU solver's iteration cap is re-solved with scikit-learn, as `train` does, that task alone."""
+    at the GPU solver's iteration cap is re-solved with scikit-learn, as `train` does, that task alone.
+    class_weight (None, "balanced" or a pair (w0, w1), as `train`): "balanced" is resolved per task from the task's own
+    counts, and the contract holds with the same argument: train(pos_t.fa, neg_t.fa, ..., class_weight=class_weight)."""
     import torch
     bad = dv.check_parameters(kernel_type, L, k, d)
     if bad:
@@ -123,7 +126,8 @@ def train_panel(fasta, labels, kernel_type=4, L=10, k=6, d=3, M=50, H=50, gamma=
     trains, labs = task_problems(Y)
     res = dv.gram_matrix(seqs, kernel_type, L, k, d, M, H, gamma, device, symmetric=True, keep_context=True)
     K = res["K"]
-    sol, _ = svmcv.train_tasks(K, trains, labs, C, tol, shrinking)
+    weights = [resolve_class_weight(class_weight, lab) for lab in labs]
+    sol, _ = svmcv.train_tasks(K, trains, labs, C, tol, shrinking, class_weight=None if class_weight is None else weights)
     models = []
     for t, (tr, lab) in enumerate(zip(trains, labs)):
         if sol.iters[t] >= 0:
@@ -133,12 +137,13 @@ def train_panel(fasta, labels, kernel_type=4, L=10, k=6, d=3, M=50, H=50, gamma=
         else:   # the GPU solver's iteration cap: the reference's solver has none (as gkmmodel.train)
             from sklearn.svm import SVC
             logging.warning("task %s re-solved with scikit-learn (iteration cap of the GPU solver)", tasks[t])
-            m = SVC(kernel="precomputed", C=C, tol=tol, shrinking=bool(shrinking))
+            m = SVC(kernel="precomputed", C=C, tol=tol, shrinking=bool(shrinking),
+                    class_weight=None if weights[t] is None else {0: weights[t][0], 1: weights[t][1]})
             m.fit(svmcv.device_block(K, tr, tr).cpu().numpy(), lab)
             idx, alpha, rho = tr[m.support_], np.abs(m.dual_coef_[0]), float(m.intercept_[0])
         n0 = int((Y[idx, t] == 0).sum())
         models.append(Model(kernel_type, L, k, d, M, H, gamma, C, tol, shrinking, rho, n0, alpha,
-                            [names[i] for i in idx], [seqs[i] for i in idx]))
+                            [names[i] for i in idx], [seqs[i] for i in idx], class_weight=weights[t]))
     del K, res
     torch.cuda.empty_cache()
     return tasks, models
@@ -233,6 +238,7 @@ def _run_train(a):
     bad = check_train_args(a)
     if bad:
         raise ModelError(bad)
+    weights = parse_class_weight(a.class_weight)
     for path in (a.seqs_fa, a.labels):
         if not os.path.isfile(path):
             raise ModelError("cannot read %s" % path)
@@ -243,7 +249,8 @@ def _run_train(a):
             raise ModelError("train: the task name %r cannot be part of a file name" % task)
     tasks, models = train_panel(a.seqs_fa, (tasks, Y), a.kernel_type, a.full_word_length, a.non_gap_length,
                                 a.max_num_gaps, a.init_decay, a.half_life_decay, a.rbf_gamma, a.regularization,
-                                a.precision, bool(a.shrinking), a.device)
+                                a.precision, bool(a.shrinking), a.device,
+                                **({} if weights is None else dict(class_weight=weights)))
     panel = fold_panel(models, tasks, a.device) if a.panel is not None else None
     for task, m in zip(tasks, models):     # (Model.save and LmerPanel.save put a complete file in place or none)
         m.save(model_path(a.out_prefix, task))
@@ -275,7 +282,7 @@ Command = collections.namedtuple("Command", "help options positionals run")
 COMMANDS = {
     "train": Command("train one model per task of labels.tsv on the pool seqs.fa from one Gram matrix: "
                      "out_prefix.<task>.model.txt per task",
-                     _TRAIN + (_DEVICE, _opt("--panel", default=None, help="also fold the models into this panel file")),
+                     _TRAIN + (_CLASS_WEIGHT, _DEVICE, _opt("--panel", default=None, help="also fold the models into this panel file")),
                      ("seqs_fa", "labels", "out_prefix"), _run_train),
     "fold": Command("fold 1..64 model files that share their kernel parameters into a panel file in one pass",
                     (_opt("--names", default=None, help="comma-separated member names (default: the files' basenames)"),

@@ -36,6 +36,10 @@ def _lib():
         L.gkmsvm_train_batch.argtypes = (i32, vp, i64, i32, i32, vp, vp, vp, dbl, dbl, vp, vp, vp, vp, vp)
         L.gkmsvm_train_batch_general.restype = i32
         L.gkmsvm_train_batch_general.argtypes = (i32, vp, i64, i32, i32, vp, vp, vp, dbl, dbl, i32, vp, vp, vp, vp, vp)
+        L.gkmsvm_train_batch_boxed.restype = i32
+        L.gkmsvm_train_batch_boxed.argtypes = (i32, vp, i64, i32, i32, vp, vp, vp, vp, dbl, vp, vp, vp, vp, vp)
+        L.gkmsvm_train_batch_general_boxed.restype = i32
+        L.gkmsvm_train_batch_general_boxed.argtypes = (i32, vp, i64, i32, i32, vp, vp, vp, vp, dbl, i32, vp, vp, vp, vp, vp)
         L.gkmsvm_decision_batch.restype = i32
         L.gkmsvm_decision_batch.argtypes = (i32, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp)
         L.gkmsvm_train_svr_batch.restype = i32
@@ -71,10 +75,12 @@ def _class_order(train, lab):
 
 
 class FoldSolutions:
-    """Result of `train_folds`: per-fold alpha (LIBSVM order), rho, iteration count."""
+    """Result of `train_folds`: per-fold alpha (LIBSVM order), rho, iteration count, and `box`: the (nprob, 2) upper
+    bounds of alpha, of the class-0 positions and of the rest (`problem_boxes`; (C, C) for a plain C)."""
 
-    def __init__(self, idx, n0, alpha, grad, rho, iters):
+    def __init__(self, idx, n0, alpha, grad, rho, iters, box=None):
         self.idx, self.n0, self.alpha, self.grad, self.rho, self.iters = idx, n0, alpha, grad, rho, iters
+        self.box = box
 
     def dual_coef(self, f):
         """sklearn's `dual_coef_[0]` and `support_` of fold f (positions in the fold's `train`)."""
@@ -84,13 +90,79 @@ class FoldSolutions:
         return -(a[sv] * ysign[sv]), self.idx[f][sv]
 
 
-def train_folds(K, trains, y, C=1.0, tol=1e-3, shrinking=False, about_to_launch=None):
+def train_folds(K, trains, y, C=1.0, tol=1e-3, shrinking=False, about_to_launch=None, class_weight=None):
     """Solve one C-SVC per entry of `trains` (index arrays into the symmetric torch CUDA fp64
     matrix K) concurrently.  Returns (FoldSolutions, device handles for `decision_values`).
     `shrinking`: LIBSVM's shrinking heuristic (scikit-learn `SVC(shrinking=True)`); it and folds of more
-    than 16 384 samples run on the general solver (k_smo_general), everything else on k_smo."""
+    than 16 384 samples run on the general solver (k_smo_general), everything else on k_smo.
+    `C`, `class_weight`: one value, or one per problem (`problem_boxes`)."""
     y = np.asarray(y)
-    return train_tasks(K, trains, [y[np.asarray(t)] for t in trains], C, tol, shrinking, about_to_launch)
+    return train_tasks(K, trains, [y[np.asarray(t)] for t in trains], C, tol, shrinking, about_to_launch, class_weight)
+
+
+def _is_pair(w):
+    return (isinstance(w, (tuple, list, np.ndarray)) and len(w) == 2
+            and all(isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool) for x in w))
+
+
+def problem_weights(labels, class_weight=None):
+    """The class weights of every problem as numbers -> (nprob, 2) float64: column 0 weighs the class that sorts first
+    (label 0), column 1 the other (label 1).  `class_weight`: None (1, 1); "balanced", resolved per problem to
+    l / (2 * count of the class) in float64 -- scikit-learn's n_samples / (n_classes * np.bincount(y)); a pair
+    (w0, w1); or a sequence of one of those per problem.  Weights that are not finite or not > 0 raise SvmError."""
+    nprob = len(labels)
+    if class_weight is None or isinstance(class_weight, str) or _is_pair(class_weight):
+        per = [class_weight] * nprob
+    else:
+        try:
+            per = list(class_weight)
+        except TypeError:
+            raise SvmError("class_weight: None, 'balanced', a pair (w0, w1) or one of those per problem")
+        if len(per) != nprob:
+            raise SvmError("%d class weightings for %d problems" % (len(per), nprob))
+    w = np.ones((nprob, 2), dtype=np.float64)
+    for t, (cw, lab) in enumerate(zip(per, labels)):
+        if cw is None:
+            continue
+        if isinstance(cw, str):
+            if cw != "balanced":
+                raise SvmError("class_weight: unknown setting %r" % (cw,))
+            lab = np.asarray(lab)
+            classes, counts = np.unique(lab, return_counts=True)
+            if len(classes) != 2:
+                raise SvmError("a fold needs samples of exactly two classes")
+            w[t] = np.float64(lab.size) / (2 * counts).astype(np.float64)
+        elif _is_pair(cw):
+            w[t] = (float(cw[0]), float(cw[1]))
+        else:
+            raise SvmError("class_weight: None, 'balanced', a pair (w0, w1) or one of those per problem")
+    if not (np.isfinite(w).all() and (w > 0).all()):
+        raise SvmError("class weights must be finite and > 0")
+    return w
+
+
+def problem_boxes(labels, C=1.0, class_weight=None):
+    """The bounds the boxed solver entries take (include/gkm_svm.h) -> (nprob, 2) float64:
+    box[t] = (C_t * w_t[0], C_t * w_t[1]), each one rounded float64 product -- what LIBSVM computes from scikit-learn's
+    `class_weight_` (Cp and Cn; class 0 is LIBSVM's y = +1).  `C`: one float or one per problem; `class_weight`: see
+    `problem_weights`.  A C or a weight that is not finite or not > 0 raises SvmError."""
+    nprob = len(labels)
+    w = problem_weights(labels, class_weight)
+    try:
+        Cs = np.asarray(C, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise SvmError("C: one float or one per problem")
+    if Cs.ndim == 0:
+        Cs = np.repeat(Cs, nprob)
+    if Cs.shape != (nprob,):
+        raise SvmError("%d values of C for %d problems" % (Cs.size, nprob))
+    if not (np.isfinite(Cs).all() and (Cs > 0).all()):
+        raise SvmError("C must be finite and > 0")
+    with np.errstate(over="ignore", under="ignore"):
+        box = Cs[:, None] * w
+    if not (np.isfinite(box).all() and (box > 0).all()):
+        raise SvmError("C times a class weight must be finite and > 0")
+    return np.ascontiguousarray(box)
 
 
 def task_orders(trains, labels):
@@ -101,10 +173,13 @@ def task_orders(trains, labels):
     return [_class_order(t, lab) for t, lab in zip(trains, labels)]
 
 
-def train_tasks(K, trains, labels, C=1.0, tol=1e-3, shrinking=False, about_to_launch=None):
+def train_tasks(K, trains, labels, C=1.0, tol=1e-3, shrinking=False, about_to_launch=None, class_weight=None):
     """train_folds with a label vector of its own per problem: labels[t][j] is the label of sample trains[t][j].  A
     problem is its index list in LIBSVM's order and the size of class 0, so the tasks of one labelled pool (one label
-    column each, over any subset of the pool) are solved concurrently from the pool's one matrix."""
+    column each, over any subset of the pool) are solved concurrently from the pool's one matrix.
+    With one scalar `C` and `class_weight=None` every problem shares the box C (the unboxed solver entries); with a `C`
+    per problem or class weights (`problem_boxes`) each problem has a bound per class, so a grid of settings is one
+    launch (the boxed entries: same solvers, same choice between them)."""
     import torch
     if not (K.is_cuda and K.dtype == torch.float64 and K.dim() == 2 and K.shape[0] == K.shape[1]
             and K.stride(1) == 1):
@@ -116,6 +191,10 @@ def train_tasks(K, trains, labels, C=1.0, tol=1e-3, shrinking=False, about_to_la
     n0 = np.array([o[1] for o in orders], dtype=np.int32)
     off = np.zeros(len(idx) + 1, dtype=np.int64)
     off[1:] = np.cumsum([len(i) for i in idx])
+    boxed = not (np.ndim(C) == 0 and class_weight is None)
+    if boxed:
+        box = problem_boxes(labels, C, class_weight)
+        return _train_boxed(K, L, idx, n0, off, box, tol, shrinking, about_to_launch)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
         d_idx = torch.from_numpy(np.concatenate(idx)).to(dev)
@@ -157,7 +236,49 @@ def train_tasks(K, trains, labels, C=1.0, tol=1e-3, shrinking=False, about_to_la
         # scikit-learn (max_iter=-1) would have kept iterating: these folds are not the reference's solution
         logging.warning("SMO stopped at the iteration cap in %d fold(s)", int((iters < 0).sum()))
     sol = FoldSolutions(idx, n0, [alpha[off[f]:off[f + 1]] for f in range(len(idx))],
-                        [grad[off[f]:off[f + 1]] for f in range(len(idx))], rho, iters)
+                        [grad[off[f]:off[f + 1]] for f in range(len(idx))], rho, iters,
+                        np.full((len(idx), 2), float(C)))
+    return sol, dict(idx=d_idx, off=off, n0=n0, alpha=d_alpha, rho=d_rho)
+
+
+def _train_boxed(K, L, idx, n0, off, box, tol, shrinking, about_to_launch):
+    """train_tasks' launch with a box per problem: gkmsvm_train_batch_boxed / gkmsvm_train_batch_general_boxed, chosen
+    and retried as the unboxed pair."""
+    import torch
+    dev = K.device
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        d_idx = torch.from_numpy(np.concatenate(idx)).to(dev)
+        d_alpha = torch.empty(int(off[-1]), dtype=torch.float64, device=dev)
+        d_grad = torch.empty_like(d_alpha)
+        d_rho = torch.empty(len(idx), dtype=torch.float64, device=dev)
+        d_it = torch.empty(len(idx), dtype=torch.int32, device=dev)
+        head = (dev.index or 0, K.data_ptr(), K.stride(0), K.shape[0], len(idx), d_idx.data_ptr(), off.ctypes.data,
+                n0.ctypes.data, box.ctypes.data, float(tol))
+        outs = (d_alpha.data_ptr(), d_grad.data_ptr(), d_rho.data_ptr(), d_it.data_ptr(), stream)
+        if about_to_launch is not None:
+            about_to_launch()
+        if shrinking or max(len(i) for i in idx) > FAST_FOLD_SAMPLES:
+            rc = L.gkmsvm_train_batch_general_boxed(*head, 1 if shrinking else 0, *outs)
+        else:
+            rc = L.gkmsvm_train_batch_boxed(*head, *outs)
+            if rc == SHAPE_REFUSED:   # as the unboxed pair: only a launch shape the device refuses is retried
+                first = L.gkmsvm_last_error().decode()
+                logging.warning("k_smo: %s: solving with the general GPU solver", first)
+                rc = L.gkmsvm_train_batch_general_boxed(*head, 0, *outs)
+                if rc:
+                    raise SvmError("gkmsvm_train_batch_boxed: %s; then gkmsvm_train_batch_general_boxed: %s"
+                                   % (first, L.gkmsvm_last_error().decode()))
+        if rc:
+            raise SvmError("gkmsvm_train_batch_boxed: %s" % L.gkmsvm_last_error().decode())
+        alpha = d_alpha.cpu().numpy()
+        grad = d_grad.cpu().numpy()
+        rho = d_rho.cpu().numpy()
+        iters = d_it.cpu().numpy()
+    if (iters < 0).any():
+        logging.warning("SMO stopped at the iteration cap in %d fold(s)", int((iters < 0).sum()))
+    sol = FoldSolutions(idx, n0, [alpha[off[f]:off[f + 1]] for f in range(len(idx))],
+                        [grad[off[f]:off[f + 1]] for f in range(len(idx))], rho, iters, box)
     return sol, dict(idx=d_idx, off=off, n0=n0, alpha=d_alpha, rho=d_rho)
 
 
@@ -366,3 +487,59 @@ def crossValidate(args_svm, K, n_pseqs, n_nseqs, about_to_launch=None, plan=None
     aucs = [u_auc[w] for w in which]
     logging.info("cross-validation finished")
     return (np.mean(aucs), np.std(aucs))
+
+
+def cross_validate_grid(K, n_pseqs, n_nseqs, Cs, class_weights=(None,), ncv=5, repeats=1, seed=1, tol=1e-3,
+                        shrinking=False):
+    """`crossValidate` for every setting of a grid at once: `Cs` x `class_weights` (entries as `problem_weights` takes:
+    None, "balanced" or a pair (w0, w1) for labels 0 = negative and 1 = positive) on the folds of `plan_folds` -- the same
+    folds for every setting.  Every (setting, distinct fold) problem goes into ONE `train_tasks` launch and one
+    `decision_values` call on the resident matrix K; the AUC is scikit-learn's.  A problem that stops at the iteration
+    cap is re-solved with scikit-learn (that problem alone) and counted.
+    -> one record per setting, C outermost: dict(C, class_weight (as given), auc_mean, auc_std, capped).  The record of
+    (C, None) holds exactly the two floats `crossValidate` returns for that C with the same ncv, repeats and seed."""
+    from sklearn.metrics import roc_auc_score
+    Cs, class_weights = list(Cs), list(class_weights)
+    if not Cs or not class_weights:
+        raise SvmError("the grid needs at least one C and one class weighting")
+    plan = plan_folds((None, tol, shrinking, None, ncv, repeats, 0, seed), n_pseqs, n_nseqs)
+    y, which, u_trains, u_tests = plan["y"], plan["which"], plan["u_trains"], plan["u_tests"]
+    settings = [(C, cw) for C in Cs for cw in class_weights]
+    nf = len(u_trains)
+    trains = [u_trains[f] for _ in settings for f in range(nf)]
+    tests = [u_tests[f] for _ in settings for f in range(nf)]
+    labels = [y[t] for t in trains]
+    C_of = [float(C) for C, _ in settings for _f in range(nf)]
+    cw_of = [cw for _, cw in settings for _f in range(nf)]
+    weights = problem_weights(labels, cw_of)
+    logging.info("grid cross-validation on the GPU: %d settings x %d distinct folds in one launch", len(settings), nf)
+    sol, handles = train_tasks(K, trains, labels, C_of, tol, bool(shrinking), None, cw_of)
+    scores = decision_values(K, handles, tests)
+    capped = [t for t in range(len(trains)) if sol.iters[t] < 0]
+    if capped:
+        from sklearn.svm import SVC
+        logging.warning("%d problem(s) re-solved with scikit-learn (iteration cap of the GPU solver)", len(capped))
+        for t in capped:
+            tr, te = trains[t], tests[t]
+            sv = SVC(kernel="precomputed", C=C_of[t], tol=tol, shrinking=bool(shrinking),
+                     class_weight={0: float(weights[t, 0]), 1: float(weights[t, 1])})
+            sv.fit(device_block(K, tr, tr).cpu().numpy(), y[tr])
+            scores[t] = sv.decision_function(device_block(K, te, tr).cpu().numpy())
+    records = []
+    for s, (C, cw) in enumerate(settings):
+        u_auc = [roc_auc_score(y[tests[s * nf + f]], scores[s * nf + f]) for f in range(nf)]
+        aucs = [u_auc[w] for w in which]
+        records.append(dict(C=C, class_weight=cw, auc_mean=np.mean(aucs), auc_std=np.std(aucs),
+                            capped=sum(1 for t in capped if t // nf == s)))
+    return records
+
+
+def best_record(records):
+    """Index of the best record of `cross_validate_grid`: the highest mean AUC; on a tie the smaller C, then the
+    earlier entry (the earlier class weighting of one C)."""
+    best = 0
+    for r in range(1, len(records)):
+        a, b = records[r], records[best]
+        if a["auc_mean"] > b["auc_mean"] or (a["auc_mean"] == b["auc_mean"] and a["C"] < b["C"]):
+            best = r
+    return best

@@ -63,6 +63,24 @@ int gkmsvm_train_batch_general(int device, const double *K, int64_t ld, int n, i
                                double *grad, double *rho, int *iters, void *stream);
 
 /*
+ * The two entries above with a box per problem and per class instead of one C per launch (LIBSVM's `-wi`, scikit-learn's
+ * `class_weight`, and a grid of C values in one launch):
+ *   box          HOST array, nprob x 2 doubles: box[2p] bounds the class-0 positions of problem p (the first n0[p], y = +1),
+ *                box[2p + 1] the rest -- LIBSVM's Cp = C * weight[0] and Cn = C * weight[1] in this order of the classes.
+ *                alpha of a position lies in 0..its class's bound.
+ * Everything else -- arguments, size limits (16 384 / 60 000 samples), outputs, iteration cap, GKMSVM_RC_SHAPE_REFUSED,
+ * the scratch pool, the environment knobs -- is as for the unboxed entries, and with box[2p] == box[2p + 1] == C the
+ * results are their bits.  A bound that is not finite or not > 0 returns 2 and writes nothing.  The unboxed entries run
+ * kernel instantiations of their own, which never read a box.
+ */
+int gkmsvm_train_batch_boxed(int device, const double *K, int64_t ld, int n, int nprob, const int *idx, const int64_t *off,
+                             const int *n0, const double *box, double eps, double *alpha, double *grad, double *rho,
+                             int *iters, void *stream);
+int gkmsvm_train_batch_general_boxed(int device, const double *K, int64_t ld, int n, int nprob, const int *idx,
+                                     const int64_t *off, const int *n0, const double *box, double eps, int shrinking,
+                                     double *alpha, double *grad, double *rho, int *iters, void *stream);
+
+/*
  * Decision values of problem p for its test samples, in LIBSVM's summation order:
  *   dec[t] = sum_{k in training order, alpha_k > 0} alpha_k y_k K(test_t, train_k) - rho
  * (scikit-learn's decision_function returns the negative of this for a two-class problem).
