@@ -63,6 +63,10 @@
  *                          or the lanes across models and a serial walk, then a fold launch over the tiles' partials
  *                          (k_lmer_contract, k_panel_contract, k_contract_fold), gkmhip_lmer_contract,
  *                          gkmhip_panel_contract, gkmhip_contract_max_windows, gkmhip_contract_scratch_bytes
+ *   gkm_knn.hip            what is kept of a block of kernel values: the best columns of every row merged into a running
+ *                          list under a total order, one wave per row and one entry per lane, and the cells at or above a
+ *                          threshold counted and listed by ballots (k_knn_merge, k_pairs_count, k_pairs_fill),
+ *                          gkmhip_knn_merge, gkmhip_pairs_count, gkmhip_pairs_fill; needs no context
  */
 #ifndef GKM_INTERNAL_H
 #define GKM_INTERNAL_H

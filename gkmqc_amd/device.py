@@ -366,6 +366,53 @@ def contract_scratch_bytes(L, n_models, nwin):
     return int(_contract_lib().gkmhip_contract_scratch_bytes(int(L), int(n_models), int(nwin)))
 
 
+_KNN_LIB = None
+
+
+def _knn_lib():
+    global _KNN_LIB
+    if _KNN_LIB is None:
+        lib = load()
+        if not hasattr(lib, "gkmhip_knn_merge"):
+            raise GkmError("%s holds no gkmhip_knn_merge: it was built before the neighbour calls" % lib_path())
+        vp, i32, i64, dbl = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double
+        lib.gkmhip_knn_merge.restype = i32
+        lib.gkmhip_knn_merge.argtypes = (i32, vp, i64, i64, i64, vp, i64, i32, i32, vp, vp, vp)
+        lib.gkmhip_pairs_count.restype = i32
+        lib.gkmhip_pairs_count.argtypes = (i32, vp, i64, i64, i64, vp, i64, i32, dbl, vp, vp)
+        lib.gkmhip_pairs_fill.restype = i32
+        lib.gkmhip_pairs_fill.argtypes = (i32, vp, i64, i64, i64, vp, i64, i32, dbl, vp, i64, vp, vp, vp, vp)
+        _KNN_LIB = lib
+    return _KNN_LIB
+
+
+def _knn_chk(rc, what):
+    if rc:
+        raise GkmError("%s failed (%d): %s" % (what, rc, load().gkmhip_last_error().decode()))
+
+
+def knn_merge(device, K_ptr, ld, nrows, ncols, row_id_ptr, col_base, mode, kcap, best_idx_ptr, best_val_ptr, stream=0):
+    """The eligible cells of a device block merged into every row's running list of its kcap best columns (include/
+    gkm_hip.h gkmhip_knn_merge): all arguments but the sizes are device pointers; one call per column block."""
+    _knn_chk(_knn_lib().gkmhip_knn_merge(int(device), K_ptr, int(ld), int(nrows), int(ncols), row_id_ptr, int(col_base),
+                                         int(mode), int(kcap), best_idx_ptr, best_val_ptr, stream), "gkmhip_knn_merge")
+
+
+def pairs_count(device, K_ptr, ld, nrows, ncols, row_id_ptr, col_base, mode, threshold, count_ptr, stream=0):
+    """count[i] = the eligible cells of row i at or above `threshold` (gkmhip_pairs_count); count: device int64."""
+    _knn_chk(_knn_lib().gkmhip_pairs_count(int(device), K_ptr, int(ld), int(nrows), int(ncols), row_id_ptr, int(col_base),
+                                           int(mode), float(threshold), count_ptr, stream), "gkmhip_pairs_count")
+
+
+def pairs_fill(device, K_ptr, ld, nrows, ncols, row_id_ptr, col_base, mode, threshold, offset_ptr, capacity, out_i_ptr,
+               out_j_ptr, out_v_ptr, stream=0):
+    """Those cells as (row_id[i], column, value) from slot offset[i] on, ascending column within a row
+    (gkmhip_pairs_fill); nothing is written at or beyond `capacity`."""
+    _knn_chk(_knn_lib().gkmhip_pairs_fill(int(device), K_ptr, int(ld), int(nrows), int(ncols), row_id_ptr, int(col_base),
+                                          int(mode), float(threshold), offset_ptr, int(capacity), out_i_ptr, out_j_ptr,
+                                          out_v_ptr, stream), "gkmhip_pairs_fill")
+
+
 class FlatSequences:
     """All sequences of a problem back to back: `codes` (uint8, 0..3) and `off` (int64, n+1).
     Behaves like a list of per-sequence arrays (views) where one is needed."""

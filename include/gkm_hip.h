@@ -569,6 +569,37 @@ int gkmhip_nullidx_cells(int device, const uint32_t *key, int64_t T, int t, int3
 int gkmhip_nullidx_sort(int device, const uint32_t *key, int64_t T, int t, int32_t *pos, void *scratch, int64_t scratch_bytes,
                         void *stream);
 
+/* ---- nearest columns and cells above a threshold of a block of kernel values (gkm_knn.hip) ----
+ * K: any DEVICE matrix of doubles, nrows x ncols with leading dimension ld >= ncols -- a block written by
+ * gkmhip_gram_block + gkmhip_normalize_block, or a resident matrix.  Column j of the block is the global column
+ * c = col_base + j; row_id: DEVICE int32[nrows], the global column that is row i's own, -1 for none.  Cell (i, j) is
+ * ELIGIBLE iff K[i ld + j] is not a NaN and c != row_id[i] (mode 0) or c > row_id[i] (mode 1: the upper triangle).
+ * Like the nullidx calls these take no context (a device index, DEVICE pointers and a stream) and keep no events: a
+ * caller times them with events of its own.  Each refuses with error 2, nothing launched and nothing written: a NULL
+ * pointer, negative nrows or ncols, nrows >= 2^25, ld < ncols, col_base < 0 or col_base + ncols >= 2^31, a mode other
+ * than 0 and 1 (and what is named below).  nrows = 0 is served and launches nothing.  Every output is the same bytes on
+ * every run: no atomic places or orders anything.
+ *
+ * gkmhip_knn_merge: best_idx int32[nrows kcap], best_val double[nrows kcap], 1 <= kcap <= 64 (else error 2): row i's
+ * running list, larger value first and on equal values (-0.0 == 0.0) the lower global column first; the cell's own bits
+ * are kept.  Unfilled entries are idx -1, val NaN at the end, which is also the state the caller writes before the first
+ * call.  The call merges the eligible cells of the block into the lists, so it is made once per column block.  This is a
+ * selection under a strict total order (a row's eligible cells have distinct columns): the final lists are the same
+ * bytes whatever the cut into column blocks and whatever the order of the calls.  Rows whose list does not change are
+ * not written. */
+int gkmhip_knn_merge(int device, const double *K, int64_t ld, int64_t nrows, int64_t ncols, const int32_t *row_id,
+                     int64_t col_base, int mode, int kcap, int32_t *best_idx, double *best_val, void *stream);
+/* count[i] (DEVICE int64[nrows], overwritten) = the eligible cells of row i with a value >= threshold (a NaN threshold:
+ * none) */
+int gkmhip_pairs_count(int device, const double *K, int64_t ld, int64_t nrows, int64_t ncols, const int32_t *row_id,
+                       int64_t col_base, int mode, double threshold, int64_t *count, void *stream);
+/* Row i writes those cells in ascending column at the slots offset[i], offset[i] + 1, ...: out_i = row_id[i], out_j = c,
+ * out_v = the value.  offset: DEVICE int64[nrows], the exclusive prefix of the counts plus what earlier calls wrote.
+ * A slot at or beyond capacity (or below 0) is not written; a negative capacity is refused. */
+int gkmhip_pairs_fill(int device, const double *K, int64_t ld, int64_t nrows, int64_t ncols, const int32_t *row_id,
+                      int64_t col_base, int mode, double threshold, const int64_t *offset, int64_t capacity, int32_t *out_i,
+                      int32_t *out_j, double *out_v, void *stream);
+
 /* sqnorm[i] = sqrt(G(i,i)) for all uploaded sequences (device array of n doubles), computed
  * from the diagonal band only (~1 % of the work of the whole matrix).  Replaces
  * gkmkernel_kernelfunc_sqnorm_single, src/libgkm.c:723-759. */
